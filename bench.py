@@ -15,6 +15,14 @@ Every report is fully recomputed by the kernels; the final aggregate is checked 
 multiplicity * the oracle's pool aggregate.
 
 Launch: python bench.py [--gpus N --steps K --warmup W]; for N > 1 via torch.distributed.run.
+
+A plain run does what the headline figure needs and no more: it generates the inputs (a pool of 4,096
+distinct reports, client + leader only), warms up, times the K steps, writes the outputs of the last
+timed step when `--dump-outputs DIR` is given, and prints the result line (value, ms_per_step, the
+HIP-event kernel times of the timed steps). `--full` adds everything else, as one run: the 32,768-report
+pool with the oracle's expected helper results and the verification against them, the single-stream
+steps behind `roofline`, the CPU baseline, and the `secondary` block (the other BASELINE configs and
+the job-granularity shapes). `--no-cpu-baseline`, `--no-secondary` and `--alone-steps` trim a full run.
 """
 from __future__ import annotations
 
@@ -203,10 +211,11 @@ def stage_roofline(summary_path: str, prefix: str, ms_per_launch: float, reports
 POOL_BLOCK = 256  # pool reports per stored block aggregate (CyclicPool prefix sums)
 
 
-def make_pool(vdaf, vk, K, seed=0x5EED, threads=16):
+def make_pool(vdaf, vk, K, seed=0x5EED, threads=16, expect=True):
     """K distinct client reports and the oracle's helper results: verdicts, prep messages, the pool
     aggregate and the aggregate of every POOL_BLOCK-report block (for expectations over any range of
-    the cyclic tiling, CyclicPool)."""
+    the cyclic tiling, CyclicPool). With expect=False only the reports (the same ones: the helper
+    results draw nothing from the generator), and None for the results."""
     from oracle import oracle as O  # input generation (client + leader), see module docstring
     orc = O.Prio3Oracle(vdaf.algo_id, vdaf.bits, vdaf.length, vdaf.chunk_length)
     rng = np.random.default_rng(seed)
@@ -217,6 +226,8 @@ def make_pool(vdaf, vk, K, seed=0x5EED, threads=16):
     for i in range(0, K, 100):  # 1% invalid: one flipped bit in the leader prep share
         j = int(rng.integers(0, lps.shape[1]))
         lps[i, j] ^= 1 << int(rng.integers(0, 8))
+    if not expect:
+        return orc, nonces, ps, his, lps, None
     want = orc.helper_prep_batch(vk, nonces, ps, his, lps, nthreads=threads, want_out_shares=True)
     outs, fin = want.pop("out_shares"), want["verdicts"] == 0
     nb = -(-K // POOL_BLOCK)
@@ -297,20 +308,25 @@ def pool_cache_path(vdaf, vk, K, seed=0x5EED) -> str:
     return os.path.join(os.environ.get("JX_POOL_CACHE", "/tmp"), f"janus_amd_bench_pool_{key}.npz")
 
 
-def load_or_make_pool(vdaf, vk, K, threads, local_rank: int, wait_s: float = 900.0):
+def load_or_make_pool(vdaf, vk, K, threads, local_rank: int, wait_s: float = 900.0, expect: bool = True):
     """The synthetic pool, generated once per node: local rank 0 runs the C oracle and writes the pool
     (inputs + the oracle's verdicts and aggregate) atomically to a cache file; the other ranks wait for
-    the file and read it. An 8-rank start therefore costs one generation, not eight."""
+    the file and read it. An 8-rank start therefore costs one generation, not eight. With expect=False
+    (a plain run: nothing is verified) only the inputs are generated, into a cache file of their own
+    unless the full one is already there; the expected results are then None."""
     from oracle import oracle as O
 
     path = pool_cache_path(vdaf, vk, K)
+    if not expect and not os.path.exists(path):
+        path = path[:-len(".npz")] + "_inputs.npz"
     if not os.path.exists(path):
         if local_rank == 0:
-            orc, nonces, ps, his, lps, want = make_pool(vdaf, vk, K, threads=threads)
+            orc, nonces, ps, his, lps, want = make_pool(vdaf, vk, K, threads=threads, expect=expect)
             tmp = f"{path}.{os.getpid()}.tmp.npz"
-            np.savez(tmp, nonces=nonces, ps=ps, his=his, lps=lps, verdicts=want["verdicts"],
-                     prep_msgs=want["prep_msgs"], blocks=want["blocks"],
-                     agg=np.frombuffer(want["agg"], np.uint8), count=np.array([want["count"]], np.int64))
+            res = {} if want is None else dict(
+                verdicts=want["verdicts"], prep_msgs=want["prep_msgs"], blocks=want["blocks"],
+                agg=np.frombuffer(want["agg"], np.uint8), count=np.array([want["count"]], np.int64))
+            np.savez(tmp, nonces=nonces, ps=ps, his=his, lps=lps, **res)
             os.replace(tmp, path)
             return orc, nonces, ps, his, lps, want, "generated"
         t0 = time.perf_counter()
@@ -321,7 +337,7 @@ def load_or_make_pool(vdaf, vk, K, threads, local_rank: int, wait_s: float = 900
     d = np.load(path)  # allow_pickle=False: plain arrays this script wrote
     orc = O.Prio3Oracle(vdaf.algo_id, vdaf.bits, vdaf.length, vdaf.chunk_length)
     want = {"verdicts": d["verdicts"], "prep_msgs": d["prep_msgs"], "blocks": d["blocks"], "agg": d["agg"].tobytes(),
-            "count": int(d["count"][0])}
+            "count": int(d["count"][0])} if expect else None
     return orc, d["nonces"], d["ps"], d["his"], d["lps"], want, "cached"
 
 
@@ -465,21 +481,65 @@ def ensure_world(gpus: int, sysfs_root: str = "/sys/class/kfd/kfd/topology/nodes
     sys.exit(subprocess.run(cmd).returncode)
 
 
+DUMP_MAX_ROWS = 1_310_720  # per-report outputs kept by --dump-outputs: 36 B each (44 B when sampled), < 64 MB
+
+
+def dump_outputs(out_dir: str, verdicts, prep_msgs, share, merged) -> dict:
+    """What a caller of the timed path holds after its last step, as float32 .npy files: the per-report
+    verdicts and Finish{prep_msg} seeds (16 bytes each, as 8 little-endian 16-bit words; zero where the
+    report was rejected, whose seed the engine leaves unwritten), this rank's aggregate share, report
+    count and checksum, and the merged shard record when the step combines. Bytes and 16-bit words are
+    exact in float32 and one unit apart under any sensible tolerance. Beyond DUMP_MAX_ROWS reports a
+    fixed, seeded sample of rows is kept (rows.npy, float64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+
+    def save(name, a, dtype=np.float32):
+        a = np.ascontiguousarray(a, dtype=dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        files[name] = list(a.shape)
+
+    def octets(b: bytes):
+        return np.frombuffer(b, np.uint8)
+
+    n = verdicts.shape[0]
+    if n > DUMP_MAX_ROWS:
+        rows = np.sort(np.random.default_rng(0xD0B5).choice(n, DUMP_MAX_ROWS, replace=False))
+        verdicts, prep_msgs = verdicts[rows], prep_msgs[rows]
+        save("rows", rows, np.float64)
+    msgs = np.where((verdicts == 0)[:, None], prep_msgs, 0).astype(np.uint8)
+    save("verdicts", verdicts)
+    save("prep_msgs", np.ascontiguousarray(msgs).view("<u2"))
+    for prefix, (agg, count, checksum) in (("", share), ("merged_", merged)) if merged else (("", share),):
+        save(prefix + "aggregate_share", octets(agg))
+        save(prefix + "report_count", [count], np.float64)
+        save(prefix + "checksum", octets(checksum))
+    return files
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reports-per-gpu", type=int, default=1_250_000)
-    ap.add_argument("--pool", type=int, default=32768)
+    ap.add_argument("--pool", type=int, default=None,
+                    help="distinct reports tiled to --reports-per-gpu (default: 4096, or 32768 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also verify every output against the oracle, time each kernel on one "
+                         "stream (roofline), run the CPU baseline and measure the secondary configs (a plain run prints "
+                         "the headline figure and the timed steps' kernel times only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (verdicts, prep messages, aggregate share, count, "
+                         "checksum, merged record) as DIR/<name>.npy; identical arguments give identical inputs")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--bits", type=int, default=8)
     ap.add_argument("--length", type=int, default=1000)
     ap.add_argument("--chunk", type=int, default=88)
     ap.add_argument("--no-secondary", dest="secondary", action="store_false",
-                    help="skip the other BASELINE configs (configs[0-2], configs[4]) that the N=1 run measures after "
-                         "the headline")
+                    help="skip the other BASELINE configs (configs[0-2], configs[4]) that the N=1 --full run measures "
+                         "after the headline")
     ap.add_argument("--no-dist", dest="dist", action="store_false",
                     help="at N=1, skip the RCCL (nccl) process group and the shard-record all-gather + device merge "
                          "that every step otherwise ends with (by default the N=1 step carries the N>1 step's work)")
@@ -487,12 +547,16 @@ def main():
                     help="engine pipelines of the fused device path (0: the engine's choice, 2 for a multi-launch step; "
                          "1: one stream)")
     ap.add_argument("--alone-steps", type=int, default=2,
-                    help="with pipelines: after the timed steps, this many single-stream steps time each kernel "
+                    help="--full with pipelines: after the timed steps, this many single-stream steps time each kernel "
                          "alone (roofline.alone); they count in the verified aggregate")
     ap.add_argument("--share-gpu", action="store_true",
                     help="rehearsal of the N>1 path on a 1-GPU box: every rank runs on cuda:0 and the shard records "
                          "go over gloo (launch under torch.distributed.run; the numbers are not a scaling result)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.pool is None:
+        args.pool = 32768 if args.full else 4096
     ensure_world(args.gpus)
 
     import torch
@@ -530,9 +594,10 @@ def main():
     cpu = cpu_threads()
     threads = min(16, cpu["threads"])  # pool generation (the oracle) per node
     t0 = time.perf_counter()
-    orc, nonces, ps, his, lps, want, how = load_or_make_pool(vdaf, vk, args.pool, threads, local_rank)
+    orc, nonces, ps, his, lps, want, how = load_or_make_pool(vdaf, vk, args.pool, threads, local_rank,
+                                                             expect=args.full)
     startup_s = time.perf_counter() - t0
-    log(f"pool of {args.pool} reports {how} in {startup_s:.1f}s; {int(want['count'])} valid")
+    log(f"pool of {args.pool} reports {how} in {startup_s:.1f}s" + (f"; {int(want['count'])} valid" if want else ""))
 
     R = args.reports_per_gpu
     K = args.pool
@@ -590,8 +655,14 @@ def main():
     # kernel's HIP-event duration includes the device time it shared with another launch's kernels. A few
     # single-stream steps after the timed region time every kernel alone (roofline.alone).
     pipes = eng.memory()["last_pipelines"]  # what the engine ran (fewer than asked if the arena was short)
+    dumped = None
+    if args.dump_outputs:  # before anything else runs on the engine: the outputs of the last timed step
+        merged = combiner.result() if combiner is not None else None
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, d_verdicts.cpu().numpy(), d_msgs.cpu().numpy(),
+                                  eng.aggregate_share(0), merged)
     kt_alone = None
-    if pipes > 1 and args.alone_steps > 0:
+    if args.full and pipes > 1 and args.alone_steps > 0:
         eng.debug(4, 1)
         eng.timing(True)
         for _ in range(args.alone_steps):
@@ -599,38 +670,49 @@ def main():
         kt_alone = eng.timing_read()
         eng.debug(4, args.pipes)
 
-    # ---- verification against the oracle, from the pool's block aggregates (CyclicPool): this rank's
+    # ---- verification against the oracle (--full), from the pool's block aggregates (CyclicPool): this rank's
     # aggregate == (steps + warmup) x the aggregate of its global range; the merged record == the same
     # over every rank's range; every verdict and every finished report's Finish{prep_msg} == the oracle's
-    agg, count, _ = eng.aggregate_share(0)
-    total_steps = args.steps + args.warmup + (args.alone_steps if kt_alone else 0)
+    def verify() -> dict:
+        agg, count, _ = eng.aggregate_share(0)
+        total_steps = args.steps + args.warmup + (args.alone_steps if kt_alone else 0)
 
-    def partial(a, r):
-        h = orc.helper_prep_batch(vk, nonces[a:r], ps[a:r], his[a:r], lps[a:r], nthreads=threads)
-        return field_elems(h["agg"], 16)
+        def partial(a, r):
+            h = orc.helper_prep_batch(vk, nonces[a:r], ps[a:r], his[a:r], lps[a:r], nthreads=threads)
+            return field_elems(h["agg"], 16)
 
-    cyc = CyclicPool(want["verdicts"] == 0, [field_elems(b.tobytes(), 16) for b in want["blocks"]], POOL_BLOCK,
-                     partial, P128)
-    enc = lambda v: b"".join(x.to_bytes(16, "little") for x in v)  # noqa: E731
-    exp_agg, exp_count = cyc.range(start, stop, total_steps)
-    verified = agg == enc(exp_agg) and count == exp_count
-    got_v = d_verdicts.cpu().numpy()
-    verdict_ok = bool(np.array_equal(got_v, want["verdicts"][idx]))
-    fin_rows = got_v == 0
-    msgs_ok = bool(np.array_equal(d_msgs.cpu().numpy()[fin_rows], want["prep_msgs"][idx][fin_rows]))
-    if combiner is not None:
-        c_agg, c_count, _ = combiner.result()
-        all_agg, all_count = cyc.range(0, R * world, total_steps)
-        verified = verified and c_agg == enc(all_agg) and c_count == all_count
+        cyc = CyclicPool(want["verdicts"] == 0, [field_elems(b.tobytes(), 16) for b in want["blocks"]], POOL_BLOCK,
+                         partial, P128)
+        enc = lambda v: b"".join(x.to_bytes(16, "little") for x in v)  # noqa: E731
+        exp_agg, exp_count = cyc.range(start, stop, total_steps)
+        verified = agg == enc(exp_agg) and count == exp_count
+        got_v = d_verdicts.cpu().numpy()
+        verdict_ok = bool(np.array_equal(got_v, want["verdicts"][idx]))
+        fin_rows = got_v == 0
+        msgs_ok = bool(np.array_equal(d_msgs.cpu().numpy()[fin_rows], want["prep_msgs"][idx][fin_rows]))
+        if combiner is not None:
+            c_agg, c_count, _ = combiner.result()
+            all_agg, all_count = cyc.range(0, R * world, total_steps)
+            verified = verified and c_agg == enc(all_agg) and c_count == all_count
 
-    rank_ok = bool(verified and verdict_ok and msgs_ok)
-    all_ok = rank_ok
-    ranks_verified = int(rank_ok)
-    if use_dist:  # every rank checked its own range: the line reports the AND over ranks
-        f = torch.tensor([int(rank_ok)], dtype=torch.int32, device="cpu" if args.share_gpu else dev)
-        dist.all_reduce(f, op=dist.ReduceOp.SUM)
-        ranks_verified = int(f.item())
-        all_ok = ranks_verified == world
+        rank_ok = bool(verified and verdict_ok and msgs_ok)
+        all_ok = rank_ok
+        ranks_verified = int(rank_ok)
+        if use_dist:  # every rank checked its own range: the line reports the AND over ranks
+            f = torch.tensor([int(rank_ok)], dtype=torch.int32, device="cpu" if args.share_gpu else dev)
+            dist.all_reduce(f, op=dist.ReduceOp.SUM)
+            ranks_verified = int(f.item())
+            all_ok = ranks_verified == world
+        return {
+            "verified": all_ok, "ranks_verified": ranks_verified,
+            "verification": {"all_ranks": all_ok, "aggregate_and_count": bool(verified), "verdicts": verdict_ok,
+                             "prep_msgs_of_finished_reports": msgs_ok,
+                             "rank_range": [start, stop], "note": "rank r holds global reports [r R, (r+1) R) of the "
+                             "cyclic pool tiling; expected aggregates from the pool's block aggregates (CyclicPool); "
+                             "all_ranks = every rank's own check (ranks_verified of rccl_world ranks), the other fields "
+                             "are rank 0's; elapsed_spread = max / min per-rank timed seconds"}}
+
+    checked = verify() if args.full else {}
 
     total_reports = R * world * args.steps
     value = total_reports / elapsed
@@ -756,18 +838,17 @@ def main():
                     "k1_hbm_GBps": round(work["hbm_k1"] * chunk_reports / (k1_ms * 1e-3) / 1e9, 1),
                     "k3_hbm_GBps": round(work["hbm_k3"] * chunk_reports / (k3_ms * 1e-3) / 1e9, 1),
                     "work_per_report": work},
-        "verified": all_ok,
-        "rccl_world": rccl_world, "ranks_verified": ranks_verified,
+        "rccl_world": rccl_world,
         "collective": ("gloo (--share-gpu rehearsal)" if args.share_gpu else "nccl (RCCL)") if use_dist else None,
         "elapsed_spread": round(elapsed / elapsed_min, 4) if elapsed_min > 0 else None,
-        "verification": {"all_ranks": all_ok, "aggregate_and_count": bool(verified), "verdicts": verdict_ok,
-                         "prep_msgs_of_finished_reports": msgs_ok,
-                         "rank_range": [start, stop], "note": "rank r holds global reports [r R, (r+1) R) of the "
-                         "cyclic pool tiling; expected aggregates from the pool's block aggregates (CyclicPool); all_ranks = "
-                         "every rank's own check (ranks_verified of rccl_world ranks), the other fields are rank 0's; "
-                         "elapsed_spread = max / min per-rank timed seconds"},
+        "full": args.full,
+        **checked,
     }
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if dumped is not None:
+        out["outputs"] = {"dir": args.dump_outputs, "files": dumped}
+    if not args.full:  # its figures are each kernel's own, from the single-stream steps of a full run
+        del out["roofline"]
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(orc, vdaf, vk, nonces, ps, his, lps, args.cpu_seconds, cpu["threads"])
         out["cpu_baseline"].update(cpu)
     eng.close()
@@ -775,7 +856,7 @@ def main():
     if combiner is not None:
         del combiner
     torch.cuda.empty_cache()
-    if world == 1 and args.secondary:
+    if args.full and world == 1 and args.secondary:
         t_sec = time.perf_counter()
         out["secondary"] = secondary_configs(cpu, threads)
         out["secondary_seconds"] = round(time.perf_counter() - t_sec, 1)

@@ -11,9 +11,9 @@ ARGS="--steps 10 --warmup 2 --no-cpu-baseline --no-secondary"
 for cfg in "1 0" "2 0" "3 0" "2 131072" "3 131072"; do
   set -- $cfg
   if [ "$2" = "0" ]; then
-    JX_PIPES=$1 timeout -k 10 300 python -u bench.py $ARGS > $OUT/p$1_c$2.json 2> $OUT/p$1_c$2.err || { echo BENCH_FAIL $cfg; tail -5 $OUT/p$1_c$2.err; exit 1; }
+    JX_PIPES=$1 timeout -k 10 300 python -u bench.py --full $ARGS > $OUT/p$1_c$2.json 2> $OUT/p$1_c$2.err || { echo BENCH_FAIL $cfg; tail -5 $OUT/p$1_c$2.err; exit 1; }
   else
-    JX_PIPES=$1 JX_CHUNK_REPORTS=$2 timeout -k 10 300 python -u bench.py $ARGS > $OUT/p$1_c$2.json 2> $OUT/p$1_c$2.err || { echo BENCH_FAIL $cfg; tail -5 $OUT/p$1_c$2.err; exit 1; }
+    JX_PIPES=$1 JX_CHUNK_REPORTS=$2 timeout -k 10 300 python -u bench.py --full $ARGS > $OUT/p$1_c$2.json 2> $OUT/p$1_c$2.err || { echo BENCH_FAIL $cfg; tail -5 $OUT/p$1_c$2.err; exit 1; }
   fi
   python3 -c "
 import json,sys; d=json.loads(open('$OUT/p$1_c$2.json').read().strip().splitlines()[-1])

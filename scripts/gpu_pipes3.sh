@@ -7,9 +7,9 @@ mkdir -p $OUT
 ARGS="--steps 10 --warmup 2 --no-cpu-baseline --no-secondary"
 for c in 0 208384 312512 416704 0; do
   if [ "$c" = "0" ]; then
-    timeout -k 10 300 python -u bench.py $ARGS > $OUT/c$c.json 2> $OUT/c$c.err || { echo BENCH_FAIL $c; tail -5 $OUT/c$c.err; exit 1; }
+    timeout -k 10 300 python -u bench.py --full $ARGS > $OUT/c$c.json 2> $OUT/c$c.err || { echo BENCH_FAIL $c; tail -5 $OUT/c$c.err; exit 1; }
   else
-    JX_CHUNK_REPORTS=$c timeout -k 10 300 python -u bench.py $ARGS > $OUT/c$c.json 2> $OUT/c$c.err || { echo BENCH_FAIL $c; tail -5 $OUT/c$c.err; exit 1; }
+    JX_CHUNK_REPORTS=$c timeout -k 10 300 python -u bench.py --full $ARGS > $OUT/c$c.json 2> $OUT/c$c.err || { echo BENCH_FAIL $c; tail -5 $OUT/c$c.err; exit 1; }
   fi
   python3 -c "
 import json; d=json.loads(open('$OUT/c$c.json').read().strip().splitlines()[-1])

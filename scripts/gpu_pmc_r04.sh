@@ -7,7 +7,7 @@ export TMPDIR=/tmp
 N=${1:?name}
 OUT=gpurun_out/$N
 mkdir -p $OUT/pmc $OUT/fp/pmc
-ONE="bench.py --steps 1 --warmup 0 --reports-per-gpu 262144 --pool 4096 --no-cpu-baseline --no-secondary"
+ONE="bench.py --full --steps 1 --warmup 0 --reports-per-gpu 262144 --pool 4096 --no-cpu-baseline --no-secondary"
 SQ="SQ_INSTS_VALU SQ_THREAD_CYCLES_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_INSTS_VALU_INT32 GRBM_GUI_ACTIVE"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d $OUT/pmc/trace_raw -o run -- python3 $ONE > $OUT/one.json 2> $OUT/one.err || { echo ONE_TRACE_FAIL; tail -20 $OUT/one.err; exit 1; }
 mkdir -p $OUT/pmc/trace && cp $OUT/pmc/trace_raw/run_kernel_stats.csv $OUT/pmc/trace/

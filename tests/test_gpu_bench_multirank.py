@@ -31,7 +31,7 @@ def test_two_ranks_on_one_gpu_verify():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(_port()), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--share-gpu", "--reports-per-gpu", "20000", "--pool", "4096", "--steps", "2",
-           "--warmup", "1", "--no-cpu-baseline", "--no-secondary"]
+           "--warmup", "1", "--full", "--no-cpu-baseline", "--no-secondary"]
     p = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=280)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [x for x in p.stdout.splitlines() if x.startswith("{")]
