@@ -5,9 +5,10 @@
  *   /root/reference/aggregator/src/aggregator.rs:1772-1832
  *     hpke::open(&hpke_keypair, &HpkeApplicationInfo::new(&Label::InputShare, &Role::Client,
  *                &Role::Helper), prepare_init.report_share().encrypted_input_share(), &aad)
- * (core/src/hpke.rs:200-230), for Janus's suite: RFC 9180 base mode, DHKEM(X25519, HKDF-SHA256)
- * (0x0020), HKDF-SHA256 (0x0001), AES-128-GCM (0x0001). Once prepare runs on the GPU this is the
- * next per-report CPU cost (X25519 + key schedule + AEAD per report).
+ * (core/src/hpke.rs:200-230): RFC 9180 base mode, DHKEM(X25519, HKDF-SHA256) (0x0020) with any of
+ * HKDF-SHA256 / -SHA384 / -SHA512 and AES-128-GCM / AES-256-GCM / ChaCha20Poly1305 (jx_hpke_create_suite;
+ * the default is HKDF-SHA256 (0x0001), AES-128-GCM (0x0001), docs/samples/tasks.yaml:54-58). Once prepare
+ * runs on the GPU this is the next per-report CPU cost (X25519 + key schedule + AEAD per report).
  *
  * Conventions as in jx_prio3.h: int32 status (0 = OK), caller-owned buffers, one context per
  * (keypair, application info, GPU). Calls on one context from several threads are serialized (a mutex per
@@ -32,6 +33,7 @@ extern "C" {
 
 #define JX_HPKE_OK 0
 #define JX_HPKE_E_INVALID (-1)
+#define JX_HPKE_E_UNSUPPORTED (-2) /* a KEM, KDF or AEAD id outside the suites below */
 #define JX_HPKE_E_HIP (-3)
 #define JX_HPKE_E_NOMEM (-4)
 #define JX_HPKE_E_NODEVICE (-6)
@@ -42,6 +44,17 @@ typedef struct jx_hpke jx_hpke;
  * info: the HPKE application info (Janus: "dap-09 input share" || sender role || recipient role). */
 int32_t jx_hpke_create(const uint8_t sk[32], const uint8_t pk[32], const uint8_t* info, uint32_t info_len,
                        int32_t device, jx_hpke** out);
+/* The same for the suite of the keypair's HpkeConfig (messages/src/lib.rs:768-846: kem_id, kdf_id, aead_id):
+ * KEM 0x0020 DHKEM(X25519, HKDF-SHA256); KDF 0x0001 HKDF-SHA256, 0x0002 HKDF-SHA384, 0x0003 HKDF-SHA512; AEAD
+ * 0x0001 AES-128-GCM, 0x0002 AES-256-GCM, 0x0003 ChaCha20Poly1305: nine suites. Any other id (the P-256 KEM
+ * 0x0010 among them) returns JX_HPKE_E_UNSUPPORTED, with the reason in jx_hpke_last_error: such a keypair stays
+ * on the host path. jx_hpke_create is the (0x0020, 0x0001, 0x0001) case. Contexts of any suites may be passed
+ * together to jx_helper_prep_encrypted_batch. */
+int32_t jx_hpke_create_suite(uint32_t kem_id, uint32_t kdf_id, uint32_t aead_id, const uint8_t sk[32],
+                             const uint8_t pk[32], const uint8_t* info, uint32_t info_len, int32_t device,
+                             jx_hpke** out);
+/* The suite a context was created with (any of the three may be NULL). */
+int32_t jx_hpke_suite(const jx_hpke* h, uint32_t* kem_id, uint32_t* kdf_id, uint32_t* aead_id);
 void jx_hpke_destroy(jx_hpke* h);
 
 /* Host buffers. */
@@ -52,6 +65,9 @@ int32_t jx_hpke_open_batch(jx_hpke* h, uint64_t n, const uint8_t* encs, const ui
 int32_t jx_hpke_open_batch_device(jx_hpke* h, uint64_t n, const void* d_encs, const void* d_cts,
                                   const uint64_t* d_ct_offsets, const void* d_aads, const uint64_t* d_aad_offsets,
                                   void* d_out_plaintexts, void* d_out_ok);
+/* The context's stream (a hipStream_t), on which jx_hpke_open_batch_device enqueues: for events around an open,
+ * or to order other work after it. */
+int32_t jx_hpke_stream(const jx_hpke* h, void** out_stream);
 const char* jx_hpke_last_error(const jx_hpke* h);
 
 #ifdef __cplusplus

@@ -427,7 +427,12 @@ static int32_t launch_lane(Coalescer* C, Lane& L, std::string& err) {
   if (L.has_enc) {  // open the encrypted reports into their helper input-share rows
     HpkeRowsArgs ha{m, q->d_encrows, q->d_ct, q->d_pt, q->d_keys, (uint32_t)L.keys.size(), q->d_nonces, q->d_ps,
                     c.ps_bytes, q->d_his, c.his_bytes, q->d_status};
-    s = launch_hpke_rows(ha, q->stream);
+    // jobs of any suites share a launch; one key outside the default suite sends all its rows to the suite kernel
+    const HpkeKeyRow* key_rows = reinterpret_cast<const HpkeKeyRow*>(L.h_in + L.o_keys);
+    bool suites = false;
+    for (size_t k = 0; k < L.keys.size(); k++)
+      suites = suites || key_rows[k].kdf != 1 || key_rows[k].aead != 1;
+    s = launch_hpke_rows(ha, suites, q->stream);
     if (s != hipSuccess) return bad(s, "hpke open");
   }
   rc = prep_core(q, m, q->d_nonces, q->d_ps, q->d_his, q->d_lps, q->d_verdicts, q->d_msgs, staging_outs(q),

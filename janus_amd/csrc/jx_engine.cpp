@@ -1392,9 +1392,11 @@ int32_t jx_helper_prep_encrypted_batch(jx_engine* e, uint64_t n, const uint8_t* 
       std::vector<EncRow> rows(n);
       uint8_t key_map[JX_ENC_MAX_KEYPAIRS];
       std::vector<HpkeKeyRow> keys(nkeypairs ? nkeypairs : 1);
+      bool suites = false;
       for (uint32_t k = 0; k < nkeypairs; k++) {
         key_map[k] = (uint8_t)k;
         hpke_key_row(keypairs[k], &keys[k]);
+        suites = suites || !hpke_default_suite(keypairs[k]);
       }
       fill_enc_rows(job, n, rows.data(), 0, key_map);
       e->enc_ct_bytes = ct ? ct : 1;
@@ -1410,7 +1412,7 @@ int32_t jx_helper_prep_encrypted_batch(jx_engine* e, uint64_t n, const uint8_t* 
         HIPCHK(e, hipMemcpyAsync(e->d_keys, keys.data(), nkeypairs * sizeof(HpkeKeyRow), hipMemcpyHostToDevice, e->stream));
       HpkeRowsArgs ha{n, e->d_encrows, e->d_ct, e->d_pt, e->d_keys, nkeypairs, B->nonces, e->d_ps, c.ps_bytes,
                       e->d_his, c.his_bytes, e->d_status};
-      HIPCHK(e, launch_hpke_rows(ha, e->stream));
+      HIPCHK(e, launch_hpke_rows(ha, suites, e->stream));
       r = prep_core(e, n, B->nonces, e->d_ps, e->d_his, e->d_lps, B->verdicts, B->msgs, B->outs);
       if (r) return r;
       HIPCHK(e, launch_open_mask(e->d_status, B->verdicts, n, e->stream));

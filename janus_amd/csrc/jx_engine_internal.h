@@ -147,7 +147,10 @@ void fill_enc_rows(const EncJob& j, uint64_t n, jx::EncRow* rows, uint64_t ct_ba
 // jx_hpke.hip
 int hpke_device(const jx_hpke* h);
 void hpke_key_row(const jx_hpke* h, jx::HpkeKeyRow* out);
-hipError_t launch_hpke_rows(const jx::HpkeRowsArgs& a, hipStream_t s);
+bool hpke_default_suite(const jx_hpke* h);  // (HKDF-SHA256, AES-128-GCM)
+// suites: the launch's key table holds a key of another suite than the default (every row then goes through
+// hpke_rows_suite_kernel)
+hipError_t launch_hpke_rows(const jx::HpkeRowsArgs& a, bool suites, hipStream_t s);
 hipError_t launch_open_mask(const uint8_t* status, uint8_t* verdicts, uint64_t n, hipStream_t s);
 
 struct Coalescer;  // jx_coalesce.cpp

@@ -10,6 +10,8 @@
 //  * SHA-256 / HMAC / HKDF over messages whose layout is fixed at compile time (every byte
 //    position is a constant after unrolling, so message buffers live in registers).
 //  * SHA-256 / HMAC and AES-128 come from jx_sha_aes.h; GHASH is bit-serial.
+//  * DHKEM decapsulation (hpke_decap) is shared with the other suites' key schedules (jx_hpke_suites.h): the
+//    KEM's own KDF is HKDF-SHA256 under every suite.
 #pragma once
 #include "jx_sha_aes.h"
 
@@ -259,6 +261,59 @@ JX_HD void ghash_mul(uint32_t x[4], const uint32_t h[4]) {
   x[1] = z1;
   x[2] = z2;
   x[3] = z3;
+}
+
+// ============================================================================ DHKEM(X25519, HKDF-SHA256)
+
+// the KEM's suite id: "KEM" || 0x0020
+JX_HD int m_suite_kem(Msg128& m, int pos) {
+  pos = m_str(m, pos, "KEM");
+  m_byte(m, pos, 0x00);
+  m_byte(m, pos + 1, 0x20);
+  return pos + 2;
+}
+
+// Decap (RFC 9180 §4.1) for the recipient key (sk clamped, pk; 8 LE words each) and encapsulated key enc (8 LE
+// words): dh = X25519(sk, enc), eae_prk = LabeledExtract("", "eae_prk", dh), shared_secret = LabeledExpand(
+// eae_prk, "shared_secret", enc || pk, 32) as 8 big-endian words. The KEM's KDF is HKDF-SHA256 whatever the
+// suite's KDF is. zist / zost: the HMAC-SHA256 pads of the empty salt. False when the DH output is all zero (a
+// low-order point: the open fails).
+JX_HD bool hpke_decap(uint32_t ss[8], const uint32_t sk[8], const uint32_t pk[8], const uint32_t zist[8],
+                      const uint32_t zost[8], const uint32_t enc[8]) {
+  uint32_t dh[8];
+  x25519_ladder(dh, sk, enc);
+  uint32_t nz = 0;
+  for (int i = 0; i < 8; i++) nz |= dh[i];
+  uint32_t eae_prk[8];
+  {
+    Msg128 m;
+    m_zero(m);
+    int pos = m_str(m, 0, "HPKE-v1");
+    pos = m_suite_kem(m, pos);
+    pos = m_str(m, pos, "eae_prk");
+    pos = m_le32(m, pos, dh);
+    uint32_t inner[8];
+    sha256_finish64(inner, zist, m, pos);
+    hmac_outer(eae_prk, zost, inner);
+  }
+  {
+    uint32_t ist[8], ost[8];
+    hmac_pads(eae_prk, ist, ost);
+    Msg128 m;
+    m_zero(m);
+    m_byte(m, 0, 0);
+    m_byte(m, 1, 32);
+    int pos = m_str(m, 2, "HPKE-v1");
+    pos = m_suite_kem(m, pos);
+    pos = m_str(m, pos, "shared_secret");
+    pos = m_le32(m, pos, enc);
+    pos = m_le32(m, pos, pk);
+    m_byte(m, pos, 1);
+    uint32_t inner[8];
+    sha256_finish64(inner, ist, m, pos + 1);
+    hmac_outer(ss, ost, inner);
+  }
+  return nz != 0;
 }
 
 }  // namespace jx

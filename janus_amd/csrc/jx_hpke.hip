@@ -5,8 +5,13 @@
 // of the helper's aggregate-init loop (aggregator/src/aggregator.rs:1772-1832; core/src/hpke.rs:
 // 200-230): RFC 9180 base mode, DHKEM(X25519, HKDF-SHA256), HKDF-SHA256, AES-128-GCM. One
 // report per lane: X25519 decapsulation, the HKDF key schedule, AES-128-GCM open.
+// The other eight X25519 suites an HpkeConfig can name (HKDF-SHA256 / -SHA384 / -SHA512 with AES-128-GCM /
+// AES-256-GCM / ChaCha20Poly1305; jx_hpke_suites.h) go through a second pair of kernels, hpke_open_suite_kernel
+// and hpke_rows_suite_kernel, which read the suite from the key row and dispatch per lane. They are launched only
+// for a context, or a launch's key table, that holds a key outside the default suite (then for every row of the
+// launch), so the default suite's kernels and their register budget are what they were.
 //
-// Two kernels:
+// Two kernels (each with its suite twin):
 //  - hpke_open_kernel: the standalone batch open of include/jx_hpke.h (caller's ciphertexts and AADs);
 //  - hpke_rows_kernel: the open INSIDE a helper prepare launch (jx_helper_prep_encrypted_batch, alone or
 //    coalesced): per report it builds the InputShareAad from the report's task id, id, time and public share
@@ -22,15 +27,25 @@
 
 #include "../../include/jx_hpke.h"
 #include "jx_engine_internal.h"
-#include "jx_hpke.h"
+#include "jx_hpke_suites.h"
 
 using namespace jx;
 
 namespace {
 
 struct HpkeCfg {
-  HpkeKeyRow key;          // clamped recipient scalar, public key, key_schedule_context
+  HpkeKeyRow key;          // clamped recipient scalar, public key, key_schedule_context, suite
   uint32_t zero_ist[8];    // HMAC-SHA256 pads of the empty salt (LabeledExtract with salt "")
+  uint32_t zero_ost[8];
+};
+// What hpke_open_kernel takes: a default-suite key with its 65-byte key_schedule_context alone (the kernel keeps
+// its argument in private memory, so the longer contexts of the other suites would cost it scratch).
+struct HpkeDefaultCfg {
+  uint32_t sk[8];
+  uint32_t pk[8];
+  uint8_t ksc[68];
+  uint8_t pad[4];
+  uint32_t zero_ist[8];
   uint32_t zero_ost[8];
 };
 
@@ -45,13 +60,7 @@ struct HpkeBufs {
   uint8_t* ok;
 };
 
-// HPKE suite ids: "KEM" || 0x0020 and "HPKE" || 0x0020 || 0x0001 || 0x0001
-JX_HD int m_suite_kem(Msg128& m, int pos) {
-  pos = m_str(m, pos, "KEM");
-  m_byte(m, pos, 0x00);
-  m_byte(m, pos + 1, 0x20);
-  return pos + 2;
-}
+// the default suite's id: "HPKE" || 0x0020 || 0x0001 || 0x0001
 JX_HD int m_suite(Msg128& m, int pos) {
   pos = m_str(m, pos, "HPKE");
   const uint8_t ids[6] = {0x00, 0x20, 0x00, 0x01, 0x00, 0x01};
@@ -90,41 +99,12 @@ JX_HD void ld_block_be(const uint8_t* p, uint64_t n, uint32_t b[4]) {  // up to 
 // The AES-128-GCM context of one recipient key for encapsulated key `enc` (8 LE words): DHKEM decap
 // (RFC 9180 §4.1), the mode_base key schedule (§5.1), the round keys, the hash key H (4 BE words) and the
 // base nonce (3 BE words). False when the DH output is all zero (a low-order point: the open fails).
-__device__ bool hpke_context(const uint8_t* sbox, const HpkeKeyRow& key, const uint32_t zist[8], const uint32_t zost[8],
+// Key: anything with sk, pk and ksc (HpkeKeyRow, HpkeDefaultCfg).
+template <class Key>
+__device__ bool hpke_context(const uint8_t* sbox, const Key& key, const uint32_t zist[8], const uint32_t zost[8],
                              const uint32_t enc[8], uint32_t rk[44], uint32_t h[4], uint32_t nonce3[3]) {
-  uint32_t dh[8];
-  x25519_ladder(dh, key.sk, enc);
-  uint32_t nz = 0;
-  for (int i = 0; i < 8; i++) nz |= dh[i];
-  uint32_t eae_prk[8], ss[8], secret[8], kk[8], nonce[8];
-  {
-    Msg128 m;
-    m_zero(m);
-    int pos = m_str(m, 0, "HPKE-v1");
-    pos = m_suite_kem(m, pos);
-    pos = m_str(m, pos, "eae_prk");
-    pos = m_le32(m, pos, dh);
-    uint32_t inner[8];
-    sha256_finish64(inner, zist, m, pos);
-    hmac_outer(eae_prk, zost, inner);
-  }
-  {
-    uint32_t ist[8], ost[8];
-    hmac_pads(eae_prk, ist, ost);
-    Msg128 m;
-    m_zero(m);
-    m_byte(m, 0, 0);
-    m_byte(m, 1, 32);
-    int pos = m_str(m, 2, "HPKE-v1");
-    pos = m_suite_kem(m, pos);
-    pos = m_str(m, pos, "shared_secret");
-    pos = m_le32(m, pos, enc);
-    pos = m_le32(m, pos, key.pk);
-    m_byte(m, pos, 1);
-    uint32_t inner[8];
-    sha256_finish64(inner, ist, m, pos + 1);
-    hmac_outer(ss, ost, inner);
-  }
+  uint32_t ss[8], secret[8], kk[8], nonce[8];
+  const bool nz = hpke_decap(ss, key.sk, key.pk, zist, zost, enc);
   {
     uint32_t ist[8], ost[8];
     hmac_pads(ss, ist, ost);
@@ -149,13 +129,14 @@ __device__ bool hpke_context(const uint8_t* sbox, const HpkeKeyRow& key, const u
   aes128_encrypt(sbox, rk, zero4, hblk);
   for (int i = 0; i < 4; i++) h[i] = bswap32(hblk[i]);
   for (int i = 0; i < 3; i++) nonce3[i] = bswap32(nonce[i]);
-  return nz != 0;
+  return nz;
 }
 
 // GCM tag check of ciphertext ct[0, clen) with tag ct[clen, clen + 16) and associated data produced 16
-// bytes at a time by aad_block(i, w) (alen bytes): GHASH, then E(J0) ^ S == tag.
-template <class AadBlock>
-__device__ bool gcm_tag_ok(const uint8_t* sbox, const uint32_t rk[44], const uint32_t h[4], const uint32_t nonce3[3],
+// bytes at a time by aad_block(i, w) (alen bytes): GHASH, then E(J0) ^ S == tag. NR: the cipher's rounds (10
+// with AES-128's 44 round-key words, 14 with AES-256's 60).
+template <int NR, class AadBlock>
+__device__ bool gcm_tag_ok(const uint8_t* sbox, const uint32_t* rk, const uint32_t h[4], const uint32_t nonce3[3],
                            uint64_t alen, AadBlock aad_block, const uint8_t* ct, uint64_t clen) {
   uint32_t y[4] = {0, 0, 0, 0};
   for (uint64_t i = 0; i < alen; i += 16) {
@@ -177,7 +158,7 @@ __device__ bool gcm_tag_ok(const uint8_t* sbox, const uint32_t rk[44], const uin
   ghash_mul(y, h);
   // counter blocks: nonce (12 bytes) || BE32 counter; J0 has counter 1
   uint32_t cb[4] = {nonce3[0], nonce3[1], nonce3[2], bswap32(1u)}, ks[4];
-  aes128_encrypt(sbox, rk, cb, ks);
+  aes_encrypt_nr<NR>(sbox, rk, cb, ks);
   uint32_t diff = 0;
   for (int k = 0; k < 4; k++) {
     uint32_t tag_w = 0;
@@ -188,12 +169,13 @@ __device__ bool gcm_tag_ok(const uint8_t* sbox, const uint32_t rk[44], const uin
 }
 
 // CTR decryption of ct[0, clen) into pt (counter blocks from 2)
-__device__ void gcm_decrypt(const uint8_t* sbox, const uint32_t rk[44], const uint32_t nonce3[3], const uint8_t* ct,
+template <int NR>
+__device__ void gcm_decrypt(const uint8_t* sbox, const uint32_t* rk, const uint32_t nonce3[3], const uint8_t* ct,
                             uint64_t clen, uint8_t* pt) {
   uint32_t cb[4] = {nonce3[0], nonce3[1], nonce3[2], 0}, ks[4];
   for (uint64_t i = 0; i < clen; i += 16) {
     cb[3] = bswap32((uint32_t)(2 + i / 16));
-    aes128_encrypt(sbox, rk, cb, ks);
+    aes_encrypt_nr<NR>(sbox, rk, cb, ks);
     for (uint64_t j = 0; j < 16 && i + j < clen; j++) pt[i + j] = ct[i + j] ^ (uint8_t)(ks[j >> 2] >> (8 * (j & 3)));
   }
 }
@@ -204,25 +186,95 @@ __device__ void load_enc(const uint8_t* p, uint32_t enc[8]) {
              ((uint32_t)p[4 * i + 3] << 24);
 }
 
-__global__ __launch_bounds__(64) void hpke_open_kernel(HpkeCfg cfg, HpkeBufs b) {
+// One open under the key's own suite (jx_hpke_suites.h): the context, then the suite's AEAD with sequence
+// number 0 (the nonce is the base nonce). The associated data comes a byte at a time from aad_byte(i).
+template <class AadByte>
+__device__ bool suite_open(const uint8_t* sbox, const HpkeKeyRow& key, const uint32_t zist[8], const uint32_t zost[8],
+                           const uint32_t enc[8], uint64_t alen, AadByte aad_byte, const uint8_t* ct, uint64_t clen,
+                           uint8_t* pt) {
+  uint8_t kb[32], nb[12];
+  const uint32_t aead = key.aead;
+  if (!hpke_suite_context(key.sk, key.pk, key.ksc, key.kdf, aead, zist, zost, enc, kb, nb)) return false;
+  uint32_t kw[8], nw[3];  // little-endian words
+  for (int i = 0; i < 8; i++)
+    kw[i] = (uint32_t)kb[4 * i] | ((uint32_t)kb[4 * i + 1] << 8) | ((uint32_t)kb[4 * i + 2] << 16) |
+            ((uint32_t)kb[4 * i + 3] << 24);
+  for (int i = 0; i < 3; i++)
+    nw[i] = (uint32_t)nb[4 * i] | ((uint32_t)nb[4 * i + 1] << 8) | ((uint32_t)nb[4 * i + 2] << 16) |
+            ((uint32_t)nb[4 * i + 3] << 24);
+  if (aead == HPKE_AEAD_CHACHA20POLY1305) {
+    if (!chapoly_tag_ok(kw, nw, alen, aad_byte, ct, clen)) return false;
+    chapoly_decrypt(kw, nw, ct, clen, pt);
+    return true;
+  }
+  auto aad_block = [&](uint64_t i, uint32_t x[4]) {  // 16 bytes as 4 big-endian words, zero padded
+    for (int w = 0; w < 4; w++) {
+      uint32_t v = 0;
+      for (int k = 0; k < 4; k++) {
+        const uint64_t j = i + 4 * w + k;
+        v = (v << 8) | (j < alen ? (uint32_t)aad_byte(j) : 0u);
+      }
+      x[w] = v;
+    }
+  };
+  uint32_t rk[60], h[4], hblk[4], zero4[4] = {0, 0, 0, 0};
+  bool ok;
+  if (aead == HPKE_AEAD_AES128GCM) {
+    aes128_expand_key(sbox, kw, rk);
+    aes128_encrypt(sbox, rk, zero4, hblk);
+    for (int i = 0; i < 4; i++) h[i] = bswap32(hblk[i]);
+    ok = gcm_tag_ok<10>(sbox, rk, h, nw, alen, aad_block, ct, clen);
+    if (ok) gcm_decrypt<10>(sbox, rk, nw, ct, clen, pt);
+  } else {
+    aes256_expand_key(sbox, kw, rk);
+    aes256_encrypt(sbox, rk, zero4, hblk);
+    for (int i = 0; i < 4; i++) h[i] = bswap32(hblk[i]);
+    ok = gcm_tag_ok<14>(sbox, rk, h, nw, alen, aad_block, ct, clen);
+    if (ok) gcm_decrypt<14>(sbox, rk, nw, ct, clen, pt);
+  }
+  return ok;
+}
+
+// The standalone batch open. SUITE false: the default suite alone (register-resident context); true: the suite of
+// cfg.key, whichever of the nine it is.
+template <bool SUITE, class Cfg>
+__device__ void open_body(const uint8_t* sbox, const Cfg& cfg, const HpkeBufs& b) {
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= b.n) return;
+  uint32_t enc[8];
+  load_enc(b.encs + 32 * r, enc);
+  const uint64_t c0 = b.ct_off[r], c1 = b.ct_off[r + 1];
+  const uint64_t a0 = b.aad_off[r], a1 = b.aad_off[r + 1];
+  const uint64_t alen = a1 - a0;
+  const uint8_t* ct = b.cts + c0;
+  const uint8_t* aad = b.aads + a0;
+  bool ok;
+  if constexpr (!SUITE) {
+    uint32_t rk[44], h[4], nonce3[3];
+    const bool nz = hpke_context(sbox, cfg, cfg.zero_ist, cfg.zero_ost, enc, rk, h, nonce3);
+    ok = nz && c1 - c0 >= 16;
+    const uint64_t clen = ok ? c1 - c0 - 16 : 0;
+    ok = ok && gcm_tag_ok<10>(sbox, rk, h, nonce3, alen,
+                              [&](uint64_t i, uint32_t x[4]) { ld_block_be(aad + i, alen - i, x); }, ct, clen);
+    if (ok) gcm_decrypt<10>(sbox, rk, nonce3, ct, clen, b.pts + c0 - 16 * r);
+  } else {
+    ok = c1 - c0 >= 16 && suite_open(sbox, cfg.key, cfg.zero_ist, cfg.zero_ost, enc, alen,
+                                     [&](uint64_t i) { return aad[i]; }, ct, c1 - c0 - 16, b.pts + c0 - 16 * r);
+  }
+  b.ok[r] = (uint8_t)ok;
+}
+
+__global__ __launch_bounds__(64) void hpke_open_kernel(HpkeDefaultCfg cfg, HpkeBufs b) {
   __shared__ uint8_t sbox[256];
   for (int i = threadIdx.x; i < 256; i += blockDim.x) sbox[i] = AES_SBOX[i];
   __syncthreads();
-  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= b.n) return;
-  uint32_t enc[8], rk[44], h[4], nonce3[3];
-  load_enc(b.encs + 32 * r, enc);
-  const bool nz = hpke_context(sbox, cfg.key, cfg.zero_ist, cfg.zero_ost, enc, rk, h, nonce3);
-  const uint64_t c0 = b.ct_off[r], c1 = b.ct_off[r + 1];
-  const uint64_t a0 = b.aad_off[r], a1 = b.aad_off[r + 1];
-  bool ok = nz && c1 - c0 >= 16;
-  const uint64_t clen = ok ? c1 - c0 - 16 : 0, alen = a1 - a0;
-  const uint8_t* ct = b.cts + c0;
-  const uint8_t* aad = b.aads + a0;
-  ok = ok && gcm_tag_ok(sbox, rk, h, nonce3, alen, [&](uint64_t i, uint32_t x[4]) { ld_block_be(aad + i, alen - i, x); },
-                        ct, clen);
-  if (ok) gcm_decrypt(sbox, rk, nonce3, ct, clen, b.pts + c0 - 16 * r);
-  b.ok[r] = (uint8_t)ok;
+  open_body<false>(sbox, cfg, b);
+}
+__global__ __launch_bounds__(64) void hpke_open_suite_kernel(HpkeCfg cfg, HpkeBufs b) {
+  __shared__ uint8_t sbox[256];
+  for (int i = threadIdx.x; i < 256; i += blockDim.x) sbox[i] = AES_SBOX[i];
+  __syncthreads();
+  open_body<true>(sbox, cfg, b);
 }
 
 // ---------------------------------------------------------------------------- open inside a prepare launch
@@ -242,10 +294,11 @@ __device__ uint8_t aad_byte(const EncRow& e, const uint8_t* nonce, const uint8_t
   return i - 60 < ps_bytes ? ps[i - 60] : 0;
 }
 
-__global__ __launch_bounds__(64) void hpke_rows_kernel(RowsArgs ra) {
-  __shared__ uint8_t sbox[256];
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) sbox[i] = AES_SBOX[i];
-  __syncthreads();
+// The open inside a prepare launch. SUITE false: every key of the launch's table is of the default suite; true: each
+// key's own suite (lanes of one wave may hold different ones). What follows the open is the same code.
+// (ra by value: by reference the kernel's argument costs hpke_rows_kernel four more spilled registers.)
+template <bool SUITE>
+__device__ __forceinline__ void rows_body(const uint8_t* sbox, const RowsArgs ra) {
   const HpkeRowsArgs& a = ra.a;
   const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.n) return;
@@ -276,21 +329,26 @@ __global__ __launch_bounds__(64) void hpke_rows_kernel(RowsArgs ra) {
     for (int t = 0; t < 2 && !ok; t++) {
       const uint32_t kidx = t == 0 ? e.key0 : e.key1;
       if (kidx >= a.nkeys) break;
-      uint32_t rk[44], h[4], nonce3[3];
-      const bool nz = hpke_context(sbox, a.keys[kidx], ra.zero_ist, ra.zero_ost, enc, rk, h, nonce3);
-      ok = nz && gcm_tag_ok(sbox, rk, h, nonce3, alen,
-                            [&](uint64_t i, uint32_t x[4]) {
-                              for (int w = 0; w < 4; w++) {
-                                uint32_t v = 0;
-                                for (int k = 0; k < 4; k++) {
-                                  const uint64_t j = i + 4 * w + k;
-                                  v = (v << 8) | (j < alen ? aad_byte(e, nonce, ps, a.ps_bytes, j) : 0u);
-                                }
-                                x[w] = v;
-                              }
-                            },
-                            ct, clen);
-      if (ok) gcm_decrypt(sbox, rk, nonce3, ct, clen, pt);
+      if constexpr (!SUITE) {
+        uint32_t rk[44], h[4], nonce3[3];
+        const bool nz = hpke_context(sbox, a.keys[kidx], ra.zero_ist, ra.zero_ost, enc, rk, h, nonce3);
+        ok = nz && gcm_tag_ok<10>(sbox, rk, h, nonce3, alen,
+                                  [&](uint64_t i, uint32_t x[4]) {
+                                    for (int w = 0; w < 4; w++) {
+                                      uint32_t v = 0;
+                                      for (int k = 0; k < 4; k++) {
+                                        const uint64_t j = i + 4 * w + k;
+                                        v = (v << 8) | (j < alen ? aad_byte(e, nonce, ps, a.ps_bytes, j) : 0u);
+                                      }
+                                      x[w] = v;
+                                    }
+                                  },
+                                  ct, clen);
+        if (ok) gcm_decrypt<10>(sbox, rk, nonce3, ct, clen, pt);
+      } else {
+        ok = suite_open(sbox, a.keys[kidx], ra.zero_ist, ra.zero_ost, enc, alen,
+                        [&](uint64_t i) { return aad_byte(e, nonce, ps, a.ps_bytes, i); }, ct, clen, pt);
+      }
     }
     if (!ok) st = JX_OPEN_HPKE_DECRYPT_ERROR;
   }
@@ -348,6 +406,19 @@ __global__ __launch_bounds__(64) void hpke_rows_kernel(RowsArgs ra) {
   a.status[r] = (uint8_t)st;
 }
 
+__global__ __launch_bounds__(64) void hpke_rows_kernel(RowsArgs ra) {
+  __shared__ uint8_t sbox[256];
+  for (int i = threadIdx.x; i < 256; i += blockDim.x) sbox[i] = AES_SBOX[i];
+  __syncthreads();
+  rows_body<false>(sbox, ra);
+}
+__global__ __launch_bounds__(64) void hpke_rows_suite_kernel(RowsArgs ra) {
+  __shared__ uint8_t sbox[256];
+  for (int i = threadIdx.x; i < 256; i += blockDim.x) sbox[i] = AES_SBOX[i];
+  __syncthreads();
+  rows_body<true>(sbox, ra);
+}
+
 __global__ __launch_bounds__(256) void open_mask_kernel(const uint8_t* status, uint8_t* verdicts, uint64_t n) {
   const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (r < n && status[r] != JX_OPEN_OK) verdicts[r] = JX_OPEN_FAILURE;
@@ -357,6 +428,7 @@ __global__ __launch_bounds__(256) void open_mask_kernel(const uint8_t* status, u
 
 struct jx_hpke {
   HpkeCfg cfg{};
+  bool default_suite = true;  // (HKDF-SHA256, AES-128-GCM): opened by hpke_open_kernel / hpke_rows_kernel
   int device = 0;
   hipStream_t stream = nullptr;
   jxi::Arena* arena = nullptr;  // the device's arena: the host-buffer open's device buffers
@@ -376,52 +448,38 @@ static int32_t hfail(int32_t code, const std::string& m) {
     if (_st != hipSuccess) return hfail(JX_HPKE_E_HIP, std::string(#call) + ": " + hipGetErrorString(_st)); \
   } while (0)
 
-// host HMAC-SHA256 over arbitrary short messages (configuration only)
-static void host_hmac(const uint8_t* key, size_t klen, const std::vector<uint8_t>& msg, uint8_t out[32]) {
-  auto sha = [](const std::vector<uint8_t>& data, uint8_t dig[32]) {
-    uint32_t st[8];
-    for (int i = 0; i < 8; i++) st[i] = SHA256_IV[i];
-    std::vector<uint8_t> d = data;
-    const uint64_t bits = 8ull * data.size();
-    d.push_back(0x80);
-    while (d.size() % 64 != 56) d.push_back(0);
-    for (int i = 7; i >= 0; i--) d.push_back((uint8_t)(bits >> (8 * i)));
-    for (size_t o = 0; o < d.size(); o += 64) {
-      uint32_t w[16];
-      for (int i = 0; i < 16; i++)
-        w[i] = ((uint32_t)d[o + 4 * i] << 24) | ((uint32_t)d[o + 4 * i + 1] << 16) | ((uint32_t)d[o + 4 * i + 2] << 8) |
-               d[o + 4 * i + 3];
-      sha256_compress(st, w);
-    }
-    for (int i = 0; i < 8; i++)
-      for (int k = 0; k < 4; k++) dig[4 * i + k] = (uint8_t)(st[i] >> (24 - 8 * k));
-  };
-  uint8_t kb[64] = {0};
-  memcpy(kb, key, klen);
-  std::vector<uint8_t> in(64), outer(64);
-  for (int i = 0; i < 64; i++) {
-    in[i] = kb[i] ^ 0x36;
-    outer[i] = kb[i] ^ 0x5c;
-  }
-  in.insert(in.end(), msg.begin(), msg.end());
-  uint8_t ih[32];
-  sha(in, ih);
-  outer.insert(outer.end(), ih, ih + 32);
-  sha(outer, out);
+// the default suite keeps its own kernel; any other goes through the suite kernel
+static void launch_open(const jx_hpke* h, const HpkeBufs& b) {
+  const dim3 grid((uint32_t)((b.n + 63) / 64)), block(64);
+  if (h->default_suite) {
+    HpkeDefaultCfg d{};
+    memcpy(d.sk, h->cfg.key.sk, 32);
+    memcpy(d.pk, h->cfg.key.pk, 32);
+    memcpy(d.ksc, h->cfg.key.ksc, 65);
+    memcpy(d.zero_ist, h->cfg.zero_ist, 32);
+    memcpy(d.zero_ost, h->cfg.zero_ost, 32);
+    hipLaunchKernelGGL(hpke_open_kernel, grid, block, 0, h->stream, d, b);
+  } else
+    hipLaunchKernelGGL(hpke_open_suite_kernel, grid, block, 0, h->stream, h->cfg, b);
 }
 
 namespace jxi {
 
 int hpke_device(const jx_hpke* h) { return h->device; }
 void hpke_key_row(const jx_hpke* h, HpkeKeyRow* out) { *out = h->cfg.key; }
+bool hpke_default_suite(const jx_hpke* h) { return h->default_suite; }
 
-hipError_t launch_hpke_rows(const HpkeRowsArgs& a, hipStream_t s) {
+hipError_t launch_hpke_rows(const HpkeRowsArgs& a, bool suites, hipStream_t s) {
   if (a.n == 0) return hipSuccess;
   RowsArgs ra;
   ra.a = a;
   const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   hmac_pads(zero, ra.zero_ist, ra.zero_ost);
-  hipLaunchKernelGGL(hpke_rows_kernel, dim3((uint32_t)((a.n + 63) / 64)), dim3(64), 0, s, ra);
+  // a key of another suite in the table: every row of the launch goes through the suite kernel
+  if (suites)
+    hipLaunchKernelGGL(hpke_rows_suite_kernel, dim3((uint32_t)((a.n + 63) / 64)), dim3(64), 0, s, ra);
+  else
+    hipLaunchKernelGGL(hpke_rows_kernel, dim3((uint32_t)((a.n + 63) / 64)), dim3(64), 0, s, ra);
   return hipGetLastError();
 }
 
@@ -437,8 +495,20 @@ extern "C" {
 
 int32_t jx_hpke_create(const uint8_t sk[32], const uint8_t pk[32], const uint8_t* info, uint32_t info_len,
                        int32_t device, jx_hpke** out) {
+  return jx_hpke_create_suite(HPKE_KEM_X25519_SHA256, HPKE_KDF_SHA256, HPKE_AEAD_AES128GCM, sk, pk, info, info_len,
+                              device, out);
+}
+
+int32_t jx_hpke_create_suite(uint32_t kem_id, uint32_t kdf_id, uint32_t aead_id, const uint8_t sk[32],
+                             const uint8_t pk[32], const uint8_t* info, uint32_t info_len, int32_t device,
+                             jx_hpke** out) {
   if (!sk || !pk || !out || (info_len && !info)) return JX_HPKE_E_INVALID;
   *out = nullptr;
+  if (!hpke_suite_supported(kem_id, kdf_id, aead_id))
+    return hfail(JX_HPKE_E_UNSUPPORTED,
+                 "unsupported HPKE suite (KEM " + std::to_string(kem_id) + ", KDF " + std::to_string(kdf_id) + ", AEAD " +
+                     std::to_string(aead_id) + "): KEM 0x0020 (X25519), KDF 1..3 (HKDF-SHA256/384/512), AEAD 1..3 "
+                     "(AES-128-GCM, AES-256-GCM, ChaCha20Poly1305)");
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return JX_HPKE_E_NODEVICE;
   if (device < 0 || device >= ndev) return JX_HPKE_E_INVALID;
@@ -455,25 +525,32 @@ int32_t jx_hpke_create(const uint8_t sk[32], const uint8_t pk[32], const uint8_t
   }
   const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   hmac_pads(zero, h->cfg.zero_ist, h->cfg.zero_ost);
-  // key_schedule_context = mode_base || LabeledExtract("", "psk_id_hash", "") || LabeledExtract("", "info_hash", info)
-  const char* ver = "HPKE-v1";
-  const uint8_t suite[10] = {'H', 'P', 'K', 'E', 0x00, 0x20, 0x00, 0x01, 0x00, 0x01};
-  auto labeled = [&](const char* label, const uint8_t* ikm, size_t n, uint8_t o[32]) {
-    std::vector<uint8_t> msg(ver, ver + 7);
-    msg.insert(msg.end(), suite, suite + 10);
-    msg.insert(msg.end(), label, label + strlen(label));
-    msg.insert(msg.end(), ikm, ikm + n);
-    host_hmac(nullptr, 0, msg, o);
-  };
-  h->cfg.key.ksc[0] = 0;
-  labeled("psk_id_hash", nullptr, 0, h->cfg.key.ksc + 1);
-  labeled("info_hash", info, info_len, h->cfg.key.ksc + 33);
+  // the key_schedule_context under the key's own suite and hash (jx_hpke_suites.h)
+  static_assert(sizeof(h->cfg.key.ksc) >= HPKE_KSC_MAX, "HpkeKeyRow holds the longest key_schedule_context");
+  hpke_key_schedule_context(kdf_id, aead_id, info, info_len, h->cfg.key.ksc);
+  h->cfg.key.kdf = (uint8_t)kdf_id;
+  h->cfg.key.aead = (uint8_t)aead_id;
+  h->default_suite = kdf_id == HPKE_KDF_SHA256 && aead_id == HPKE_AEAD_AES128GCM;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
     delete h;
     return JX_HPKE_E_HIP;
   }
   h->arena = jxi::arena_for(device);
   *out = h;
+  return JX_HPKE_OK;
+}
+
+int32_t jx_hpke_suite(const jx_hpke* h, uint32_t* kem_id, uint32_t* kdf_id, uint32_t* aead_id) {
+  if (!h) return JX_HPKE_E_INVALID;
+  if (kem_id) *kem_id = HPKE_KEM_X25519_SHA256;
+  if (kdf_id) *kdf_id = h->cfg.key.kdf;
+  if (aead_id) *aead_id = h->cfg.key.aead;
+  return JX_HPKE_OK;
+}
+
+int32_t jx_hpke_stream(const jx_hpke* h, void** out_stream) {
+  if (!h || !out_stream) return JX_HPKE_E_INVALID;
+  *out_stream = (void*)h->stream;
   return JX_HPKE_OK;
 }
 
@@ -504,7 +581,7 @@ int32_t jx_hpke_open_batch_device(jx_hpke* h, uint64_t n, const void* d_encs, co
              d_aad_offsets,
              (uint8_t*)d_out_plaintexts,
              (uint8_t*)d_out_ok};
-  hipLaunchKernelGGL(hpke_open_kernel, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, h->stream, h->cfg, b);
+  launch_open(h, b);
   HCHK(hipGetLastError());
   return JX_HPKE_OK;
 }
@@ -543,7 +620,7 @@ int32_t jx_hpke_open_batch(jx_hpke* h, uint64_t n, const uint8_t* encs, const ui
     }
     HpkeBufs b{n, base + o_enc, base + o_ct, (const uint64_t*)(base + o_co), base + o_aad, (const uint64_t*)(base + o_ao),
                base + o_pt, base + o_ok};
-    hipLaunchKernelGGL(hpke_open_kernel, dim3((uint32_t)((n + 63) / 64)), dim3(64), 0, h->stream, h->cfg, b);
+    launch_open(h, b);
     if (hipGetLastError() != hipSuccess) {
       rc = hfail(JX_HPKE_E_HIP, "kernel launch failed");
       break;

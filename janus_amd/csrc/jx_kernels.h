@@ -251,14 +251,17 @@ hipError_t launch_scatter_jobs(const Cfg& c, const JobSlice* d_jobs, uint32_t nj
                                hipStream_t s);
 // ---- HPKE open inside a helper prepare launch (jx_hpke.hip; jx_helper_prep_encrypted_batch)
 // A recipient keypair as the rows kernel reads it: clamped X25519 scalar and public key (LE words) and the
-// RFC 9180 key_schedule_context of its application info (0x00 || psk_id_hash || info_hash, 65 bytes).
+// RFC 9180 key_schedule_context of its application info (0x00 || psk_id_hash || info_hash: 1 + 2 Nh bytes, 65
+// for HKDF-SHA256, 97 for -SHA384, 129 for -SHA512) under the key's own suite, whose KDF and AEAD ids follow
+// (the KEM is always 0x0020). The default-suite kernels read the first 65 context bytes and no ids.
 struct HpkeKeyRow {
   uint32_t sk[8];
   uint32_t pk[8];
-  uint8_t ksc[68];
-  uint8_t pad[4];
+  uint8_t ksc[132];
+  uint8_t kdf, aead;
+  uint8_t pad[2];
 };
-static_assert(sizeof(HpkeKeyRow) == 136, "HpkeKeyRow layout");
+static_assert(sizeof(HpkeKeyRow) == 200, "HpkeKeyRow layout");
 enum : uint8_t {
   ENC_ROW_ENCRYPTED = 1,         // the report's helper input share is inside `enc` / the ciphertext (else: uploaded)
   ENC_ROW_REQUIRE_TASKPROV = 2,  // the task is provisioned by taskprov (aggregator.rs:1869-1879)

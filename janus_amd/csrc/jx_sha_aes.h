@@ -1,4 +1,4 @@
-// jx_sha_aes.h — SHA-256 / HMAC-SHA256 and AES-128 building blocks shared by the batched HPKE
+// jx_sha_aes.h — SHA-256 / HMAC-SHA256 and AES-128 / AES-256 building blocks shared by the batched HPKE
 // open (jx_hpke.hip) and the XofHmacSha256Aes128 Prio3 path (jx_mp64.hip). __host__ __device__ so
 // that tests/csrc/hosttest.cpp checks them on the CPU against the test oracles.
 #pragma once
@@ -138,12 +138,31 @@ JX_HD void aes128_expand_key(const uint8_t* sbox, const uint32_t key[4], uint32_
     rk[i] = rk[i - 4] ^ t;
   }
 }
+// AES-256 (FIPS 197 §5.2, Nk = 8): 60 round-key words; SubWord without the rotation at i = 4 mod 8
+JX_HD void aes256_expand_key(const uint8_t* sbox, const uint32_t key[8], uint32_t rk[60]) {
+#pragma unroll
+  for (int i = 0; i < 8; i++) rk[i] = key[i];
+  uint32_t rcon = 1;
+#pragma unroll
+  for (int i = 8; i < 60; i++) {
+    uint32_t t = rk[i - 1];
+    if (i % 8 == 0) {
+      t = sub_word(sbox, (t >> 8) | (t << 24)) ^ rcon;
+      rcon = (rcon << 1) ^ ((rcon >> 7) * 0x11bu);
+    } else if (i % 8 == 4) {
+      t = sub_word(sbox, t);
+    }
+    rk[i] = rk[i - 8] ^ t;
+  }
+}
 JX_HD uint32_t xtime4(uint32_t x) { return ((x & 0x7f7f7f7fu) << 1) ^ (((x >> 7) & 0x01010101u) * 0x1bu); }
-// one 16-byte block as 4 little-endian column words
-JX_HD void aes128_encrypt(const uint8_t* sbox, const uint32_t rk[44], const uint32_t in[4], uint32_t out[4]) {
+// one 16-byte block as 4 little-endian column words; NR rounds over 4 (NR + 1) round-key words (10 / 44 for
+// AES-128, 14 / 60 for AES-256)
+template <int NR>
+JX_HD void aes_encrypt_nr(const uint8_t* sbox, const uint32_t* rk, const uint32_t in[4], uint32_t out[4]) {
   uint32_t s0 = in[0] ^ rk[0], s1 = in[1] ^ rk[1], s2 = in[2] ^ rk[2], s3 = in[3] ^ rk[3];
 #pragma unroll
-  for (int r = 1; r <= 10; r++) {
+  for (int r = 1; r <= NR; r++) {
     // SubBytes + ShiftRows: row i of column c comes from column (c + i) mod 4
     uint32_t t0 = (uint32_t)sbox[s0 & 0xff] | ((uint32_t)sbox[(s1 >> 8) & 0xff] << 8) |
                   ((uint32_t)sbox[(s2 >> 16) & 0xff] << 16) | ((uint32_t)sbox[s3 >> 24] << 24);
@@ -153,7 +172,7 @@ JX_HD void aes128_encrypt(const uint8_t* sbox, const uint32_t rk[44], const uint
                   ((uint32_t)sbox[(s0 >> 16) & 0xff] << 16) | ((uint32_t)sbox[s1 >> 24] << 24);
     uint32_t t3 = (uint32_t)sbox[s3 & 0xff] | ((uint32_t)sbox[(s0 >> 8) & 0xff] << 8) |
                   ((uint32_t)sbox[(s1 >> 16) & 0xff] << 16) | ((uint32_t)sbox[s2 >> 24] << 24);
-    if (r != 10) {  // MixColumns: b_i = 2(a_i ^ a_{i+1}) ^ a_{i+1} ^ a_{i+2} ^ a_{i+3}
+    if (r != NR) {  // MixColumns: b_i = 2(a_i ^ a_{i+1}) ^ a_{i+1} ^ a_{i+2} ^ a_{i+3}
       uint32_t c[4] = {t0, t1, t2, t3};
 #pragma unroll
       for (int q = 0; q < 4; q++) {
@@ -175,6 +194,12 @@ JX_HD void aes128_encrypt(const uint8_t* sbox, const uint32_t rk[44], const uint
   out[1] = s1;
   out[2] = s2;
   out[3] = s3;
+}
+JX_HD void aes128_encrypt(const uint8_t* sbox, const uint32_t rk[44], const uint32_t in[4], uint32_t out[4]) {
+  aes_encrypt_nr<10>(sbox, rk, in, out);
+}
+JX_HD void aes256_encrypt(const uint8_t* sbox, const uint32_t rk[60], const uint32_t in[4], uint32_t out[4]) {
+  aes_encrypt_nr<14>(sbox, rk, in, out);
 }
 
 // FIPS 197 S-box

@@ -2,10 +2,13 @@
 
 Mirror of janus_core::hpke::open (core/src/hpke.rs:200-230) as the helper calls it once per
 report in its aggregate-init loop (aggregator/src/aggregator.rs:1772-1832): RFC 9180 base
-mode with DHKEM(X25519, HKDF-SHA256) / HKDF-SHA256 / AES-128-GCM, application info
-HpkeApplicationInfo::new(&Label::InputShare, &Role::Client, &Role::Helper) (core/src/hpke.rs:
-69-84), associated data the encoded InputShareAad (messages/src/lib.rs:1854-1858). Here the
-whole request's ciphertexts are opened in one launch. There is no CPU fallback.
+mode with DHKEM(X25519, HKDF-SHA256) and the KDF and AEAD of the keypair's HpkeConfig (messages/src/
+lib.rs:768-846): HKDF-SHA256 / -SHA384 / -SHA512 with AES-128-GCM / AES-256-GCM / ChaCha20Poly1305, by
+default HKDF-SHA256 / AES-128-GCM. Application info HpkeApplicationInfo::new(&Label::InputShare,
+&Role::Client, &Role::Helper) (core/src/hpke.rs:69-84), associated data the encoded InputShareAad
+(messages/src/lib.rs:1854-1858). Here the whole request's ciphertexts are opened in one launch. There
+is no CPU fallback: a suite outside these nine (the P-256 KEM among them) is refused when the opener is
+created (UnsupportedSuite), and such a keypair stays on the host path.
 """
 from __future__ import annotations
 
@@ -21,8 +24,18 @@ ROLE_COLLECTOR, ROLE_CLIENT, ROLE_LEADER, ROLE_HELPER = 0, 1, 2, 3
 LABEL_INPUT_SHARE = b"dap-09 input share"
 LABEL_AGGREGATE_SHARE = b"dap-09 aggregate share"
 
-EXPORTED_SYMBOLS = ("jx_hpke_create", "jx_hpke_destroy", "jx_hpke_open_batch", "jx_hpke_open_batch_device",
-                    "jx_hpke_last_error")
+# HpkeKemId, HpkeKdfId, HpkeAeadId (messages/src/lib.rs:768-846): the ids the engine opens
+KEM_X25519_HKDF_SHA256 = 0x0020
+KDF_HKDF_SHA256, KDF_HKDF_SHA384, KDF_HKDF_SHA512 = 0x0001, 0x0002, 0x0003
+AEAD_AES_128_GCM, AEAD_AES_256_GCM, AEAD_CHACHA20_POLY1305 = 0x0001, 0x0002, 0x0003
+E_UNSUPPORTED = -2  # JX_HPKE_E_UNSUPPORTED
+
+EXPORTED_SYMBOLS = ("jx_hpke_create", "jx_hpke_create_suite", "jx_hpke_suite", "jx_hpke_stream", "jx_hpke_destroy",
+                    "jx_hpke_open_batch", "jx_hpke_open_batch_device", "jx_hpke_last_error")
+
+
+class UnsupportedSuite(EngineError):
+    """A KEM, KDF or AEAD id the engine does not open (include/jx_hpke.h: JX_HPKE_E_UNSUPPORTED)."""
 
 
 def application_info(label: bytes = LABEL_INPUT_SHARE, sender: int = ROLE_CLIENT, recipient: int = ROLE_HELPER) -> bytes:
@@ -44,6 +57,12 @@ def _declare(L):
     vp, u64, i32, u32 = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_int32, ctypes.c_uint32
     L.jx_hpke_create.restype = i32
     L.jx_hpke_create.argtypes = [vp, vp, vp, u32, i32, ctypes.POINTER(vp)]
+    L.jx_hpke_create_suite.restype = i32
+    L.jx_hpke_create_suite.argtypes = [u32, u32, u32, vp, vp, vp, u32, i32, ctypes.POINTER(vp)]
+    L.jx_hpke_suite.restype = i32
+    L.jx_hpke_suite.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]
+    L.jx_hpke_stream.restype = i32
+    L.jx_hpke_stream.argtypes = [vp, ctypes.POINTER(vp)]
     L.jx_hpke_destroy.restype = None
     L.jx_hpke_destroy.argtypes = [vp]
     L.jx_hpke_open_batch.restype = i32
@@ -61,9 +80,10 @@ def _p(a: np.ndarray):
 
 
 class HpkeOpener:
-    """One recipient key pair + application info on one GPU."""
+    """One recipient key pair of one HPKE suite + application info on one GPU."""
 
-    def __init__(self, private_key: bytes, public_key: bytes, info: bytes, device: int = 0):
+    def __init__(self, private_key: bytes, public_key: bytes, info: bytes, device: int = 0,
+                 kem_id: int = KEM_X25519_HKDF_SHA256, kdf_id: int = KDF_HKDF_SHA256, aead_id: int = AEAD_AES_128_GCM):
         if len(private_key) != 32 or len(public_key) != 32:
             raise ValueError("X25519 keys are 32 bytes")
         self._L = _declare(_lib.load())
@@ -71,15 +91,35 @@ class HpkeOpener:
         sk = np.frombuffer(private_key, np.uint8).copy()
         pk = np.frombuffer(public_key, np.uint8).copy()
         inf = np.frombuffer(info, np.uint8).copy() if info else np.zeros(1, np.uint8)
-        st = self._L.jx_hpke_create(_p(sk), _p(pk), _p(inf), len(info), device, ctypes.byref(h))
+        st = self._L.jx_hpke_create_suite(kem_id, kdf_id, aead_id, _p(sk), _p(pk), _p(inf), len(info), device,
+                                          ctypes.byref(h))
+        if st == E_UNSUPPORTED:
+            raise UnsupportedSuite(self._L.jx_hpke_last_error(None).decode())
         if st != 0:
-            raise EngineError(f"jx_hpke_create: status {st}")
+            raise EngineError(f"jx_hpke_create_suite: status {st}")
         self._h = h
+        kem, kdf, aead = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
+        self._L.jx_hpke_suite(h, ctypes.byref(kem), ctypes.byref(kdf), ctypes.byref(aead))
+        self._suite = (kem.value, kdf.value, aead.value)
+
+    @property
+    def suite(self) -> tuple[int, int, int]:
+        """(kem_id, kdf_id, aead_id) of the context, as jx_hpke_suite reports it."""
+        return self._suite
 
     @property
     def handle(self):
         """The jx_hpke context (for jx_helper_prep_encrypted_batch)."""
         return self._h
+
+    @property
+    def stream(self) -> int:
+        """The context's hipStream_t (jx_hpke_stream), on which the device-buffer open runs."""
+        s = ctypes.c_void_p()
+        st = self._L.jx_hpke_stream(self._h, ctypes.byref(s))
+        if st != 0:
+            raise EngineError(f"jx_hpke_stream: status {st}")
+        return s.value or 0
 
     def close(self):
         if getattr(self, "_h", None):
