@@ -5,9 +5,10 @@
  *   /root/reference/aggregator/src/aggregator.rs:1772-1832
  *     hpke::open(&hpke_keypair, &HpkeApplicationInfo::new(&Label::InputShare, &Role::Client,
  *                &Role::Helper), prepare_init.report_share().encrypted_input_share(), &aad)
- * (core/src/hpke.rs:200-230): RFC 9180 base mode, DHKEM(X25519, HKDF-SHA256) (0x0020) with any of
- * HKDF-SHA256 / -SHA384 / -SHA512 and AES-128-GCM / AES-256-GCM / ChaCha20Poly1305 (jx_hpke_create_suite;
- * the default is HKDF-SHA256 (0x0001), AES-128-GCM (0x0001), docs/samples/tasks.yaml:54-58). Once prepare
+ * (core/src/hpke.rs:200-230): RFC 9180 base mode, DHKEM(X25519, HKDF-SHA256) (0x0020) or DHKEM(P-256,
+ * HKDF-SHA256) (0x0010) with any of HKDF-SHA256 / -SHA384 / -SHA512 and AES-128-GCM / AES-256-GCM /
+ * ChaCha20Poly1305: the 18 suites the reference opens (jx_hpke_create_key; jx_hpke_create_suite for the X25519
+ * ones; the default is X25519, HKDF-SHA256 (0x0001), AES-128-GCM (0x0001), docs/samples/tasks.yaml:54-58). Once prepare
  * runs on the GPU this is the next per-report CPU cost (X25519 + key schedule + AEAD per report).
  *
  * Conventions as in jx_prio3.h: int32 status (0 = OK), caller-owned buffers, one context per
@@ -15,12 +16,14 @@
  * context); jx_hpke_last_error returns the calling thread's last failure. The host-buffer open takes its
  * device buffers from the device's arena (shared with the prepare engines) and synchronizes only the
  * context's stream. jx_helper_prep_encrypted_batch (jx_prio3.h) opens inside the prepare launch instead.
- *  - encs:        n x 32 bytes (HpkeCiphertext.encapsulated_key)
+ *  - encs:        n x jx_hpke_enc_len(h) bytes (HpkeCiphertext.encapsulated_key: 32 under X25519, 65 under
+ *                 P-256, the uncompressed SEC 1 point)
  *  - cts:         ciphertexts (payload || 16-byte tag) back to back; ct_offsets[n + 1], ciphertext i
  *                 is [ct_offsets[i], ct_offsets[i+1]) and at least 16 bytes
  *  - aads:        associated data back to back (the encoded InputShareAad), aad_offsets[n + 1]
  *  - plaintexts:  plaintext i (ct length - 16 bytes) at offset ct_offsets[i] - 16 * i
- *  - ok:          n bytes, 1 = opened, 0 = HpkeDecryptError (bad tag, bad length, all-zero DH)
+ *  - ok:          n bytes, 1 = opened, 0 = HpkeDecryptError (bad tag, bad length, all-zero DH, under P-256 an
+ *                 encapsulated key that is no point of the curve)
  */
 #ifndef JX_HPKE_H
 #define JX_HPKE_H
@@ -46,15 +49,26 @@ int32_t jx_hpke_create(const uint8_t sk[32], const uint8_t pk[32], const uint8_t
                        int32_t device, jx_hpke** out);
 /* The same for the suite of the keypair's HpkeConfig (messages/src/lib.rs:768-846: kem_id, kdf_id, aead_id):
  * KEM 0x0020 DHKEM(X25519, HKDF-SHA256); KDF 0x0001 HKDF-SHA256, 0x0002 HKDF-SHA384, 0x0003 HKDF-SHA512; AEAD
- * 0x0001 AES-128-GCM, 0x0002 AES-256-GCM, 0x0003 ChaCha20Poly1305: nine suites. Any other id (the P-256 KEM
- * 0x0010 among them) returns JX_HPKE_E_UNSUPPORTED, with the reason in jx_hpke_last_error: such a keypair stays
- * on the host path. jx_hpke_create is the (0x0020, 0x0001, 0x0001) case. Contexts of any suites may be passed
- * together to jx_helper_prep_encrypted_batch. */
+ * 0x0001 AES-128-GCM, 0x0002 AES-256-GCM, 0x0003 ChaCha20Poly1305: nine suites. Any other id returns
+ * JX_HPKE_E_UNSUPPORTED, with the reason in jx_hpke_last_error; that includes the P-256 KEM 0x0010, whose public
+ * key does not fit this call's 32 bytes (jx_hpke_create_key). jx_hpke_create is the (0x0020, 0x0001, 0x0001)
+ * case. Contexts of any suites may be passed together to jx_helper_prep_encrypted_batch[2]. */
 int32_t jx_hpke_create_suite(uint32_t kem_id, uint32_t kdf_id, uint32_t aead_id, const uint8_t sk[32],
                              const uint8_t pk[32], const uint8_t* info, uint32_t info_len, int32_t device,
                              jx_hpke** out);
+/* A keypair of either KEM, with the lengths of its keys. KEM 0x0020: sk_len = pk_len = 32, exactly
+ * jx_hpke_create_suite. KEM 0x0010, DHKEM(P-256, HKDF-SHA256): sk is the private key as 32 big-endian bytes
+ * (SerializePrivateKey), pk the public key as the 65-byte uncompressed SEC 1 point (SerializePublicKey);
+ * JX_HPKE_E_INVALID, with the reason in jx_hpke_last_error, unless sk_len == 32, 1 <= sk <= n - 1, pk_len == 65, pk is
+ * a point of the curve and pk == sk * G (computed on the host by the kernels' own code). Ids are checked first
+ * (JX_HPKE_E_UNSUPPORTED), then the keypair, then the device. */
+int32_t jx_hpke_create_key(uint32_t kem_id, uint32_t kdf_id, uint32_t aead_id, const uint8_t* sk, uint32_t sk_len,
+                           const uint8_t* pk, uint32_t pk_len, const uint8_t* info, uint32_t info_len, int32_t device,
+                           jx_hpke** out);
 /* The suite a context was created with (any of the three may be NULL). */
 int32_t jx_hpke_suite(const jx_hpke* h, uint32_t* kem_id, uint32_t* kdf_id, uint32_t* aead_id);
+/* The length of an encapsulated key under the context's KEM: 32 (X25519) or 65 (P-256); 0 for NULL. */
+int32_t jx_hpke_enc_len(const jx_hpke* h);
 void jx_hpke_destroy(jx_hpke* h);
 
 /* Host buffers. */

@@ -98,7 +98,9 @@ extern "C" {
 #define JX_OPEN_UNKNOWN_CONFIG 7             /* HpkeUnknownConfigId, "unknown_hpke_config_id" */
 /* key_index values besides keypair indices */
 #define JX_KEY_NONE 0xFF      /* no keypair (first: the config id is unknown; second: no fallback) */
-#define JX_KEY_MALFORMED 0xFE /* first only: the encapsulated key is not 32 bytes (HpkeDecryptError) */
+/* first only: the caller found the encapsulated key malformed (HpkeDecryptError without an open). A length that
+ * fits no keypair of the report is found by the engine itself (jx_helper_prep_encrypted_batch2). */
+#define JX_KEY_MALFORMED 0xFE
 #define JX_ENC_MAX_KEYPAIRS 8
 /* flags */
 #define JX_ENC_REQUIRE_TASKPROV 1u /* the task is provisioned by taskprov (aggregator.rs:1869-1879) */
@@ -228,7 +230,8 @@ int32_t jx_helper_prep_batch(jx_engine* e, uint64_t n, const uint8_t* nonces, co
  *   keypairs            nkeypairs (<= JX_ENC_MAX_KEYPAIRS) HPKE contexts on the engine's device, created with
  *                       the input-share application info (Label::InputShare, Client -> Helper)
  *   key_index[n x 2]    per report: first keypair, fallback keypair (JX_KEY_NONE / JX_KEY_MALFORMED above)
- *   encs[n x 32]        HpkeCiphertext.encapsulated_key
+ *   encs[n x 32]        HpkeCiphertext.encapsulated_key (X25519; a P-256 keypair here is a failed trial: see
+ *                       jx_helper_prep_encrypted_batch2)
  *   payloads            ciphertexts back to back; report i's is [payload_offsets[i], payload_offsets[i+1])
  *   flags               JX_ENC_REQUIRE_TASKPROV or 0
  * Public shares are fixed-length rows: a report whose public share has another length cannot go here (the
@@ -239,6 +242,21 @@ int32_t jx_helper_prep_encrypted_batch(jx_engine* e, uint64_t n, const uint8_t* 
                                        const uint8_t* encs, const uint8_t* payloads, const uint64_t* payload_offsets,
                                        uint32_t flags, const uint8_t* leader_prep_shares, uint8_t* out_prep_msgs,
                                        uint8_t* out_verdicts, uint8_t* out_open_status, uint64_t* out_batch_id);
+/* The same call for encapsulated keys of any length, so that one request may mix KEMs: encs holds them back to
+ * back, report i's is [enc_offsets[i], enc_offsets[i+1]) (enc_offsets[n + 1]; NULL: n x 32 bytes, the call above).
+ * A trial of a keypair can only succeed when the report's encapsulated key has the length of the keypair's KEM
+ * (jx_hpke_enc_len: 32 for X25519, 65 for P-256); any other trial fails without an open, as the hpke crate's
+ * deserialisation of the encapsulated key does, and a report none of whose keypairs fits gets
+ * JX_OPEN_HPKE_DECRYPT_ERROR (JX_OPEN_UNKNOWN_CONFIG still comes first when key_index[2i] is JX_KEY_NONE).
+ * Reports with 65-byte keys are opened by a kernel of their own in the same launch; a request without any runs
+ * exactly what the call above runs. */
+int32_t jx_helper_prep_encrypted_batch2(jx_engine* e, uint64_t n, const uint8_t* nonces, const uint64_t* times,
+                                        const uint8_t* public_shares, const uint8_t task_id[32],
+                                        jx_hpke* const* keypairs, uint32_t nkeypairs, const uint8_t* key_index,
+                                        const uint8_t* encs, const uint64_t* enc_offsets, const uint8_t* payloads,
+                                        const uint64_t* payload_offsets, uint32_t flags,
+                                        const uint8_t* leader_prep_shares, uint8_t* out_prep_msgs, uint8_t* out_verdicts,
+                                        uint8_t* out_open_status, uint64_t* out_batch_id);
 /* Handle of the most recently prepared batch if it is still resident (0 otherwise). */
 int32_t jx_engine_batch_id(const jx_engine* e, uint64_t* batch_id);
 /* Resident batches and the device bytes they hold (either pointer nullable). */

@@ -334,7 +334,7 @@ def handle_aggregate_init_encrypted(engine: HelperEngine, opener, hpke_config_id
                                     require_taskprov: bool = False, report_deadline: int | None = None,
                                     inject_tx_failures: int = 0) -> AggregateInitOutcome:
     """The helper's aggregate-init loop from the encrypted report shares (aggregator.rs:1763-2013), with the
-    HPKE open inside the prepare launch (jx_helper_prep_encrypted_batch; coalesced with other jobs when the
+    HPKE open inside the prepare launch (jx_helper_prep_encrypted_batch2; coalesced with other jobs when the
     engine coalesces): per report, the task's keypair (opener, config id hpke_config_id) and then the
     aggregator's global keypair for the report's config id (global_keypairs: {config_id: HpkeOpener}) are
     tried (:1781-1832), the PlaintextInputShare is decoded and its extensions checked (:1834-1893), the payload
@@ -344,7 +344,7 @@ def handle_aggregate_init_encrypted(engine: HelperEngine, opener, hpke_config_id
     public share), ReportTooEarly, VdafPrepError. A report whose public share has the wrong length cannot ride
     the fixed-stride device rows: it is opened alone (janus_amd.hpke) and fails with InvalidMessage unless an
     earlier check fails it first."""
-    from .engine import KEY_MALFORMED, KEY_NONE, OPEN_STATUS
+    from .engine import KEY_NONE, OPEN_STATUS
 
     v = engine.vdaf
     n = len(prepare_inits)
@@ -378,9 +378,7 @@ def handle_aggregate_init_encrypted(engine: HelperEngine, opener, hpke_config_id
             continue
         if first is None:
             k0, k1 = KEY_NONE, KEY_NONE
-        elif len(ct.encapsulated_key) != 32:
-            k0, k1 = KEY_MALFORMED, KEY_NONE
-        else:
+        else:  # a keypair whose KEM has another encapsulated-key length is a failed trial (the engine's rule)
             k0, k1 = key_slot(first), (key_slot(second) if second is not None else KEY_NONE)
         if len(keypairs) > 8:
             raise ValueError("more than JX_ENC_MAX_KEYPAIRS distinct keypairs in one request")
@@ -395,9 +393,7 @@ def handle_aggregate_init_encrypted(engine: HelperEngine, opener, hpke_config_id
         nonces = np.frombuffer(b"".join(x.report_id for x in md), np.uint8).reshape(m, 16)
         times = np.array([x.time for x in md], np.uint64)
         ps = np.frombuffer(b"".join(prepare_inits[i].report_share.public_share for i in rows), np.uint8)
-        encs = np.frombuffer(b"".join(
-            (lambda e: e if len(e) == 32 else bytes(32))(prepare_inits[i].report_share.encrypted_input_share
-                                                           .encapsulated_key) for i in rows), np.uint8).reshape(m, 32)
+        encs = [prepare_inits[i].report_share.encrypted_input_share.encapsulated_key for i in rows]
         payloads = [prepare_inits[i].report_share.encrypted_input_share.payload for i in rows]
         # a leader message that is not Initialize, or a prep share of the wrong length, fails inside
         # helper_initialized, after the open: the row rides with a zero prep share and is fixed up below

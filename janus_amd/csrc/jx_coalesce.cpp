@@ -98,6 +98,7 @@ struct Lane {
   bool full = false;      // a caller could not fit: close now
   bool enc = false;       // the layout holds the encrypted-input regions
   bool has_enc = false;   // a job of this gather is encrypted
+  bool has_enc65 = false; // ... and holds a row with a 65-byte (P-256) encapsulated key
   uint64_t reports = 0, cap_reports = 0, ct_bytes = 0, ct_cap = 0;
   uint32_t copying = 0;
   std::atomic<uint32_t> unconsumed{0};  // callers still to copy their results out (the last one frees the lane)
@@ -431,8 +432,8 @@ static int32_t launch_lane(Coalescer* C, Lane& L, std::string& err) {
     const HpkeKeyRow* key_rows = reinterpret_cast<const HpkeKeyRow*>(L.h_in + L.o_keys);
     bool suites = false;
     for (size_t k = 0; k < L.keys.size(); k++)
-      suites = suites || key_rows[k].kdf != 1 || key_rows[k].aead != 1;
-    s = launch_hpke_rows(ha, suites, q->stream);
+      suites = suites || key_rows[k].kdf != 1 || key_rows[k].aead != 1 || key_rows[k].kem != 0x20;
+    s = launch_hpke_rows(ha, suites, L.has_enc65, q->stream);
     if (s != hipSuccess) return bad(s, "hpke open");
   }
   rc = prep_core(q, m, q->d_nonces, q->d_ps, q->d_his, q->d_lps, q->d_verdicts, q->d_msgs, staging_outs(q),
@@ -873,6 +874,7 @@ static Lane* reserve(Coalescer* C, std::unique_lock<std::mutex>& lk, CReq* r, in
         L.full = false;
         L.all_back = false;
         L.has_enc = false;
+        L.has_enc65 = false;
         L.reports = 0;
         L.ct_bytes = 0;
         L.keys.clear();
@@ -889,12 +891,15 @@ static Lane* reserve(Coalescer* C, std::unique_lock<std::mutex>& lk, CReq* r, in
 }
 
 // Lay out one job's EncRows (its ciphertexts at ct_base + their offset within the job).
-void fill_enc_rows(const EncJob& j, uint64_t n, EncRow* rows, uint64_t ct_base, const uint8_t* key_map) {
-  const uint64_t c0 = j.payload_offsets[0];
+uint64_t fill_enc_rows(const EncJob& j, uint64_t n, EncRow* rows, uint64_t ct_base, const uint8_t* key_map,
+                       uint8_t* enc65) {
+  const uint64_t c0 = j.payload_offsets[0], enc65_base = ct_base + j.payload_bytes(n);
+  uint64_t n65 = 0;
+  uint32_t klen[JX_ENC_MAX_KEYPAIRS];
+  for (uint32_t k = 0; k < j.nkeys; k++) klen[k] = hpke_enc_len(j.keypairs[k]);
   for (uint64_t i = 0; i < n; i++) {
     EncRow& w = rows[i];
     memset(&w, 0, sizeof w);
-    memcpy(w.enc, j.encs + 32 * i, 32);
     memcpy(w.task_id, j.task_id, 32);
     const uint64_t t = j.times[i];
     for (int b = 0; b < 8; b++) w.time_be[b] = (uint8_t)(t >> (56 - 8 * b));
@@ -902,10 +907,24 @@ void fill_enc_rows(const EncJob& j, uint64_t n, EncRow* rows, uint64_t ct_base, 
     w.ct_len = (uint32_t)(j.payload_offsets[i + 1] - j.payload_offsets[i]);
     const uint8_t k0 = j.key_index[2 * i], k1 = j.key_index[2 * i + 1];
     w.flags = ENC_ROW_ENCRYPTED | ((j.flags & JX_ENC_REQUIRE_TASKPROV) ? ENC_ROW_REQUIRE_TASKPROV : 0);
-    if (k0 == JX_KEY_MALFORMED) w.flags |= ENC_ROW_MALFORMED;
+    // a trial can only succeed when the encapsulated key has the length of the keypair's KEM (32: X25519, 65:
+    // P-256); the others fail as the hpke crate's deserialisation does, on the device by the key row's KEM id
+    const uint64_t len = j.enc_len(i);
+    const bool fits = (k0 < j.nkeys && klen[k0] == len) || (k1 < j.nkeys && klen[k1] == len);
+    if (k0 == JX_KEY_MALFORMED || (k0 < j.nkeys && !fits)) {
+      w.flags |= ENC_ROW_MALFORMED;
+    } else if (fits && len == 65) {
+      w.flags |= ENC_ROW_ENC65;
+      w.enc65_off = enc65_base + 65 * n65;
+      memcpy(enc65 + 65 * n65, j.enc(i), 65);
+      n65++;
+    } else if (len == 32) {
+      memcpy(w.enc, j.enc(i), 32);
+    }
     w.key0 = k0 < j.nkeys ? key_map[k0] : (k0 == JX_KEY_MALFORMED ? (uint8_t)0 : (uint8_t)JX_KEY_NONE);
     w.key1 = k1 < j.nkeys ? key_map[k1] : (uint8_t)JX_KEY_NONE;
   }
+  return n65;
 }
 
 // The coalesced prepare of one job (both roles).
@@ -956,6 +975,7 @@ static int32_t coalesced(jx_engine* e, bool leader, uint64_t n, const uint8_t* n
   lk.unlock();
   // copy this job's rows into the lane's pinned input (in parallel with the other callers)
   const uint64_t f = r.first;
+  uint64_t n65 = 0;
   memcpy(L->h_in + L->o_non + f * 16, nonces, n * 16);
   if (c.ps_bytes) memcpy(L->h_in + L->o_ps + f * c.ps_bytes, ps, n * c.ps_bytes);
   if (leader) {
@@ -965,8 +985,9 @@ static int32_t coalesced(jx_engine* e, bool leader, uint64_t n, const uint8_t* n
     memcpy(L->h_in + L->o_lps + f * c.lps_bytes, lps, n * c.lps_bytes);
     EncRow* rows = L->enc ? reinterpret_cast<EncRow*>(L->h_in + L->o_enc) + f : nullptr;
     if (enc) {
-      fill_enc_rows(*enc, n, rows, r.ct_first, r.key_map);
-      memcpy(L->h_in + L->o_ct + r.ct_first, enc->payloads + enc->payload_offsets[0], r.ct_bytes);
+      const uint64_t pb = enc->payload_bytes(n);
+      n65 = fill_enc_rows(*enc, n, rows, r.ct_first, r.key_map, L->h_in + L->o_ct + r.ct_first + pb);
+      memcpy(L->h_in + L->o_ct + r.ct_first, enc->payloads + enc->payload_offsets[0], pb);
     } else if (rows) {
       memset(rows, 0, n * sizeof(EncRow));  // plain reports: the open kernel leaves their rows alone
     }
@@ -979,6 +1000,7 @@ static int32_t coalesced(jx_engine* e, bool leader, uint64_t n, const uint8_t* n
     for (uint64_t i = 0; i < n; i++) memcpy(dst + i * vb, row, vb);
   }
   lk.lock();
+  if (n65) L->has_enc65 = true;
   if (--L->copying == 0) C->role[r.role].cv.notify_one();
   lk.unlock();
   {

@@ -1346,6 +1346,19 @@ int32_t jx_helper_prep_encrypted_batch(jx_engine* e, uint64_t n, const uint8_t* 
                                        const uint8_t* encs, const uint8_t* payloads, const uint64_t* payload_offsets,
                                        uint32_t flags, const uint8_t* leader_prep_shares, uint8_t* out_prep_msgs,
                                        uint8_t* out_verdicts, uint8_t* out_open_status, uint64_t* out_batch_id) {
+  // the case of the call below in which every encapsulated key is 32 bytes
+  return jx_helper_prep_encrypted_batch2(e, n, nonces, times, public_shares, task_id, keypairs, nkeypairs, key_index, encs,
+                                         nullptr, payloads, payload_offsets, flags, leader_prep_shares, out_prep_msgs,
+                                         out_verdicts, out_open_status, out_batch_id);
+}
+
+int32_t jx_helper_prep_encrypted_batch2(jx_engine* e, uint64_t n, const uint8_t* nonces, const uint64_t* times,
+                                        const uint8_t* public_shares, const uint8_t task_id[32],
+                                        jx_hpke* const* keypairs, uint32_t nkeypairs, const uint8_t* key_index,
+                                        const uint8_t* encs, const uint64_t* enc_offsets, const uint8_t* payloads,
+                                        const uint64_t* payload_offsets, uint32_t flags,
+                                        const uint8_t* leader_prep_shares, uint8_t* out_prep_msgs, uint8_t* out_verdicts,
+                                        uint8_t* out_open_status, uint64_t* out_batch_id) {
   if (out_batch_id) *out_batch_id = 0;
   if (!e || (n && (!nonces || !times || !task_id || !key_index || !encs || !payload_offsets || !leader_prep_shares ||
                    !out_verdicts)))
@@ -1365,6 +1378,12 @@ int32_t jx_helper_prep_encrypted_batch(jx_engine* e, uint64_t n, const uint8_t* 
   }
   if (n && payload_offsets[n] > payload_offsets[0] && !payloads) return JX_E_INVALID;
   EncJob job;
+  for (uint64_t i = 0; enc_offsets && i < n; i++) {
+    if (enc_offsets[i + 1] < enc_offsets[i])
+      return fail(e, JX_E_INVALID, "encrypted prepare: encapsulated-key offsets decreasing");
+    job.enc65 += enc_offsets[i + 1] - enc_offsets[i] == 65;
+  }
+  job.enc_offsets = enc_offsets;
   job.times = times;
   job.task_id = task_id;
   job.keypairs = keypairs;
@@ -1398,7 +1417,9 @@ int32_t jx_helper_prep_encrypted_batch(jx_engine* e, uint64_t n, const uint8_t* 
         hpke_key_row(keypairs[k], &keys[k]);
         suites = suites || !hpke_default_suite(keypairs[k]);
       }
-      fill_enc_rows(job, n, rows.data(), 0, key_map);
+      // the 65-byte encapsulated keys follow the ciphertexts in the launch's ciphertext region
+      std::vector<uint8_t> enc65(job.enc65 ? 65 * job.enc65 : 1);
+      const uint64_t pb = job.payload_bytes(n), n65 = fill_enc_rows(job, n, rows.data(), 0, key_map, enc65.data());
       e->enc_ct_bytes = ct ? ct : 1;
       Stage st;
       int32_t r = stage_acquire(e, n, SG_IN | SG_HIN | SG_ENC | helper_meas_flag(c) | SG_PREP, st);
@@ -1407,12 +1428,13 @@ int32_t jx_helper_prep_encrypted_batch(jx_engine* e, uint64_t n, const uint8_t* 
       if (c.ps_bytes) HIPCHK(e, hipMemcpyAsync(e->d_ps, public_shares, n * c.ps_bytes, hipMemcpyHostToDevice, e->stream));
       HIPCHK(e, hipMemcpyAsync(e->d_lps, leader_prep_shares, n * c.lps_bytes, hipMemcpyHostToDevice, e->stream));
       HIPCHK(e, hipMemcpyAsync(e->d_encrows, rows.data(), n * sizeof(EncRow), hipMemcpyHostToDevice, e->stream));
-      if (ct) HIPCHK(e, hipMemcpyAsync(e->d_ct, payloads + payload_offsets[0], ct, hipMemcpyHostToDevice, e->stream));
+      if (pb) HIPCHK(e, hipMemcpyAsync(e->d_ct, payloads + payload_offsets[0], pb, hipMemcpyHostToDevice, e->stream));
+      if (n65) HIPCHK(e, hipMemcpyAsync(e->d_ct + pb, enc65.data(), 65 * n65, hipMemcpyHostToDevice, e->stream));
       if (nkeypairs)
         HIPCHK(e, hipMemcpyAsync(e->d_keys, keys.data(), nkeypairs * sizeof(HpkeKeyRow), hipMemcpyHostToDevice, e->stream));
       HpkeRowsArgs ha{n, e->d_encrows, e->d_ct, e->d_pt, e->d_keys, nkeypairs, B->nonces, e->d_ps, c.ps_bytes,
                       e->d_his, c.his_bytes, e->d_status};
-      HIPCHK(e, launch_hpke_rows(ha, suites, e->stream));
+      HIPCHK(e, launch_hpke_rows(ha, suites, n65 != 0, e->stream));
       r = prep_core(e, n, B->nonces, e->d_ps, e->d_his, e->d_lps, B->verdicts, B->msgs, B->outs);
       if (r) return r;
       HIPCHK(e, launch_open_mask(e->d_status, B->verdicts, n, e->stream));

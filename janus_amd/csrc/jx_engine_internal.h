@@ -136,21 +136,32 @@ struct EncJob {
   uint32_t nkeys = 0;
   const uint8_t* key_index = nullptr;  // n x 2
   const uint8_t* encs = nullptr;
+  const uint64_t* enc_offsets = nullptr;  // n + 1 (jx_helper_prep_encrypted_batch2); null: n x 32 bytes
+  uint64_t enc65 = 0;                     // encapsulated keys of 65 bytes (P-256) among them
   const uint8_t* payloads = nullptr;
   const uint64_t* payload_offsets = nullptr;  // n + 1
   uint32_t flags = 0;
-  uint64_t ct_bytes(uint64_t n) const { return payload_offsets[n] - payload_offsets[0]; }
+  uint64_t payload_bytes(uint64_t n) const { return payload_offsets[n] - payload_offsets[0]; }
+  // what the job takes of a launch's ciphertext region: its ciphertexts, then its 65-byte encapsulated keys
+  uint64_t ct_bytes(uint64_t n) const { return payload_bytes(n) + 65 * enc65; }
+  uint64_t enc_len(uint64_t i) const { return enc_offsets ? enc_offsets[i + 1] - enc_offsets[i] : 32; }
+  const uint8_t* enc(uint64_t i) const { return encs + (enc_offsets ? enc_offsets[i] : 32 * i); }
 };
 // The job's EncRows, ciphertexts at ct_base + their offset within the job; key_map: the job's keypair
-// index -> the launch's key-table row.
-void fill_enc_rows(const EncJob& j, uint64_t n, jx::EncRow* rows, uint64_t ct_base, const uint8_t* key_map);
+// index -> the launch's key-table row. The one place that copies encapsulated keys: a 32-byte one into its row, a
+// 65-byte one that a P-256 keypair of the row can try to enc65 (the host copy of the launch's ciphertext region
+// at ct_base + the job's payload bytes; ENC_ROW_ENC65). A key whose length fits neither keypair's KEM marks the
+// row malformed. Returns the number of ENC_ROW_ENC65 rows.
+uint64_t fill_enc_rows(const EncJob& j, uint64_t n, jx::EncRow* rows, uint64_t ct_base, const uint8_t* key_map,
+                       uint8_t* enc65);
 // jx_hpke.hip
 int hpke_device(const jx_hpke* h);
 void hpke_key_row(const jx_hpke* h, jx::HpkeKeyRow* out);
-bool hpke_default_suite(const jx_hpke* h);  // (HKDF-SHA256, AES-128-GCM)
-// suites: the launch's key table holds a key of another suite than the default (every row then goes through
-// hpke_rows_suite_kernel)
-hipError_t launch_hpke_rows(const jx::HpkeRowsArgs& a, bool suites, hipStream_t s);
+bool hpke_default_suite(const jx_hpke* h);  // X25519 with (HKDF-SHA256, AES-128-GCM)
+uint32_t hpke_enc_len(const jx_hpke* h);    // the length of its KEM's encapsulated keys: 32 or 65
+// suites: the launch's key table holds a key of another suite than the default (every 32-byte row then goes through
+// hpke_rows_suite_kernel); p256_rows: the launch holds an ENC_ROW_ENC65 row (hpke_rows_p256_kernel runs too)
+hipError_t launch_hpke_rows(const jx::HpkeRowsArgs& a, bool suites, bool p256_rows, hipStream_t s);
 hipError_t launch_open_mask(const uint8_t* status, uint8_t* verdicts, uint64_t n, hipStream_t s);
 
 struct Coalescer;  // jx_coalesce.cpp

@@ -10,8 +10,12 @@
 // and hpke_rows_suite_kernel, which read the suite from the key row and dispatch per lane. They are launched only
 // for a context, or a launch's key table, that holds a key outside the default suite (then for every row of the
 // launch), so the default suite's kernels and their register budget are what they were.
+// The second KEM the reference opens under, DHKEM(P-256, HKDF-SHA256) (0x0010; jx_p256.h), has a third pair,
+// hpke_open_p256_kernel and hpke_rows_p256_kernel: its encapsulated keys are 65 bytes, so the rows of a prepare
+// launch partition by that length (a trial of a keypair of the other KEM fails without an open), the X25519 rows
+// kernels skip the 65-byte rows, and the P-256 rows kernel, launched only when the launch holds one, takes them.
 //
-// Two kernels (each with its suite twin):
+// Two kernels (each with its suite twin and its P-256 twin):
 //  - hpke_open_kernel: the standalone batch open of include/jx_hpke.h (caller's ciphertexts and AADs);
 //  - hpke_rows_kernel: the open INSIDE a helper prepare launch (jx_helper_prep_encrypted_batch, alone or
 //    coalesced): per report it builds the InputShareAad from the report's task id, id, time and public share
@@ -188,13 +192,11 @@ __device__ void load_enc(const uint8_t* p, uint32_t enc[8]) {
 
 // One open under the key's own suite (jx_hpke_suites.h): the context, then the suite's AEAD with sequence
 // number 0 (the nonce is the base nonce). The associated data comes a byte at a time from aad_byte(i).
+// (suite_aead_open: the AEAD of either KEM's context, inlined into both callers.)
 template <class AadByte>
-__device__ bool suite_open(const uint8_t* sbox, const HpkeKeyRow& key, const uint32_t zist[8], const uint32_t zost[8],
-                           const uint32_t enc[8], uint64_t alen, AadByte aad_byte, const uint8_t* ct, uint64_t clen,
-                           uint8_t* pt) {
-  uint8_t kb[32], nb[12];
-  const uint32_t aead = key.aead;
-  if (!hpke_suite_context(key.sk, key.pk, key.ksc, key.kdf, aead, zist, zost, enc, kb, nb)) return false;
+__device__ __forceinline__ bool suite_aead_open(const uint8_t* sbox, uint32_t aead, const uint8_t kb[32],
+                                                const uint8_t nb[12], uint64_t alen, AadByte aad_byte, const uint8_t* ct,
+                                                uint64_t clen, uint8_t* pt) {
   uint32_t kw[8], nw[3];  // little-endian words
   for (int i = 0; i < 8; i++)
     kw[i] = (uint32_t)kb[4 * i] | ((uint32_t)kb[4 * i + 1] << 8) | ((uint32_t)kb[4 * i + 2] << 16) |
@@ -233,6 +235,25 @@ __device__ bool suite_open(const uint8_t* sbox, const HpkeKeyRow& key, const uin
     if (ok) gcm_decrypt<14>(sbox, rk, nw, ct, clen, pt);
   }
   return ok;
+}
+template <class AadByte>
+__device__ bool suite_open(const uint8_t* sbox, const HpkeKeyRow& key, const uint32_t zist[8], const uint32_t zost[8],
+                           const uint32_t enc[8], uint64_t alen, AadByte aad_byte, const uint8_t* ct, uint64_t clen,
+                           uint8_t* pt) {
+  uint8_t kb[32], nb[12];
+  const uint32_t aead = key.aead;
+  if (!hpke_suite_context(key.sk, key.pk, key.ksc, key.kdf, aead, zist, zost, enc, kb, nb)) return false;
+  return suite_aead_open(sbox, aead, kb, nb, alen, aad_byte, ct, clen, pt);
+}
+// The same under DHKEM(P-256, HKDF-SHA256): enc is the 65-byte encapsulated key where it lies in device memory. An
+// invalid point (jx_p256.h) is a failed open.
+template <class AadByte>
+__device__ bool p256_open(const uint8_t* sbox, const HpkeKeyRow& key, const uint8_t* enc, uint64_t alen,
+                          AadByte aad_byte, const uint8_t* ct, uint64_t clen, uint8_t* pt) {
+  uint8_t kb[32], nb[12];
+  const uint32_t aead = key.aead;
+  if (!hpke_p256_context(key.sk, (const uint8_t*)key.pk, key.pky, key.ksc, key.kdf, aead, enc, kb, nb)) return false;
+  return suite_aead_open(sbox, aead, kb, nb, alen, aad_byte, ct, clen, pt);
 }
 
 // The standalone batch open. SUITE false: the default suite alone (register-resident context); true: the suite of
@@ -277,6 +298,21 @@ __global__ __launch_bounds__(64) void hpke_open_suite_kernel(HpkeCfg cfg, HpkeBu
   open_body<true>(sbox, cfg, b);
 }
 
+// The standalone batch open of a P-256 context: encapsulated keys at a stride of 65 bytes.
+__global__ __launch_bounds__(64) void hpke_open_p256_kernel(HpkeCfg cfg, HpkeBufs b) {
+  __shared__ uint8_t sbox[256];
+  for (int i = threadIdx.x; i < 256; i += blockDim.x) sbox[i] = AES_SBOX[i];
+  __syncthreads();
+  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= b.n) return;
+  const uint64_t c0 = b.ct_off[r], c1 = b.ct_off[r + 1];
+  const uint64_t a0 = b.aad_off[r], a1 = b.aad_off[r + 1];
+  const uint8_t* aad = b.aads + a0;
+  const bool ok = c1 - c0 >= 16 && p256_open(sbox, cfg.key, b.encs + 65 * r, a1 - a0, [&](uint64_t i) { return aad[i]; },
+                                             b.cts + c0, c1 - c0 - 16, b.pts + c0 - 16 * r);
+  b.ok[r] = (uint8_t)ok;
+}
+
 // ---------------------------------------------------------------------------- open inside a prepare launch
 
 struct RowsArgs {
@@ -297,15 +333,25 @@ __device__ uint8_t aad_byte(const EncRow& e, const uint8_t* nonce, const uint8_t
 // The open inside a prepare launch. SUITE false: every key of the launch's table is of the default suite; true: each
 // key's own suite (lanes of one wave may hold different ones). What follows the open is the same code.
 // (ra by value: by reference the kernel's argument costs hpke_rows_kernel four more spilled registers.)
-template <bool SUITE>
+// P256: the rows whose encapsulated key is 65 bytes (ENC_ROW_ENC65), which the other two skip; a trial with a key
+// of the other KEM fails without an open, as the hpke crate's deserialisation of the encapsulated key does. A
+// table of default-suite keys alone never comes with such a row (fill_enc_rows), so that body knows neither.
+template <bool SUITE, bool P256 = false>
 __device__ __forceinline__ void rows_body(const uint8_t* sbox, const RowsArgs ra) {
   const HpkeRowsArgs& a = ra.a;
   const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.n) return;
   const EncRow& e = a.rows[r];
-  if (!(e.flags & ENC_ROW_ENCRYPTED)) {  // a plain report of the launch: its helper input share was uploaded
-    a.status[r] = JX_OPEN_OK;
-    return;
+  if constexpr (P256) {
+    if ((e.flags & (ENC_ROW_ENCRYPTED | ENC_ROW_ENC65)) != (ENC_ROW_ENCRYPTED | ENC_ROW_ENC65)) return;
+  } else {
+    if (!(e.flags & ENC_ROW_ENCRYPTED)) {  // a plain report of the launch: its helper input share was uploaded
+      a.status[r] = JX_OPEN_OK;
+      return;
+    }
+    if constexpr (SUITE) {
+      if (e.flags & ENC_ROW_ENC65) return;  // hpke_rows_p256_kernel's
+    }
   }
   uint8_t* his = a.his + (uint64_t)a.his_bytes * r;
   uint32_t st = JX_OPEN_OK;
@@ -316,10 +362,10 @@ __device__ __forceinline__ void rows_body(const uint8_t* sbox, const RowsArgs ra
   if (e.key0 == JX_KEY_NONE) {
     st = JX_OPEN_UNKNOWN_CONFIG;  // neither the task nor the global keys hold the config id
   } else if ((e.flags & ENC_ROW_MALFORMED) || clen_all < 16) {
-    st = JX_OPEN_HPKE_DECRYPT_ERROR;  // an encapsulated key that is not 32 bytes, a ciphertext without a tag
+    st = JX_OPEN_HPKE_DECRYPT_ERROR;  // an encapsulated key that fits neither keypair's KEM, a ciphertext without a tag
   } else {
     uint32_t enc[8];
-    load_enc(e.enc, enc);
+    if constexpr (!P256) load_enc(e.enc, enc);
     const uint8_t* nonce = a.nonces + 16 * r;
     const uint8_t* ps = a.ps + (uint64_t)a.ps_bytes * r;
     const uint64_t alen = 60 + a.ps_bytes;
@@ -345,7 +391,12 @@ __device__ __forceinline__ void rows_body(const uint8_t* sbox, const RowsArgs ra
                                   },
                                   ct, clen);
         if (ok) gcm_decrypt<10>(sbox, rk, nonce3, ct, clen, pt);
+      } else if constexpr (P256) {
+        if (a.keys[kidx].kem != (uint8_t)HPKE_KEM_P256_SHA256) continue;
+        ok = p256_open(sbox, a.keys[kidx], a.cts + e.enc65_off, alen,
+                       [&](uint64_t i) { return aad_byte(e, nonce, ps, a.ps_bytes, i); }, ct, clen, pt);
       } else {
+        if (a.keys[kidx].kem != (uint8_t)HPKE_KEM_X25519_SHA256) continue;
         ok = suite_open(sbox, a.keys[kidx], ra.zero_ist, ra.zero_ost, enc, alen,
                         [&](uint64_t i) { return aad_byte(e, nonce, ps, a.ps_bytes, i); }, ct, clen, pt);
       }
@@ -419,6 +470,13 @@ __global__ __launch_bounds__(64) void hpke_rows_suite_kernel(RowsArgs ra) {
   rows_body<true>(sbox, ra);
 }
 
+__global__ __launch_bounds__(64) void hpke_rows_p256_kernel(RowsArgs ra) {
+  __shared__ uint8_t sbox[256];
+  for (int i = threadIdx.x; i < 256; i += blockDim.x) sbox[i] = AES_SBOX[i];
+  __syncthreads();
+  rows_body<true, true>(sbox, ra);
+}
+
 __global__ __launch_bounds__(256) void open_mask_kernel(const uint8_t* status, uint8_t* verdicts, uint64_t n) {
   const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (r < n && status[r] != JX_OPEN_OK) verdicts[r] = JX_OPEN_FAILURE;
@@ -428,7 +486,8 @@ __global__ __launch_bounds__(256) void open_mask_kernel(const uint8_t* status, u
 
 struct jx_hpke {
   HpkeCfg cfg{};
-  bool default_suite = true;  // (HKDF-SHA256, AES-128-GCM): opened by hpke_open_kernel / hpke_rows_kernel
+  bool default_suite = true;  // X25519 with (HKDF-SHA256, AES-128-GCM): opened by hpke_open_kernel / hpke_rows_kernel
+  uint32_t kem = HPKE_KEM_X25519_SHA256;
   int device = 0;
   hipStream_t stream = nullptr;
   jxi::Arena* arena = nullptr;  // the device's arena: the host-buffer open's device buffers
@@ -448,10 +507,12 @@ static int32_t hfail(int32_t code, const std::string& m) {
     if (_st != hipSuccess) return hfail(JX_HPKE_E_HIP, std::string(#call) + ": " + hipGetErrorString(_st)); \
   } while (0)
 
-// the default suite keeps its own kernel; any other goes through the suite kernel
+// the default suite keeps its own kernel; any other goes through the suite kernel of its KEM
 static void launch_open(const jx_hpke* h, const HpkeBufs& b) {
   const dim3 grid((uint32_t)((b.n + 63) / 64)), block(64);
-  if (h->default_suite) {
+  if (h->kem == HPKE_KEM_P256_SHA256) {
+    hipLaunchKernelGGL(hpke_open_p256_kernel, grid, block, 0, h->stream, h->cfg, b);
+  } else if (h->default_suite) {
     HpkeDefaultCfg d{};
     memcpy(d.sk, h->cfg.key.sk, 32);
     memcpy(d.pk, h->cfg.key.pk, 32);
@@ -468,8 +529,9 @@ namespace jxi {
 int hpke_device(const jx_hpke* h) { return h->device; }
 void hpke_key_row(const jx_hpke* h, HpkeKeyRow* out) { *out = h->cfg.key; }
 bool hpke_default_suite(const jx_hpke* h) { return h->default_suite; }
+uint32_t hpke_enc_len(const jx_hpke* h) { return jx::hpke_enc_len(h->kem); }
 
-hipError_t launch_hpke_rows(const HpkeRowsArgs& a, bool suites, hipStream_t s) {
+hipError_t launch_hpke_rows(const HpkeRowsArgs& a, bool suites, bool p256_rows, hipStream_t s) {
   if (a.n == 0) return hipSuccess;
   RowsArgs ra;
   ra.a = a;
@@ -480,6 +542,8 @@ hipError_t launch_hpke_rows(const HpkeRowsArgs& a, bool suites, hipStream_t s) {
     hipLaunchKernelGGL(hpke_rows_suite_kernel, dim3((uint32_t)((a.n + 63) / 64)), dim3(64), 0, s, ra);
   else
     hipLaunchKernelGGL(hpke_rows_kernel, dim3((uint32_t)((a.n + 63) / 64)), dim3(64), 0, s, ra);
+  // the rows with a 65-byte encapsulated key (the others' rows it skips; both write his / status of their own rows)
+  if (p256_rows) hipLaunchKernelGGL(hpke_rows_p256_kernel, dim3((uint32_t)((a.n + 63) / 64)), dim3(64), 0, s, ra);
   return hipGetLastError();
 }
 
@@ -507,30 +571,56 @@ int32_t jx_hpke_create_suite(uint32_t kem_id, uint32_t kdf_id, uint32_t aead_id,
   if (!hpke_suite_supported(kem_id, kdf_id, aead_id))
     return hfail(JX_HPKE_E_UNSUPPORTED,
                  "unsupported HPKE suite (KEM " + std::to_string(kem_id) + ", KDF " + std::to_string(kdf_id) + ", AEAD " +
-                     std::to_string(aead_id) + "): KEM 0x0020 (X25519), KDF 1..3 (HKDF-SHA256/384/512), AEAD 1..3 "
-                     "(AES-128-GCM, AES-256-GCM, ChaCha20Poly1305)");
+                     std::to_string(aead_id) + "): KEM 0x0020 (X25519) with 32-byte keys (KEM 0x0010, P-256, has 65-byte "
+                     "public keys: jx_hpke_create_key), KDF 1..3 (HKDF-SHA256/384/512), AEAD 1..3 (AES-128-GCM, "
+                     "AES-256-GCM, ChaCha20Poly1305)");
+  return jx_hpke_create_key(kem_id, kdf_id, aead_id, sk, 32, pk, 32, info, info_len, device, out);
+}
+
+int32_t jx_hpke_create_key(uint32_t kem_id, uint32_t kdf_id, uint32_t aead_id, const uint8_t* sk, uint32_t sk_len,
+                           const uint8_t* pk, uint32_t pk_len, const uint8_t* info, uint32_t info_len, int32_t device,
+                           jx_hpke** out) {
+  if (!sk || !pk || !out || (info_len && !info)) return JX_HPKE_E_INVALID;
+  *out = nullptr;
+  if (!hpke_key_supported(kem_id, kdf_id, aead_id))
+    return hfail(JX_HPKE_E_UNSUPPORTED,
+                 "unsupported HPKE suite (KEM " + std::to_string(kem_id) + ", KDF " + std::to_string(kdf_id) + ", AEAD " +
+                     std::to_string(aead_id) + "): KEM 0x0020 (X25519) or 0x0010 (P-256), KDF 1..3 (HKDF-SHA256/384/512), "
+                     "AEAD 1..3 (AES-128-GCM, AES-256-GCM, ChaCha20Poly1305)");
+  const bool p256 = kem_id == HPKE_KEM_P256_SHA256;
+  if (sk_len != 32 || pk_len != hpke_enc_len(kem_id))
+    return hfail(JX_HPKE_E_INVALID, p256 ? "P-256 keypair: the private key is 32 bytes, the public key 65"
+                                         : "X25519 keypair: the private and the public key are 32 bytes each");
+  HpkeKeyRow key{};
+  if (p256) {  // the same code as the kernels', on the host (jx_p256.h)
+    if (const char* why = hpke_p256_keypair(sk, pk, key.sk, (uint8_t*)key.pk, key.pky)) return hfail(JX_HPKE_E_INVALID, why);
+  } else {
+    uint8_t k[32];
+    memcpy(k, sk, 32);
+    k[0] &= 248;
+    k[31] &= 127;
+    k[31] |= 64;
+    for (int i = 0; i < 8; i++) {
+      memcpy(&key.sk[i], k + 4 * i, 4);
+      memcpy(&key.pk[i], pk + 4 * i, 4);
+    }
+  }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return JX_HPKE_E_NODEVICE;
   if (device < 0 || device >= ndev) return JX_HPKE_E_INVALID;
   jx_hpke* h = new jx_hpke();
   h->device = device;
-  uint8_t k[32];
-  memcpy(k, sk, 32);
-  k[0] &= 248;
-  k[31] &= 127;
-  k[31] |= 64;
-  for (int i = 0; i < 8; i++) {
-    memcpy(&h->cfg.key.sk[i], k + 4 * i, 4);
-    memcpy(&h->cfg.key.pk[i], pk + 4 * i, 4);
-  }
+  h->cfg.key = key;
+  h->kem = kem_id;
   const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   hmac_pads(zero, h->cfg.zero_ist, h->cfg.zero_ost);
   // the key_schedule_context under the key's own suite and hash (jx_hpke_suites.h)
   static_assert(sizeof(h->cfg.key.ksc) >= HPKE_KSC_MAX, "HpkeKeyRow holds the longest key_schedule_context");
-  hpke_key_schedule_context(kdf_id, aead_id, info, info_len, h->cfg.key.ksc);
+  hpke_key_schedule_context(kdf_id, aead_id, info, info_len, h->cfg.key.ksc, kem_id);
   h->cfg.key.kdf = (uint8_t)kdf_id;
   h->cfg.key.aead = (uint8_t)aead_id;
-  h->default_suite = kdf_id == HPKE_KDF_SHA256 && aead_id == HPKE_AEAD_AES128GCM;
+  h->cfg.key.kem = (uint8_t)kem_id;
+  h->default_suite = !p256 && kdf_id == HPKE_KDF_SHA256 && aead_id == HPKE_AEAD_AES128GCM;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
     delete h;
     return JX_HPKE_E_HIP;
@@ -542,11 +632,13 @@ int32_t jx_hpke_create_suite(uint32_t kem_id, uint32_t kdf_id, uint32_t aead_id,
 
 int32_t jx_hpke_suite(const jx_hpke* h, uint32_t* kem_id, uint32_t* kdf_id, uint32_t* aead_id) {
   if (!h) return JX_HPKE_E_INVALID;
-  if (kem_id) *kem_id = HPKE_KEM_X25519_SHA256;
+  if (kem_id) *kem_id = h->kem;
   if (kdf_id) *kdf_id = h->cfg.key.kdf;
   if (aead_id) *aead_id = h->cfg.key.aead;
   return JX_HPKE_OK;
 }
+
+int32_t jx_hpke_enc_len(const jx_hpke* h) { return h ? (int32_t)hpke_enc_len(h->kem) : 0; }
 
 int32_t jx_hpke_stream(const jx_hpke* h, void** out_stream) {
   if (!h || !out_stream) return JX_HPKE_E_INVALID;
@@ -600,7 +692,8 @@ int32_t jx_hpke_open_batch(jx_hpke* h, uint64_t n, const uint8_t* encs, const ui
   std::lock_guard<std::mutex> lk(h->mu);
   HCHK(hipSetDevice(h->device));
   const uint64_t ct_bytes = ct_offsets[n], aad_bytes = aad_offsets[n], pt_bytes = ct_bytes - 16 * n;
-  const size_t o_enc = 0, o_ct = o_enc + jxi::align256(n * 32), o_aad = o_ct + jxi::align256(ct_bytes),
+  const uint64_t enc_bytes = n * hpke_enc_len(h->kem);
+  const size_t o_enc = 0, o_ct = o_enc + jxi::align256(enc_bytes), o_aad = o_ct + jxi::align256(ct_bytes),
                o_pt = o_aad + jxi::align256(aad_bytes ? aad_bytes : 1), o_ok = o_pt + jxi::align256(pt_bytes ? pt_bytes : 1),
                o_co = o_ok + jxi::align256(n), o_ao = o_co + jxi::align256((n + 1) * 8), bytes = o_ao + jxi::align256((n + 1) * 8);
   jxi::Slab slab;
@@ -610,7 +703,7 @@ int32_t jx_hpke_open_batch(jx_hpke* h, uint64_t n, const uint8_t* encs, const ui
   uint8_t* base = (uint8_t*)slab.p;
   int32_t rc = JX_HPKE_OK;
   do {
-    if (hipMemcpyAsync(base + o_enc, encs, n * 32, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+    if (hipMemcpyAsync(base + o_enc, encs, enc_bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         hipMemcpyAsync(base + o_ct, cts, ct_bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
         (aad_bytes && hipMemcpyAsync(base + o_aad, aads, aad_bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) ||
         hipMemcpyAsync(base + o_co, ct_offsets, (n + 1) * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||

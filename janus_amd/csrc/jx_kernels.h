@@ -250,22 +250,29 @@ hipError_t launch_scatter_jobs(const Cfg& c, const JobSlice* d_jobs, uint32_t nj
                                const uint4* outs, const uint8_t* verdicts, const uint8_t* msgs, const uint8_t* nonces,
                                hipStream_t s);
 // ---- HPKE open inside a helper prepare launch (jx_hpke.hip; jx_helper_prep_encrypted_batch)
-// A recipient keypair as the rows kernel reads it: clamped X25519 scalar and public key (LE words) and the
-// RFC 9180 key_schedule_context of its application info (0x00 || psk_id_hash || info_hash: 1 + 2 Nh bytes, 65
-// for HKDF-SHA256, 97 for -SHA384, 129 for -SHA512) under the key's own suite, whose KDF and AEAD ids follow
-// (the KEM is always 0x0020). The default-suite kernels read the first 65 context bytes and no ids.
+// A recipient keypair as the rows kernels read it: the private and public key and the RFC 9180
+// key_schedule_context of its application info (0x00 || psk_id_hash || info_hash: 1 + 2 Nh bytes, 65 for
+// HKDF-SHA256, 97 for -SHA384, 129 for -SHA512) under the key's own suite, whose KDF, AEAD and KEM ids follow (kem:
+// the low byte of the id, 0x20 or 0x10). KEM 0x0020: sk the clamped X25519 scalar, pk the public key, both as LE
+// words. KEM 0x0010 (P-256): sk the LE words of the private integer (sk[0] least significant), pk the 32
+// big-endian bytes of the public point's x and pky those of its y, in memory order. The default-suite kernels
+// read the first 65 context bytes and no ids.
 struct HpkeKeyRow {
   uint32_t sk[8];
   uint32_t pk[8];
   uint8_t ksc[132];
-  uint8_t kdf, aead;
-  uint8_t pad[2];
+  uint8_t kdf, aead, kem;
+  uint8_t pad;
+  uint8_t pky[32];
 };
-static_assert(sizeof(HpkeKeyRow) == 200, "HpkeKeyRow layout");
+static_assert(sizeof(HpkeKeyRow) == 232, "HpkeKeyRow layout");
 enum : uint8_t {
   ENC_ROW_ENCRYPTED = 1,         // the report's helper input share is inside `enc` / the ciphertext (else: uploaded)
   ENC_ROW_REQUIRE_TASKPROV = 2,  // the task is provisioned by taskprov (aggregator.rs:1869-1879)
-  ENC_ROW_MALFORMED = 4,         // the encapsulated key is not 32 bytes: HpkeDecryptError without an open
+  ENC_ROW_MALFORMED = 4,         // the encapsulated key has the length of neither keypair's KEM: HpkeDecryptError
+                                 // without an open
+  ENC_ROW_ENC65 = 8,             // a 65-byte (P-256) encapsulated key, at enc65_off of the launch's ciphertext bytes:
+                                 // hpke_rows_p256_kernel's row, skipped by the X25519 rows kernels
 };
 // One report's encrypted input share: the HpkeCiphertext's encapsulated key and ciphertext (at ct_off of the
 // launch's ciphertext bytes), what its InputShareAad needs besides the id and public share rows, and the
@@ -277,7 +284,7 @@ struct EncRow {
   uint64_t ct_off;
   uint32_t ct_len;
   uint8_t key0, key1, flags, pad;
-  uint8_t pad2[8];
+  uint64_t enc65_off;  // ENC_ROW_ENC65: where the encapsulated key lies (`enc` is zero)
 };
 static_assert(sizeof(EncRow) == 96, "EncRow layout");
 constexpr uint32_t ENC_MAX_KEYS = 16;  // distinct keypairs in one launch's key table

@@ -265,10 +265,11 @@ class HelperEngine:
                                            key_index, encs, payloads: list[bytes], leader_prep_shares,
                                            require_taskprov: bool = False, keep: bool = True) -> "EncryptedResult":
         """The helper's per-report loop from the encrypted report share to helper_initialized + evaluate
-        (aggregator.rs:1763-1967), on the GPU for the whole job (jx_helper_prep_encrypted_batch): report i
+        (aggregator.rs:1763-1967), on the GPU for the whole job (jx_helper_prep_encrypted_batch2): report i
         is opened with keypairs[key_index[i][0]] (then keypairs[key_index[i][1]] if that fails to decrypt;
-        KEY_NONE: none; KEY_MALFORMED: an encapsulated key that is not 32 bytes), its PlaintextInputShare
-        decoded and checked, and prepared. keypairs: janus_amd.hpke.HpkeOpener contexts on this engine's
+        KEY_NONE: none), its PlaintextInputShare decoded and checked, and prepared. encs: an (n, 32) array, or a
+        list of the reports' encapsulated keys of any lengths (32 bytes under X25519, 65 under P-256); a trial of
+        a keypair whose KEM has another length fails without an open. keypairs: janus_amd.hpke.HpkeOpener contexts on this engine's
         device. Returns verdicts (OPEN_FAILURE where the share did not open / decode), prep messages, the
         open status per report (OPEN_STATUS) and the batch handle."""
         n = int(np.asarray(nonces).reshape(-1, 16).shape[0])
@@ -277,7 +278,16 @@ class HelperEngine:
         lps = _u8(leader_prep_shares, n, self.prep_share_len, "leader_prep_shares")
         tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
         ki = np.ascontiguousarray(np.asarray(key_index, dtype=np.uint8).reshape(n, 2)) if n else np.zeros((1, 2), np.uint8)
-        en = _u8(encs, n, 32, "encs") if n else np.zeros((1, 32), np.uint8)
+        if isinstance(encs, (list, tuple)):
+            if len(encs) != n:
+                raise ValueError("one encapsulated key per report")
+            en = np.frombuffer(b"".join(bytes(x) for x in encs) or b"\0", np.uint8).copy()
+            eoff = np.zeros(n + 1, np.uint64)
+            if n:
+                eoff[1:] = np.cumsum([len(x) for x in encs])
+        else:
+            en = _u8(encs, n, 32, "encs") if n else np.zeros((1, 32), np.uint8)
+            eoff = np.arange(n + 1, dtype=np.uint64) * 32
         if len(task_id) != 32 or len(payloads) != n:
             raise ValueError("task id is 32 bytes; one payload per report")
         off = np.zeros(n + 1, np.uint64)
@@ -290,12 +300,13 @@ class HelperEngine:
         status = np.zeros(max(n, 1), np.uint8)
         msgs = np.zeros((max(n, 1), max(self.prep_msg_len, 1)), np.uint8)
         bid = ctypes.c_uint64()
-        st = self._L.jx_helper_prep_encrypted_batch(
+        st = self._L.jx_helper_prep_encrypted_batch2(
             self._h, n, _ptr(nn), tm.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
-            _ptr(ps) if self.public_share_len else None, _ptr(task), hs, len(keypairs), _ptr(ki), _ptr(en), _ptr(ct),
+            _ptr(ps) if self.public_share_len else None, _ptr(task), hs, len(keypairs), _ptr(ki), _ptr(en),
+            eoff.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _ptr(ct),
             off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ENC_REQUIRE_TASKPROV if require_taskprov else 0,
             _ptr(lps), _ptr(msgs) if self.prep_msg_len else None, _ptr(verdicts), _ptr(status), ctypes.byref(bid))
-        check(st, self._h, "jx_helper_prep_encrypted_batch")
+        check(st, self._h, "jx_helper_prep_encrypted_batch2")
         if not keep:
             self.release(bid.value)
             bid.value = 0

@@ -2,13 +2,14 @@
 
 Mirror of janus_core::hpke::open (core/src/hpke.rs:200-230) as the helper calls it once per
 report in its aggregate-init loop (aggregator/src/aggregator.rs:1772-1832): RFC 9180 base
-mode with DHKEM(X25519, HKDF-SHA256) and the KDF and AEAD of the keypair's HpkeConfig (messages/src/
-lib.rs:768-846): HKDF-SHA256 / -SHA384 / -SHA512 with AES-128-GCM / AES-256-GCM / ChaCha20Poly1305, by
-default HKDF-SHA256 / AES-128-GCM. Application info HpkeApplicationInfo::new(&Label::InputShare,
+mode with DHKEM(X25519, HKDF-SHA256) or DHKEM(P-256, HKDF-SHA256) and the KDF and AEAD of the keypair's HpkeConfig
+(messages/src/lib.rs:768-846): HKDF-SHA256 / -SHA384 / -SHA512 with AES-128-GCM / AES-256-GCM /
+ChaCha20Poly1305, by default X25519 / HKDF-SHA256 / AES-128-GCM: the 18 suites the reference opens. Application info HpkeApplicationInfo::new(&Label::InputShare,
 &Role::Client, &Role::Helper) (core/src/hpke.rs:69-84), associated data the encoded InputShareAad
 (messages/src/lib.rs:1854-1858). Here the whole request's ciphertexts are opened in one launch. There
-is no CPU fallback: a suite outside these nine (the P-256 KEM among them) is refused when the opener is
-created (UnsupportedSuite), and such a keypair stays on the host path.
+is no CPU fallback: any other id is refused when the opener is created (UnsupportedSuite). A P-256 keypair is a
+32-byte private key (big-endian) with a 65-byte public key (the uncompressed SEC 1 point); its encapsulated keys
+are 65 bytes.
 """
 from __future__ import annotations
 
@@ -26,11 +27,14 @@ LABEL_AGGREGATE_SHARE = b"dap-09 aggregate share"
 
 # HpkeKemId, HpkeKdfId, HpkeAeadId (messages/src/lib.rs:768-846): the ids the engine opens
 KEM_X25519_HKDF_SHA256 = 0x0020
+KEM_P256_HKDF_SHA256 = 0x0010
 KDF_HKDF_SHA256, KDF_HKDF_SHA384, KDF_HKDF_SHA512 = 0x0001, 0x0002, 0x0003
 AEAD_AES_128_GCM, AEAD_AES_256_GCM, AEAD_CHACHA20_POLY1305 = 0x0001, 0x0002, 0x0003
 E_UNSUPPORTED = -2  # JX_HPKE_E_UNSUPPORTED
+E_INVALID = -1  # JX_HPKE_E_INVALID
 
-EXPORTED_SYMBOLS = ("jx_hpke_create", "jx_hpke_create_suite", "jx_hpke_suite", "jx_hpke_stream", "jx_hpke_destroy",
+EXPORTED_SYMBOLS = ("jx_hpke_create", "jx_hpke_create_suite", "jx_hpke_create_key", "jx_hpke_suite", "jx_hpke_enc_len",
+                    "jx_hpke_stream", "jx_hpke_destroy",
                     "jx_hpke_open_batch", "jx_hpke_open_batch_device", "jx_hpke_last_error")
 
 
@@ -59,6 +63,10 @@ def _declare(L):
     L.jx_hpke_create.argtypes = [vp, vp, vp, u32, i32, ctypes.POINTER(vp)]
     L.jx_hpke_create_suite.restype = i32
     L.jx_hpke_create_suite.argtypes = [u32, u32, u32, vp, vp, vp, u32, i32, ctypes.POINTER(vp)]
+    L.jx_hpke_create_key.restype = i32
+    L.jx_hpke_create_key.argtypes = [u32, u32, u32, vp, u32, vp, u32, vp, u32, i32, ctypes.POINTER(vp)]
+    L.jx_hpke_enc_len.restype = i32
+    L.jx_hpke_enc_len.argtypes = [vp]
     L.jx_hpke_suite.restype = i32
     L.jx_hpke_suite.argtypes = [vp, ctypes.POINTER(u32), ctypes.POINTER(u32), ctypes.POINTER(u32)]
     L.jx_hpke_stream.restype = i32
@@ -84,20 +92,29 @@ class HpkeOpener:
 
     def __init__(self, private_key: bytes, public_key: bytes, info: bytes, device: int = 0,
                  kem_id: int = KEM_X25519_HKDF_SHA256, kdf_id: int = KDF_HKDF_SHA256, aead_id: int = AEAD_AES_128_GCM):
-        if len(private_key) != 32 or len(public_key) != 32:
-            raise ValueError("X25519 keys are 32 bytes")
+        if len(private_key) != 32 or len(public_key) not in (32, 65):
+            raise ValueError("private keys are 32 bytes; public keys 32 (X25519) or 65 (P-256)")
         self._L = _declare(_lib.load())
         h = ctypes.c_void_p()
         sk = np.frombuffer(private_key, np.uint8).copy()
         pk = np.frombuffer(public_key, np.uint8).copy()
         inf = np.frombuffer(info, np.uint8).copy() if info else np.zeros(1, np.uint8)
-        st = self._L.jx_hpke_create_suite(kem_id, kdf_id, aead_id, _p(sk), _p(pk), _p(inf), len(info), device,
-                                          ctypes.byref(h))
+        if len(public_key) == 32:  # the X25519 entry: any other KEM id is refused there
+            call = "jx_hpke_create_suite"
+            st = self._L.jx_hpke_create_suite(kem_id, kdf_id, aead_id, _p(sk), _p(pk), _p(inf), len(info), device,
+                                              ctypes.byref(h))
+        else:
+            call = "jx_hpke_create_key"
+            st = self._L.jx_hpke_create_key(kem_id, kdf_id, aead_id, _p(sk), len(sk), _p(pk), len(pk), _p(inf), len(info),
+                                            device, ctypes.byref(h))
         if st == E_UNSUPPORTED:
             raise UnsupportedSuite(self._L.jx_hpke_last_error(None).decode())
+        if st == E_INVALID:
+            raise ValueError(f"{call}: {self._L.jx_hpke_last_error(None).decode() or 'invalid argument'}")
         if st != 0:
-            raise EngineError(f"jx_hpke_create_suite: status {st}")
+            raise EngineError(f"{call}: status {st}")
         self._h = h
+        self._enc_len = int(self._L.jx_hpke_enc_len(h))
         kem, kdf, aead = ctypes.c_uint32(), ctypes.c_uint32(), ctypes.c_uint32()
         self._L.jx_hpke_suite(h, ctypes.byref(kem), ctypes.byref(kdf), ctypes.byref(aead))
         self._suite = (kem.value, kdf.value, aead.value)
@@ -106,6 +123,11 @@ class HpkeOpener:
     def suite(self) -> tuple[int, int, int]:
         """(kem_id, kdf_id, aead_id) of the context, as jx_hpke_suite reports it."""
         return self._suite
+
+    @property
+    def enc_len(self) -> int:
+        """The length of an encapsulated key under the context's KEM (jx_hpke_enc_len): 32 or 65."""
+        return self._enc_len
 
     @property
     def handle(self):
@@ -146,8 +168,8 @@ class HpkeOpener:
         if n == 0:
             return []
         # a malformed share fails alone (HpkeDecryptError for that report, aggregator.rs:1772-1831):
-        # a wrong-length encapsulated key or a ciphertext shorter than the GCM tag never reaches the GPU
-        idx = [i for i in range(n) if len(encs[i]) == 32 and len(ciphertexts[i]) >= 16]
+        # an encapsulated key of another length than the KEM's or a ciphertext shorter than the tag never reaches the GPU
+        idx = [i for i in range(n) if len(encs[i]) == self._enc_len and len(ciphertexts[i]) >= 16]
         out: list[bytes | None] = [None] * n
         if not idx:
             return out
