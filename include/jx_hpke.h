@@ -16,6 +16,21 @@
  * context); jx_hpke_last_error returns the calling thread's last failure. The host-buffer open takes its
  * device buffers from the device's arena (shared with the prepare engines) and synchronizes only the
  * context's stream. jx_helper_prep_encrypted_batch (jx_prio3.h) opens inside the prepare launch instead.
+ *
+ * The key registry. Every device has one registry of keypairs: a fixed array of JX_HPKE_MAX_CONTEXTS (16,384) rows
+ * of device memory (3.8 MB, allocated at the first context creation on the device, outside the arena, and never
+ * moved or reallocated). Creating a context takes a free row and writes the keypair into it, synchronously, before
+ * the call returns; jx_hpke_destroy wipes the row and frees it for the next context. So a row's lifetime is its
+ * context's lifetime, and the prepare launches of jx_helper_prep_encrypted_batch[2] read the keys from there: a
+ * launch carries no key table, and jobs of any number of tasks, each with its own keypair, share one launch. A
+ * context passed to a call is borrowed for the duration of that call, as everywhere in this ABI: destroy it only
+ * when no call that was given it is still running. With JX_HPKE_MAX_CONTEXTS contexts alive on a device the next
+ * creation returns JX_HPKE_E_NOMEM, with the reason in jx_hpke_last_error. A context costs its registry row and a
+ * few hundred bytes of host memory; its stream is created at its first jx_hpke_open_batch[_device] or
+ * jx_hpke_stream, so a context that is only ever passed to a prepare call never has one.
+ *
+ * No branch and no address of the X25519 ladder or of the P-256 scalar multiplication depends on the private key
+ * (masked selects).
  *  - encs:        n x jx_hpke_enc_len(h) bytes (HpkeCiphertext.encapsulated_key: 32 under X25519, 65 under
  *                 P-256, the uncompressed SEC 1 point)
  *  - cts:         ciphertexts (payload || 16-byte tag) back to back; ct_offsets[n + 1], ciphertext i
@@ -38,8 +53,10 @@ extern "C" {
 #define JX_HPKE_E_INVALID (-1)
 #define JX_HPKE_E_UNSUPPORTED (-2) /* a KEM, KDF or AEAD id outside the suites below */
 #define JX_HPKE_E_HIP (-3)
-#define JX_HPKE_E_NOMEM (-4)
+#define JX_HPKE_E_NOMEM (-4) /* device memory, or JX_HPKE_MAX_CONTEXTS contexts alive on the device */
 #define JX_HPKE_E_NODEVICE (-6)
+
+#define JX_HPKE_MAX_CONTEXTS 16384 /* live contexts per device: the rows of its key registry */
 
 typedef struct jx_hpke jx_hpke;
 
@@ -80,7 +97,7 @@ int32_t jx_hpke_open_batch_device(jx_hpke* h, uint64_t n, const void* d_encs, co
                                   const uint64_t* d_ct_offsets, const void* d_aads, const uint64_t* d_aad_offsets,
                                   void* d_out_plaintexts, void* d_out_ok);
 /* The context's stream (a hipStream_t), on which jx_hpke_open_batch_device enqueues: for events around an open,
- * or to order other work after it. */
+ * or to order other work after it. Created by the first call that needs it (this one included). */
 int32_t jx_hpke_stream(const jx_hpke* h, void** out_stream);
 const char* jx_hpke_last_error(const jx_hpke* h);
 

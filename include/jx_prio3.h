@@ -228,7 +228,11 @@ int32_t jx_helper_prep_batch(jx_engine* e, uint64_t n, const uint8_t* nonces, co
  *   times[n]            ReportMetadata.time (seconds); InputShareAad = task_id || id || time || public share
  *   task_id             32 bytes
  *   keypairs            nkeypairs (<= JX_ENC_MAX_KEYPAIRS) HPKE contexts on the engine's device, created with
- *                       the input-share application info (Label::InputShare, Client -> Helper)
+ *                       the input-share application info (Label::InputShare, Client -> Helper). Borrowed for the
+ *                       call. Their keys are in the device's key registry since they were created (jx_hpke.h):
+ *                       the request carries no key material, and the limit is per request only. Coalesced jobs of
+ *                       any number of tasks, each with keypairs of its own, share one launch (up to
+ *                       JX_HPKE_MAX_CONTEXTS keypairs alive on the device)
  *   key_index[n x 2]    per report: first keypair, fallback keypair (JX_KEY_NONE / JX_KEY_MALFORMED above)
  *   encs[n x 32]        HpkeCiphertext.encapsulated_key (X25519; a P-256 keypair here is a failed trial: see
  *                       jx_helper_prep_encrypted_batch2)

@@ -61,7 +61,6 @@ struct CReq {
   uint64_t n = 0, first = 0, id = 0;
   const EncJob* enc = nullptr;  // encrypted helper inputs
   uint64_t ct_first = 0, ct_bytes = 0;
-  uint8_t key_map[JX_ENC_MAX_KEYPAIRS] = {0};
   JobSlice dst{};
   hipEvent_t batch_ev = nullptr;  // the batch slab's last user (the lane waits on it)
   uint8_t* out_msgs = nullptr;
@@ -99,14 +98,14 @@ struct Lane {
   bool enc = false;       // the layout holds the encrypted-input regions
   bool has_enc = false;   // a job of this gather is encrypted
   bool has_enc65 = false; // ... and holds a row with a 65-byte (P-256) encapsulated key
+  bool has_suites = false;  // ... and a job of it holds a keypair outside the default suite
   uint64_t reports = 0, cap_reports = 0, ct_bytes = 0, ct_cap = 0;
   uint32_t copying = 0;
   std::atomic<uint32_t> unconsumed{0};  // callers still to copy their results out (the last one frees the lane)
   std::vector<CReq*> reqs;
-  std::vector<const jx_hpke*> keys;  // the launch's key table
   clk::time_point opened, launched, last_arrival;
   // region offsets in h_in (rows of cap_reports)
-  size_t o_non = 0, o_ps = 0, o_his = 0, o_lps = 0, o_lis = 0, o_vk = 0, o_jobs = 0, o_enc = 0, o_ct = 0, o_keys = 0;
+  size_t o_non = 0, o_ps = 0, o_his = 0, o_lps = 0, o_lis = 0, o_vk = 0, o_jobs = 0, o_enc = 0, o_ct = 0;
   // region offsets in h_out
   size_t r_ver = 0, r_msg = 0, r_lps = 0, r_st = 0;
 };
@@ -293,7 +292,6 @@ static int32_t lane_layout(Coalescer* C, Lane& L, int role, uint64_t n, uint64_t
     if (ct_cap < ct) ct_cap = ct;
     take(L.o_enc, cap * sizeof(EncRow));
     take(L.o_ct, ct_cap);
-    take(L.o_keys, ENC_MAX_KEYS * sizeof(HpkeKeyRow));
   }
   const size_t in_bytes = off;
   off = 0;
@@ -395,7 +393,6 @@ static int32_t launch_lane(Coalescer* C, Lane& L, std::string& err) {
   if (L.has_enc) {
     flat(ua, q->d_encrows, L.o_enc, m * sizeof(EncRow));
     flat(ua, q->d_ct, L.o_ct, L.ct_bytes);
-    flat(ua, q->d_keys, L.o_keys, L.keys.size() * sizeof(HpkeKeyRow));
   }
   JobSlice* h_jobs = reinterpret_cast<JobSlice*>(L.h_in + L.o_jobs);
   uint64_t max_job = 0;
@@ -426,14 +423,14 @@ static int32_t launch_lane(Coalescer* C, Lane& L, std::string& err) {
   }
   if (s != hipSuccess) return bad(s, "upload");
   if (L.has_enc) {  // open the encrypted reports into their helper input-share rows
-    HpkeRowsArgs ha{m, q->d_encrows, q->d_ct, q->d_pt, q->d_keys, (uint32_t)L.keys.size(), q->d_nonces, q->d_ps,
+    // the rows name their keypairs by their slots of the device's key registry: any number of keypairs, no upload
+    const HpkeKeyRow* reg = nullptr;
+    uint32_t reg_cap = 0;
+    hpke_registry(C->device, &reg, &reg_cap);
+    HpkeRowsArgs ha{m, q->d_encrows, q->d_ct, q->d_pt, reg, reg ? reg_cap : 0, q->d_nonces, q->d_ps,
                     c.ps_bytes, q->d_his, c.his_bytes, q->d_status};
     // jobs of any suites share a launch; one key outside the default suite sends all its rows to the suite kernel
-    const HpkeKeyRow* key_rows = reinterpret_cast<const HpkeKeyRow*>(L.h_in + L.o_keys);
-    bool suites = false;
-    for (size_t k = 0; k < L.keys.size(); k++)
-      suites = suites || key_rows[k].kdf != 1 || key_rows[k].aead != 1 || key_rows[k].kem != 0x20;
-    s = launch_hpke_rows(ha, suites, L.has_enc65, q->stream);
+    s = launch_hpke_rows(ha, L.has_suites, L.has_enc65, q->stream);
     if (s != hipSuccess) return bad(s, "hpke open");
   }
   rc = prep_core(q, m, q->d_nonces, q->d_ps, q->d_his, q->d_lps, q->d_verdicts, q->d_msgs, staging_outs(q),
@@ -809,27 +806,15 @@ void coalescer_stats(const jx_engine* e, uint64_t out[16]) {
   out[14] = C->enc_jobs;
 }
 
-// Whether r joins the gathering lane L (with C->mu held); if so, its rows (and ciphertext bytes and keypairs)
-// are reserved.
+// Whether r joins the gathering lane L (with C->mu held); if so, its rows (and ciphertext bytes) are reserved. A
+// job's keypairs never keep it out: they live in the device's key registry, not in the launch.
 static bool try_join(Coalescer* C, Lane& L, CReq* r) {
   (void)C;
   if (L.reports + r->n > L.cap_reports || L.reqs.size() >= MAX_JOBS_PER_LAUNCH) return false;
   if (r->enc) {
     if (!L.enc || L.ct_bytes + r->ct_bytes > L.ct_cap) return false;
-    size_t add = 0;
     for (uint32_t k = 0; k < r->enc->nkeys; k++)
-      if (std::find(L.keys.begin(), L.keys.end(), r->enc->keypairs[k]) == L.keys.end()) add++;
-    if (L.keys.size() + add > ENC_MAX_KEYS) return false;
-    for (uint32_t k = 0; k < r->enc->nkeys; k++) {
-      const jx_hpke* h = r->enc->keypairs[k];
-      auto it = std::find(L.keys.begin(), L.keys.end(), h);
-      if (it == L.keys.end()) {
-        hpke_key_row(h, reinterpret_cast<HpkeKeyRow*>(L.h_in + L.o_keys) + L.keys.size());
-        L.keys.push_back(h);
-        it = L.keys.end() - 1;
-      }
-      r->key_map[k] = (uint8_t)(it - L.keys.begin());
-    }
+      if (!hpke_default_suite(r->enc->keypairs[k])) L.has_suites = true;
     r->ct_first = L.ct_bytes;
     L.ct_bytes += r->ct_bytes;
     L.has_enc = true;
@@ -875,9 +860,9 @@ static Lane* reserve(Coalescer* C, std::unique_lock<std::mutex>& lk, CReq* r, in
         L.all_back = false;
         L.has_enc = false;
         L.has_enc65 = false;
+        L.has_suites = false;
         L.reports = 0;
         L.ct_bytes = 0;
-        L.keys.clear();
         L.reqs.clear();
         L.copying = 0;
         L.opened = L.last_arrival = clk::now();
@@ -891,12 +876,15 @@ static Lane* reserve(Coalescer* C, std::unique_lock<std::mutex>& lk, CReq* r, in
 }
 
 // Lay out one job's EncRows (its ciphertexts at ct_base + their offset within the job).
-uint64_t fill_enc_rows(const EncJob& j, uint64_t n, EncRow* rows, uint64_t ct_base, const uint8_t* key_map,
-                       uint8_t* enc65) {
+uint64_t fill_enc_rows(const EncJob& j, uint64_t n, EncRow* rows, uint64_t ct_base, uint8_t* enc65) {
   const uint64_t c0 = j.payload_offsets[0], enc65_base = ct_base + j.payload_bytes(n);
   uint64_t n65 = 0;
   uint32_t klen[JX_ENC_MAX_KEYPAIRS];
-  for (uint32_t k = 0; k < j.nkeys; k++) klen[k] = hpke_enc_len(j.keypairs[k]);
+  uint16_t slot[JX_ENC_MAX_KEYPAIRS];  // the request's keypair index -> its slot of the device's key registry
+  for (uint32_t k = 0; k < j.nkeys; k++) {
+    klen[k] = hpke_enc_len(j.keypairs[k]);
+    slot[k] = hpke_slot(j.keypairs[k]);
+  }
   for (uint64_t i = 0; i < n; i++) {
     EncRow& w = rows[i];
     memset(&w, 0, sizeof w);
@@ -921,8 +909,8 @@ uint64_t fill_enc_rows(const EncJob& j, uint64_t n, EncRow* rows, uint64_t ct_ba
     } else if (len == 32) {
       memcpy(w.enc, j.enc(i), 32);
     }
-    w.key0 = k0 < j.nkeys ? key_map[k0] : (k0 == JX_KEY_MALFORMED ? (uint8_t)0 : (uint8_t)JX_KEY_NONE);
-    w.key1 = k1 < j.nkeys ? key_map[k1] : (uint8_t)JX_KEY_NONE;
+    w.key0 = k0 < j.nkeys ? slot[k0] : (k0 == JX_KEY_MALFORMED ? (uint16_t)0 : KEY_SLOT_NONE);
+    w.key1 = k1 < j.nkeys ? slot[k1] : KEY_SLOT_NONE;
   }
   return n65;
 }
@@ -986,7 +974,7 @@ static int32_t coalesced(jx_engine* e, bool leader, uint64_t n, const uint8_t* n
     EncRow* rows = L->enc ? reinterpret_cast<EncRow*>(L->h_in + L->o_enc) + f : nullptr;
     if (enc) {
       const uint64_t pb = enc->payload_bytes(n);
-      n65 = fill_enc_rows(*enc, n, rows, r.ct_first, r.key_map, L->h_in + L->o_ct + r.ct_first + pb);
+      n65 = fill_enc_rows(*enc, n, rows, r.ct_first, L->h_in + L->o_ct + r.ct_first + pb);
       memcpy(L->h_in + L->o_ct + r.ct_first, enc->payloads + enc->payload_offsets[0], pb);
     } else if (rows) {
       memset(rows, 0, n * sizeof(EncRow));  // plain reports: the open kernel leaves their rows alone

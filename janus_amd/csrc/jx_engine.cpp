@@ -426,7 +426,6 @@ static size_t stage_layout(jx_engine* e, uint64_t cap, uint32_t fl, uint8_t* bas
     take(e->d_encrows, cap * sizeof(EncRow));
     take(e->d_ct, e->enc_ct_bytes);
     take(e->d_pt, e->enc_ct_bytes);
-    take(e->d_keys, (size_t)ENC_MAX_KEYS * sizeof(HpkeKeyRow));
     take(e->d_status, cap);
   }
   return off;
@@ -446,7 +445,6 @@ static void stage_clear(jx_engine* e) {
   e->d_jobs = nullptr;
   e->d_encrows = nullptr;
   e->d_ct = e->d_pt = e->d_status = nullptr;
-  e->d_keys = nullptr;
   e->cap = 0;
   e->stage_flags = 0;
 }
@@ -1407,19 +1405,17 @@ int32_t jx_helper_prep_encrypted_batch2(jx_engine* e, uint64_t n, const uint8_t*
   if (rc) return rc;
   if (n) {
     auto run = [&]() -> int32_t {
-      // the job's rows in pageable host memory, uploaded with its inputs; the key table is the job's keypairs
+      // the job's rows in pageable host memory, uploaded with its inputs; they name their keypairs by their slots
+      // of the device's key registry, where the keys have been since the contexts were created
       std::vector<EncRow> rows(n);
-      uint8_t key_map[JX_ENC_MAX_KEYPAIRS];
-      std::vector<HpkeKeyRow> keys(nkeypairs ? nkeypairs : 1);
       bool suites = false;
-      for (uint32_t k = 0; k < nkeypairs; k++) {
-        key_map[k] = (uint8_t)k;
-        hpke_key_row(keypairs[k], &keys[k]);
-        suites = suites || !hpke_default_suite(keypairs[k]);
-      }
+      for (uint32_t k = 0; k < nkeypairs; k++) suites = suites || !hpke_default_suite(keypairs[k]);
+      const HpkeKeyRow* reg = nullptr;
+      uint32_t reg_cap = 0;
+      hpke_registry(e->device, &reg, &reg_cap);
       // the 65-byte encapsulated keys follow the ciphertexts in the launch's ciphertext region
       std::vector<uint8_t> enc65(job.enc65 ? 65 * job.enc65 : 1);
-      const uint64_t pb = job.payload_bytes(n), n65 = fill_enc_rows(job, n, rows.data(), 0, key_map, enc65.data());
+      const uint64_t pb = job.payload_bytes(n), n65 = fill_enc_rows(job, n, rows.data(), 0, enc65.data());
       e->enc_ct_bytes = ct ? ct : 1;
       Stage st;
       int32_t r = stage_acquire(e, n, SG_IN | SG_HIN | SG_ENC | helper_meas_flag(c) | SG_PREP, st);
@@ -1430,9 +1426,7 @@ int32_t jx_helper_prep_encrypted_batch2(jx_engine* e, uint64_t n, const uint8_t*
       HIPCHK(e, hipMemcpyAsync(e->d_encrows, rows.data(), n * sizeof(EncRow), hipMemcpyHostToDevice, e->stream));
       if (pb) HIPCHK(e, hipMemcpyAsync(e->d_ct, payloads + payload_offsets[0], pb, hipMemcpyHostToDevice, e->stream));
       if (n65) HIPCHK(e, hipMemcpyAsync(e->d_ct + pb, enc65.data(), 65 * n65, hipMemcpyHostToDevice, e->stream));
-      if (nkeypairs)
-        HIPCHK(e, hipMemcpyAsync(e->d_keys, keys.data(), nkeypairs * sizeof(HpkeKeyRow), hipMemcpyHostToDevice, e->stream));
-      HpkeRowsArgs ha{n, e->d_encrows, e->d_ct, e->d_pt, e->d_keys, nkeypairs, B->nonces, e->d_ps, c.ps_bytes,
+      HpkeRowsArgs ha{n, e->d_encrows, e->d_ct, e->d_pt, reg, reg ? reg_cap : 0, B->nonces, e->d_ps, c.ps_bytes,
                       e->d_his, c.his_bytes, e->d_status};
       HIPCHK(e, launch_hpke_rows(ha, suites, n65 != 0, e->stream));
       r = prep_core(e, n, B->nonces, e->d_ps, e->d_his, e->d_lps, B->verdicts, B->msgs, B->outs);

@@ -124,8 +124,7 @@ enum : uint32_t {
   SG_LMSG = 64,  // host-path leader finish: inbound prep messages
   SG_VK = 128,   // coalesced launches: one verify key per report (16 B; multiproof: HMAC pads, 64 B)
   SG_JOBS = 512, // coalesced launches: the job table (MAX_JOBS_PER_LAUNCH slices)
-  SG_ENC = 1024, // encrypted helper inputs: EncRows, ciphertext + plaintext bytes (enc_ct_bytes each), key table,
-                 // open status
+  SG_ENC = 1024, // encrypted helper inputs: EncRows, ciphertext + plaintext bytes (enc_ct_bytes each), open status
 };
 
 // One job's encrypted input shares (jx_helper_prep_encrypted_batch), as the caller passed them.
@@ -147,19 +146,22 @@ struct EncJob {
   uint64_t enc_len(uint64_t i) const { return enc_offsets ? enc_offsets[i + 1] - enc_offsets[i] : 32; }
   const uint8_t* enc(uint64_t i) const { return encs + (enc_offsets ? enc_offsets[i] : 32 * i); }
 };
-// The job's EncRows, ciphertexts at ct_base + their offset within the job; key_map: the job's keypair
-// index -> the launch's key-table row. The one place that copies encapsulated keys: a 32-byte one into its row, a
+// The job's EncRows, ciphertexts at ct_base + their offset within the job; the request's keypair indices become
+// the keypairs' slots of the device's key registry (hpke_slot). The one place that copies encapsulated keys: a 32-byte one into its row, a
 // 65-byte one that a P-256 keypair of the row can try to enc65 (the host copy of the launch's ciphertext region
 // at ct_base + the job's payload bytes; ENC_ROW_ENC65). A key whose length fits neither keypair's KEM marks the
 // row malformed. Returns the number of ENC_ROW_ENC65 rows.
-uint64_t fill_enc_rows(const EncJob& j, uint64_t n, jx::EncRow* rows, uint64_t ct_base, const uint8_t* key_map,
-                       uint8_t* enc65);
+uint64_t fill_enc_rows(const EncJob& j, uint64_t n, jx::EncRow* rows, uint64_t ct_base, uint8_t* enc65);
 // jx_hpke.hip
 int hpke_device(const jx_hpke* h);
-void hpke_key_row(const jx_hpke* h, jx::HpkeKeyRow* out);
+// The context's slot of its device's key registry (jx_keyreg.h), its own from creation to jx_hpke_destroy, and the
+// registry itself: the device array the rows kernels index (HpkeRowsArgs::keys / nkeys). The array never moves;
+// rows is null until the first context of the device exists.
+uint16_t hpke_slot(const jx_hpke* h);
+void hpke_registry(int device, const jx::HpkeKeyRow** rows, uint32_t* capacity);
 bool hpke_default_suite(const jx_hpke* h);  // X25519 with (HKDF-SHA256, AES-128-GCM)
 uint32_t hpke_enc_len(const jx_hpke* h);    // the length of its KEM's encapsulated keys: 32 or 65
-// suites: the launch's key table holds a key of another suite than the default (every 32-byte row then goes through
+// suites: a job of the launch holds a key of another suite than the default (every 32-byte row then goes through
 // hpke_rows_suite_kernel); p256_rows: the launch holds an ENC_ROW_ENC65 row (hpke_rows_p256_kernel runs too)
 hipError_t launch_hpke_rows(const jx::HpkeRowsArgs& a, bool suites, bool p256_rows, hipStream_t s);
 hipError_t launch_open_mask(const uint8_t* status, uint8_t* verdicts, uint64_t n, hipStream_t s);
@@ -237,7 +239,6 @@ struct jx_engine {
   // SG_ENC: encrypted helper inputs (enc_ct_bytes: the ciphertext region's size, set before stage_acquire)
   jx::EncRow* d_encrows = nullptr;
   uint8_t *d_ct = nullptr, *d_pt = nullptr, *d_status = nullptr;
-  jx::HpkeKeyRow* d_keys = nullptr;
   uint64_t enc_ct_bytes = 0;
   uint32_t acc_chunks = 0;  // report chunks of the accumulate kernel (0: acc_nchunks picks)
   std::map<uint32_t, jxi::Segment> segs;  // running batch aggregations (the engine as one shard)

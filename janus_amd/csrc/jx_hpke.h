@@ -5,8 +5,9 @@
 //
 //  * X25519 (RFC 7748): field 2^255 - 19 in ten 26-bit limbs (loosely reduced, < 2^28),
 //    products accumulated in 64-bit columns by v_mad_u64_u32 with no carries, reduced once per
-//    multiplication (2^260 == 608 mod p). The recipient scalar is the same for every lane, so
-//    the ladder's conditional swaps are wave-uniform branches.
+//    multiplication (2^260 == 608 mod p). The lanes of a wave hold different recipient scalars (a prepare
+//    launch opens under any number of keypairs), so the ladder's conditional swaps are masked selects over the
+//    limbs: no branch and no address in the ladder depends on the scalar.
 //  * SHA-256 / HMAC / HKDF over messages whose layout is fixed at compile time (every byte
 //    position is a constant after unrolling, so message buffers live in registers).
 //  * SHA-256 / HMAC and AES-128 come from jx_sha_aes.h; GHASH is bit-serial.
@@ -189,7 +190,18 @@ JX_HD void fe_to_bytes(uint32_t w[8], const fe& a) {
   if (wi < 8) w[wi] = (uint32_t)acc;
 }
 
-// X25519(k, u) with a wave-uniform clamped scalar k (8 LE words, bit 254 set, bits 0..2 clear)
+// a, b = b, a where m is all ones; unchanged where m is zero (each a bitfield select of the mask)
+JX_HD void fe_cswap(fe& a, fe& b, uint32_t m) {
+#pragma unroll
+  for (int i = 0; i < 10; i++) {
+    const uint32_t x = a.v[i], y = b.v[i];
+    a.v[i] = (y & m) | (x & ~m);
+    b.v[i] = (x & m) | (y & ~m);
+  }
+}
+
+// X25519(k, u) with a clamped scalar k (8 LE words, bit 254 set, bits 0..2 clear). The same instructions and
+// addresses for every k: the bit positions are the loop counter's, and the swaps are masked selects.
 JX_HD void x25519_ladder(uint32_t out[8], const uint32_t k[8], const uint32_t u[8]) {
   fe x1, x2, z2, x3, z3, A, AA, B, BB, E, C, D, DA, CB, t;
   fe_from_bytes(x1, u);
@@ -203,14 +215,9 @@ JX_HD void x25519_ladder(uint32_t out[8], const uint32_t k[8], const uint32_t u[
   uint32_t swap = 0;
   for (int pos = 254; pos >= 0; pos--) {
     const uint32_t kt = (k[pos >> 5] >> (pos & 31)) & 1u;
-    if (swap ^ kt) {  // uniform: the scalar is the same in every lane
-      fe s = x2;
-      x2 = x3;
-      x3 = s;
-      s = z2;
-      z2 = z3;
-      z3 = s;
-    }
+    const uint32_t m = 0u - (swap ^ kt);
+    fe_cswap(x2, x3, m);
+    fe_cswap(z2, z3, m);
     swap = kt;
     fe_add(A, x2, z2);
     fe_sq(AA, A);
@@ -231,10 +238,9 @@ JX_HD void x25519_ladder(uint32_t out[8], const uint32_t k[8], const uint32_t u[
     fe_add(t, AA, t);
     fe_mul(z2, E, t);
   }
-  if (swap) {
-    x2 = x3;
-    z2 = z3;
-  }
+  const uint32_t m = 0u - swap;
+  fe_cswap(x2, x3, m);
+  fe_cswap(z2, z3, m);
   fe_invert(t, z2);
   fe_mul(x2, x2, t);
   fe_to_bytes(out, x2);

@@ -8,7 +8,7 @@
 // The other eight X25519 suites an HpkeConfig can name (HKDF-SHA256 / -SHA384 / -SHA512 with AES-128-GCM /
 // AES-256-GCM / ChaCha20Poly1305; jx_hpke_suites.h) go through a second pair of kernels, hpke_open_suite_kernel
 // and hpke_rows_suite_kernel, which read the suite from the key row and dispatch per lane. They are launched only
-// for a context, or a launch's key table, that holds a key outside the default suite (then for every row of the
+// for a context, or a launch with a job, that holds a key outside the default suite (then for every row of the
 // launch), so the default suite's kernels and their register budget are what they were.
 // The second KEM the reference opens under, DHKEM(P-256, HKDF-SHA256) (0x0010; jx_p256.h), has a third pair,
 // hpke_open_p256_kernel and hpke_rows_p256_kernel: its encapsulated keys are 65 bytes, so the rows of a prepare
@@ -26,12 +26,14 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
+#include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/jx_hpke.h"
 #include "jx_engine_internal.h"
 #include "jx_hpke_suites.h"
+#include "jx_keyreg.h"
 
 using namespace jx;
 
@@ -330,12 +332,13 @@ __device__ uint8_t aad_byte(const EncRow& e, const uint8_t* nonce, const uint8_t
   return i - 60 < ps_bytes ? ps[i - 60] : 0;
 }
 
-// The open inside a prepare launch. SUITE false: every key of the launch's table is of the default suite; true: each
+// The open inside a prepare launch. Keys come from the device's key registry (a.keys, jx_keyreg.h): a row names the
+// slots of its two trials. SUITE false: every key of the launch's jobs is of the default suite; true: each
 // key's own suite (lanes of one wave may hold different ones). What follows the open is the same code.
 // (ra by value: by reference the kernel's argument costs hpke_rows_kernel four more spilled registers.)
 // P256: the rows whose encapsulated key is 65 bytes (ENC_ROW_ENC65), which the other two skip; a trial with a key
-// of the other KEM fails without an open, as the hpke crate's deserialisation of the encapsulated key does. A
-// table of default-suite keys alone never comes with such a row (fill_enc_rows), so that body knows neither.
+// of the other KEM fails without an open, as the hpke crate's deserialisation of the encapsulated key does. Jobs
+// of default-suite keys alone never come with such a row (fill_enc_rows), so that body knows neither.
 template <bool SUITE, bool P256 = false>
 __device__ __forceinline__ void rows_body(const uint8_t* sbox, const RowsArgs ra) {
   const HpkeRowsArgs& a = ra.a;
@@ -359,7 +362,7 @@ __device__ __forceinline__ void rows_body(const uint8_t* sbox, const RowsArgs ra
   const uint8_t* ct = a.cts + c0;
   uint8_t* pt = a.pts + c0;
   const uint64_t clen = clen_all >= 16 ? clen_all - 16 : 0;
-  if (e.key0 == JX_KEY_NONE) {
+  if (e.key0 == KEY_SLOT_NONE) {
     st = JX_OPEN_UNKNOWN_CONFIG;  // neither the task nor the global keys hold the config id
   } else if ((e.flags & ENC_ROW_MALFORMED) || clen_all < 16) {
     st = JX_OPEN_HPKE_DECRYPT_ERROR;  // an encapsulated key that fits neither keypair's KEM, a ciphertext without a tag
@@ -489,7 +492,8 @@ struct jx_hpke {
   bool default_suite = true;  // X25519 with (HKDF-SHA256, AES-128-GCM): opened by hpke_open_kernel / hpke_rows_kernel
   uint32_t kem = HPKE_KEM_X25519_SHA256;
   int device = 0;
-  hipStream_t stream = nullptr;
+  uint32_t slot = 0;            // the context's row of the device's key registry, for as long as it lives
+  hipStream_t stream = nullptr;  // created at the first standalone open or jx_hpke_stream (ensure_stream)
   jxi::Arena* arena = nullptr;  // the device's arena: the host-buffer open's device buffers
   std::mutex mu;                // one call at a time per handle (its stream and staging)
 };
@@ -506,6 +510,73 @@ static int32_t hfail(int32_t code, const std::string& m) {
     hipError_t _st = (call);                                                                         \
     if (_st != hipSuccess) return hfail(JX_HPKE_E_HIP, std::string(#call) + ": " + hipGetErrorString(_st)); \
   } while (0)
+
+// The device's key registry: KEY_SLOTS rows of device memory of its own (not the arena's: a launch in flight must
+// never see the table move), allocated at the first context creation on the device and kept for the life of the
+// process; one stream for the rows' uploads.
+namespace {
+struct KeyRegistry {
+  std::mutex mu;
+  HpkeKeyRow* d_rows = nullptr;
+  hipStream_t stream = nullptr;
+  KeySlots slots;
+};
+std::mutex g_reg_mu;
+std::vector<KeyRegistry*> g_regs;  // by device
+
+KeyRegistry* registry_for(int device) {
+  std::lock_guard<std::mutex> lk(g_reg_mu);
+  if ((size_t)device >= g_regs.size()) g_regs.resize(device + 1, nullptr);
+  if (!g_regs[device]) g_regs[device] = new KeyRegistry();
+  return g_regs[device];
+}
+
+// Take a slot and write the row, synchronously: the row is on the device when this returns.
+int32_t registry_add(int device, const HpkeKeyRow& row, uint32_t* slot) {
+  KeyRegistry* R = registry_for(device);
+  std::lock_guard<std::mutex> lk(R->mu);
+  HCHK(hipSetDevice(device));
+  if (!R->d_rows) {
+    HpkeKeyRow* p = nullptr;
+    const hipError_t st = hipMalloc((void**)&p, (size_t)KEY_SLOTS * sizeof(HpkeKeyRow));
+    if (st == hipErrorOutOfMemory) return hfail(JX_HPKE_E_NOMEM, "device allocation failed (HPKE key registry)");
+    HCHK(st);
+    if (!R->stream) HCHK(hipStreamCreateWithFlags(&R->stream, hipStreamNonBlocking));
+    R->d_rows = p;
+  }
+  const int32_t s = R->slots.take();
+  if (s < 0)
+    return hfail(JX_HPKE_E_NOMEM, "the device's HPKE key registry is full: " + std::to_string(KEY_SLOTS) +
+                                      " live contexts (jx_hpke_destroy frees a slot)");
+  hipError_t st = hipMemcpyAsync(R->d_rows + s, &row, sizeof row, hipMemcpyHostToDevice, R->stream);
+  if (st == hipSuccess) st = hipStreamSynchronize(R->stream);
+  if (st != hipSuccess) {
+    R->slots.free((uint32_t)s);
+    return hfail(JX_HPKE_E_HIP, std::string("HPKE key registry upload: ") + hipGetErrorString(st));
+  }
+  *slot = (uint32_t)s;
+  return JX_HPKE_OK;
+}
+
+// Wipe the row (it held a private key) and free the slot for the next context.
+void registry_remove(int device, uint32_t slot) {
+  KeyRegistry* R = registry_for(device);
+  std::lock_guard<std::mutex> lk(R->mu);
+  const HpkeKeyRow zero{};
+  if (hipSetDevice(device) == hipSuccess &&
+      hipMemcpyAsync(R->d_rows + slot, &zero, sizeof zero, hipMemcpyHostToDevice, R->stream) == hipSuccess)
+    (void)hipStreamSynchronize(R->stream);
+  R->slots.free(slot);
+}
+
+// with h->mu held
+int32_t ensure_stream(jx_hpke* h) {
+  if (h->stream) return JX_HPKE_OK;
+  HCHK(hipSetDevice(h->device));
+  HCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  return JX_HPKE_OK;
+}
+}  // namespace
 
 // the default suite keeps its own kernel; any other goes through the suite kernel of its KEM
 static void launch_open(const jx_hpke* h, const HpkeBufs& b) {
@@ -527,7 +598,13 @@ static void launch_open(const jx_hpke* h, const HpkeBufs& b) {
 namespace jxi {
 
 int hpke_device(const jx_hpke* h) { return h->device; }
-void hpke_key_row(const jx_hpke* h, HpkeKeyRow* out) { *out = h->cfg.key; }
+uint16_t hpke_slot(const jx_hpke* h) { return (uint16_t)h->slot; }
+void hpke_registry(int device, const HpkeKeyRow** rows, uint32_t* capacity) {
+  KeyRegistry* R = registry_for(device);
+  std::lock_guard<std::mutex> lk(R->mu);
+  *rows = R->d_rows;
+  *capacity = KEY_SLOTS;
+}
 bool hpke_default_suite(const jx_hpke* h) { return h->default_suite; }
 uint32_t hpke_enc_len(const jx_hpke* h) { return jx::hpke_enc_len(h->kem); }
 
@@ -537,7 +614,7 @@ hipError_t launch_hpke_rows(const HpkeRowsArgs& a, bool suites, bool p256_rows, 
   ra.a = a;
   const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   hmac_pads(zero, ra.zero_ist, ra.zero_ost);
-  // a key of another suite in the table: every row of the launch goes through the suite kernel
+  // a key of another suite among the launch's jobs: every row of the launch goes through the suite kernel
   if (suites)
     hipLaunchKernelGGL(hpke_rows_suite_kernel, dim3((uint32_t)((a.n + 63) / 64)), dim3(64), 0, s, ra);
   else
@@ -621,9 +698,10 @@ int32_t jx_hpke_create_key(uint32_t kem_id, uint32_t kdf_id, uint32_t aead_id, c
   h->cfg.key.aead = (uint8_t)aead_id;
   h->cfg.key.kem = (uint8_t)kem_id;
   h->default_suite = !p256 && kdf_id == HPKE_KDF_SHA256 && aead_id == HPKE_AEAD_AES128GCM;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
+  // the context's row of the device's key registry (full: JX_HPKE_E_NOMEM)
+  if (const int32_t rc = registry_add(device, h->cfg.key, &h->slot)) {
     delete h;
-    return JX_HPKE_E_HIP;
+    return rc;
   }
   h->arena = jxi::arena_for(device);
   *out = h;
@@ -642,6 +720,9 @@ int32_t jx_hpke_enc_len(const jx_hpke* h) { return h ? (int32_t)hpke_enc_len(h->
 
 int32_t jx_hpke_stream(const jx_hpke* h, void** out_stream) {
   if (!h || !out_stream) return JX_HPKE_E_INVALID;
+  jx_hpke* m = const_cast<jx_hpke*>(h);  // the stream is created at its first use
+  std::lock_guard<std::mutex> lk(m->mu);
+  if (const int32_t rc = ensure_stream(m)) return rc;
   *out_stream = (void*)h->stream;
   return JX_HPKE_OK;
 }
@@ -653,6 +734,7 @@ void jx_hpke_destroy(jx_hpke* h) {
     (void)hipStreamSynchronize(h->stream);
     (void)hipStreamDestroy(h->stream);
   }
+  registry_remove(h->device, h->slot);
   delete h;
 }
 
@@ -665,6 +747,7 @@ int32_t jx_hpke_open_batch_device(jx_hpke* h, uint64_t n, const void* d_encs, co
   if (n == 0) return JX_HPKE_OK;
   std::lock_guard<std::mutex> lk(h->mu);
   HCHK(hipSetDevice(h->device));
+  if (const int32_t rc = ensure_stream(h)) return rc;
   HpkeBufs b{n,
              (const uint8_t*)d_encs,
              (const uint8_t*)d_cts,
@@ -691,6 +774,7 @@ int32_t jx_hpke_open_batch(jx_hpke* h, uint64_t n, const uint8_t* encs, const ui
       return hfail(JX_HPKE_E_INVALID, "offsets must be non-decreasing and every ciphertext >= 16 bytes");
   std::lock_guard<std::mutex> lk(h->mu);
   HCHK(hipSetDevice(h->device));
+  if (const int32_t rc = ensure_stream(h)) return rc;
   const uint64_t ct_bytes = ct_offsets[n], aad_bytes = aad_offsets[n], pt_bytes = ct_bytes - 16 * n;
   const uint64_t enc_bytes = n * hpke_enc_len(h->kem);
   const size_t o_enc = 0, o_ct = o_enc + jxi::align256(enc_bytes), o_aad = o_ct + jxi::align256(ct_bytes),

@@ -4,6 +4,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "jx_keyreg.h"
+
 namespace jx {
 
 enum Algo : uint32_t {
@@ -250,51 +252,14 @@ hipError_t launch_scatter_jobs(const Cfg& c, const JobSlice* d_jobs, uint32_t nj
                                const uint4* outs, const uint8_t* verdicts, const uint8_t* msgs, const uint8_t* nonces,
                                hipStream_t s);
 // ---- HPKE open inside a helper prepare launch (jx_hpke.hip; jx_helper_prep_encrypted_batch)
-// A recipient keypair as the rows kernels read it: the private and public key and the RFC 9180
-// key_schedule_context of its application info (0x00 || psk_id_hash || info_hash: 1 + 2 Nh bytes, 65 for
-// HKDF-SHA256, 97 for -SHA384, 129 for -SHA512) under the key's own suite, whose KDF, AEAD and KEM ids follow (kem:
-// the low byte of the id, 0x20 or 0x10). KEM 0x0020: sk the clamped X25519 scalar, pk the public key, both as LE
-// words. KEM 0x0010 (P-256): sk the LE words of the private integer (sk[0] least significant), pk the 32
-// big-endian bytes of the public point's x and pky those of its y, in memory order. The default-suite kernels
-// read the first 65 context bytes and no ids.
-struct HpkeKeyRow {
-  uint32_t sk[8];
-  uint32_t pk[8];
-  uint8_t ksc[132];
-  uint8_t kdf, aead, kem;
-  uint8_t pad;
-  uint8_t pky[32];
-};
-static_assert(sizeof(HpkeKeyRow) == 232, "HpkeKeyRow layout");
-enum : uint8_t {
-  ENC_ROW_ENCRYPTED = 1,         // the report's helper input share is inside `enc` / the ciphertext (else: uploaded)
-  ENC_ROW_REQUIRE_TASKPROV = 2,  // the task is provisioned by taskprov (aggregator.rs:1869-1879)
-  ENC_ROW_MALFORMED = 4,         // the encapsulated key has the length of neither keypair's KEM: HpkeDecryptError
-                                 // without an open
-  ENC_ROW_ENC65 = 8,             // a 65-byte (P-256) encapsulated key, at enc65_off of the launch's ciphertext bytes:
-                                 // hpke_rows_p256_kernel's row, skipped by the X25519 rows kernels
-};
-// One report's encrypted input share: the HpkeCiphertext's encapsulated key and ciphertext (at ct_off of the
-// launch's ciphertext bytes), what its InputShareAad needs besides the id and public share rows, and the
-// keypairs to try (launch key-table rows; key0 JX_KEY_NONE: the config id is unknown).
-struct EncRow {
-  uint8_t enc[32];
-  uint8_t task_id[32];
-  uint8_t time_be[8];  // ReportMetadata.time, big-endian as encoded
-  uint64_t ct_off;
-  uint32_t ct_len;
-  uint8_t key0, key1, flags, pad;
-  uint64_t enc65_off;  // ENC_ROW_ENC65: where the encapsulated key lies (`enc` is zero)
-};
-static_assert(sizeof(EncRow) == 96, "EncRow layout");
-constexpr uint32_t ENC_MAX_KEYS = 16;  // distinct keypairs in one launch's key table
+// HpkeKeyRow (a row of the device key registry) and EncRow: jx_keyreg.h
 struct HpkeRowsArgs {
   uint64_t n;
   const EncRow* rows;
   const uint8_t* cts;   // ciphertext bytes of the launch
   uint8_t* pts;         // plaintext scratch (same offsets as cts)
-  const HpkeKeyRow* keys;
-  uint32_t nkeys;
+  const HpkeKeyRow* keys;  // the device's key registry (jx_keyreg.h), indexed by EncRow::key0 / key1
+  uint32_t nkeys;          // its capacity
   const uint8_t* nonces;
   const uint8_t* ps;
   uint32_t ps_bytes;

@@ -15,8 +15,9 @@ verdicts and Finish{prep_msg}s are compared with the oracle's, and the engine's 
 and count with the multiplicity-weighted oracle aggregate (verification, not timed).
 
     python tools/bench_jobs.py [--vdafs sumvec,count] [--sizes 10,100,1000,10000] [--threads 1,8,64]
-                               [--seconds 2] [--mode direct|coalesce]
-One JSON line per (vdaf, n, threads).
+                               [--seconds 2] [--mode direct|coalesce] [--encrypted] [--tasks N]
+One JSON line per (vdaf, n, threads). --tasks N (native driver): the many-task shape, N tasks each with its own
+verify key, task id, engine and HPKE keypair, thread t serving task t % N, the pool split across the tasks.
 """
 from __future__ import annotations
 
@@ -36,11 +37,11 @@ P64 = 2**64 - 2**32 + 1
 P128 = 2**128 - 28 * 2**64 + 1
 
 
-def make_pool(vdaf, vk, K, threads):
+def make_pool(vdaf, vk, K, threads, seed=0x10B5):
     from oracle import oracle as O  # input generation and the checker only
 
     orc = O.Prio3Oracle(vdaf.algo_id, vdaf.bits, vdaf.length, vdaf.chunk_length)
-    rng = np.random.default_rng(0x10B5)
+    rng = np.random.default_rng(seed)
     hi = 1 << vdaf.bits if vdaf.algo_id in (1, 2) else 2
     meas = rng.integers(0, hi, size=(K, max(1, vdaf.length)), dtype=np.uint64)
     if vdaf.algo_id == 0:
@@ -268,17 +269,28 @@ def build_driver() -> str:
 
 def run_case_cpp(vdaf, vk, pool, n, T, seconds, mode, window_us, tmp, enc=None, leader=None, leader_threads=0):
     """One case through the native driver (no interpreter between the threads and the C ABI); the
-    aggregate it read is checked here against the oracle. enc: the make_enc_pool extras (the jobs start from
+    aggregates it read are checked here against the oracle. enc: the make_enc_pool extras (the jobs start from
     encrypted report shares); leader: (leader vk, make_leader_pool output) with leader_threads threads of
-    leader prepare_init jobs beside the helper's."""
+    leader prepare_init jobs beside the helper's. Several tasks: vk, pool and enc are lists, one verify key, pool
+    and extras per task (thread t serves task t % len(vk))."""
     import subprocess
 
-    nonces, ps, his, lps, want = pool
-    K = nonces.shape[0]
+    if isinstance(vk, (bytes, bytearray)):
+        vks, pools, encs = [vk], [pool], [enc] if enc else None
+    else:
+        vks, pools, encs = list(vk), list(pool), list(enc) if enc else None
+    N = len(vks)
     pm = vdaf.prep_msg_len
-    src = os.path.join(tmp, f"pool_{vdaf.algo_id}_{K}{'_enc' if enc else ''}.bin")
-    if not os.path.exists(src):
-        with open(src + ".tmp", "wb") as f:
+    K0 = pools[0][0].shape[0]
+    src = os.path.join(tmp, f"pool_{vdaf.algo_id}_{K0}{'_enc' if encs else ''}{f'_{N}tasks' if N > 1 else ''}.bin")
+    for k in range(N):  # task 0's pool is the file itself, task k's the file with ".k" appended
+        nonces, ps, his, lps, want = pools[k]
+        enc = encs[k] if encs else None
+        K = nonces.shape[0]
+        path = src + (f".{k}" if k else "")
+        if os.path.exists(path):
+            continue
+        with open(path + ".tmp", "wb") as f:
             f.write(np.array([K, ps.shape[1], his.shape[1], lps.shape[1], pm, 1 if enc else 0,
                               len(enc["cts"]) if enc else 0, 0], np.uint64).tobytes())
             for a in (nonces, ps, his, lps, want["verdicts"].astype(np.uint8)):
@@ -291,10 +303,10 @@ def run_case_cpp(vdaf, vk, pool, n, T, seconds, mode, window_us, tmp, enc=None, 
                 f.write(enc["cts"])
                 f.write(np.ascontiguousarray(enc["kidx"]).tobytes())
                 f.write(np.ascontiguousarray(enc["status"]).tobytes())
-        os.replace(src + ".tmp", src)
+        os.replace(path + ".tmp", path)
     out = os.path.join(tmp, "jobs_out.bin")
     cmd = [DRIVER, src, out, str(vdaf.algo_id), str(vdaf.bits), str(vdaf.length), str(vdaf.chunk_length),
-           str(vdaf.num_proofs), vk.hex(), str(n), str(T), str(seconds), str(int(mode == "coalesce")), str(window_us),
+           str(vdaf.num_proofs), ",".join(vk.hex() for vk in vks), str(n), str(T), str(seconds), str(int(mode == "coalesce")), str(window_us),
            "1"]
     if leader is not None and leader_threads:
         lvk, (ln, lps_, llis, lv, lsh) = leader
@@ -311,15 +323,19 @@ def run_case_cpp(vdaf, vk, pool, n, T, seconds, mode, window_us, tmp, enc=None, 
                 "error": (r.stderr or "")[-400:]}
     line = json.loads(r.stdout.strip().splitlines()[-1])
     raw = open(out, "rb").read()
-    head = np.frombuffer(raw[:32], np.uint64)
     ob = vdaf.output_len * vdaf.field_bytes
-    agg = raw[32:32 + ob]
-    mult = np.frombuffer(raw[32 + ob:32 + ob + 8 * K], np.uint64).astype(np.int64)
-    fin = want["verdicts"] == 0
-    m_fin = np.where(fin, mult, 0)
     p = P64 if vdaf.field_bytes == 8 else P128
-    exp = weighted_aggregate(want["out_shares"].reshape(K, -1), m_fin, vdaf.field_bytes, p)
-    agg_ok = agg == exp and int(head[3]) == int(m_fin.sum())
+    agg_ok, at = True, 0
+    for k in range(N):  # every task's aggregate and count against the oracle's over the reports its jobs prepared
+        want = pools[k][4]
+        K = pools[k][0].shape[0]
+        head = np.frombuffer(raw[at:at + 32], np.uint64)
+        agg = raw[at + 32:at + 32 + ob]
+        mult = np.frombuffer(raw[at + 32 + ob:at + 32 + ob + 8 * K], np.uint64).astype(np.int64)
+        at += 32 + ob + 8 * K
+        m_fin = np.where(want["verdicts"] == 0, mult, 0)
+        exp = weighted_aggregate(want["out_shares"].reshape(K, -1), m_fin, vdaf.field_bytes, p)
+        agg_ok = agg_ok and agg == exp and int(head[3]) == int(m_fin.sum())
     res = {"vdaf": vdaf.name(), "mode": mode, "driver": "cpp", "reports_per_job": n, "threads": T}
     res.update(line)
     res["verified"] = bool(agg_ok and line["bad_jobs"] == 0 and line.get("leader_bad_jobs", 0) == 0)
@@ -343,6 +359,9 @@ def main():
                          "tools/bin/jobs_driver directly, e.g. under rocprofv3)")
     ap.add_argument("--encrypted", action="store_true",
                     help="cpp driver: the jobs start from HPKE-encrypted report shares (jx_helper_prep_encrypted_batch)")
+    ap.add_argument("--tasks", type=int, default=1,
+                    help="cpp driver: N tasks, each with its own verify key, task id, engine and HPKE keypair; thread t "
+                         "serves task t %% N, and the pool is split across the tasks (pool // N reports each)")
     ap.add_argument("--leader-threads", default="0",
                     help="cpp driver: comma list; L threads of 100-report leader prepare_init jobs of another task "
                          "beside the helper's (an aggregator that is leader for some tasks and helper for others)")
@@ -358,20 +377,27 @@ def main():
     vdafs = {"sumvec": Prio3.sum_vec(8, 1000, 88), "count": Prio3.count(), "sum32": Prio3.sum(32),
              "hist": Prio3.histogram(256, 16)}
     vk = bytes(range(16))
+    sizes = [int(x) for x in a.sizes.split(",") if int(x) > 0]
+    if a.tasks < 1 or (a.tasks > 1 and (a.driver != "cpp" or a.pool // a.tasks < max(sizes))):
+        ap.error("--tasks: the cpp driver's, and pool // tasks must hold the largest job")
     out = open(a.out, "a") if a.out else None
     for key in a.vdafs.split(","):
         vdaf = vdafs[key]
         t0 = time.perf_counter()
-        pool = make_pool(vdaf, vk, a.pool, threads_gen)
+        # task k: verify key vk + k in every byte, pool // N reports of its own (task 0 of one task: the whole pool)
+        vks = [bytes((b + k) % 256 for b in vk) for k in range(a.tasks)]
+        pools = [make_pool(vdaf, vks[k], a.pool // a.tasks, threads_gen, seed=0x10B5 + k) for k in range(a.tasks)]
+        pool = pools[0]
         print(f"# {key}: pool of {a.pool} in {time.perf_counter() - t0:.1f}s", file=sys.stderr, flush=True)
         if a.driver == "cpp":  # this process never touches the GPU: the driver child does
             import tempfile
 
             build_driver()
-            enc = None
+            encs = None
             if a.encrypted:
                 t0 = time.perf_counter()
-                pool, enc = make_enc_pool(vdaf, pool)
+                sealed = [make_enc_pool(vdaf, pools[k], seed=0x5EA1 + k) for k in range(a.tasks)]
+                pools, encs = [s[0] for s in sealed], [s[1] for s in sealed]
                 print(f"# sealed {a.pool} report shares in {time.perf_counter() - t0:.1f}s", file=sys.stderr, flush=True)
             lts = [int(x) for x in a.leader_threads.split(",")]
             leader = None
@@ -382,10 +408,10 @@ def main():
                 if a.keep_pool:
                     os.makedirs(a.keep_pool, exist_ok=True)
                     tmp = a.keep_pool
-                for n in [int(x) for x in a.sizes.split(",") if int(x) > 0]:
+                for n in sizes:
                     for T in [int(x) for x in a.threads.split(",")]:
                         for L in lts:
-                            r = run_case_cpp(vdaf, vk, pool, n, T, a.seconds, a.mode, a.window_us, tmp, enc=enc,
+                            r = run_case_cpp(vdaf, vks, pools, n, T, a.seconds, a.mode, a.window_us, tmp, enc=encs,
                                              leader=leader, leader_threads=L)
                             line = json.dumps(r)
                             print(line, flush=True)
