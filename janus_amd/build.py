@@ -7,13 +7,17 @@ from __future__ import annotations
 import os
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("jx_kernels.hip", "jx_engine.cpp", "jx_arena.cpp", "jx_coalesce.cpp",
-                                                  "jx_hpke.hip", "jx_mp64.hip")]
+SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("jx_hpke_p256.hip", "jx_kernels.hip", "jx_hpke_suite.hip",
+                                                  "jx_hpke_default.hip", "jx_flp.hip", "jx_accumulate.hip",
+                                                  "jx_mp64.hip", "jx_engine.cpp", "jx_coalesce.cpp", "jx_arena.cpp",
+                                                  "jx_hpke.hip")]  # the slowest to compile first
 HEADERS = [os.path.join(_HERE, "csrc", f) for f in ("jx_field.h", "jx_keccak.h", "jx_sha256.h", "jx_kernels.h",
                                                   "jx_hpke.h", "jx_sha_aes.h", "jx_engine_internal.h", "jx_sha512.h",
-                                                  "jx_chapoly.h", "jx_hpke_suites.h", "jx_p256.h", "jx_keyreg.h")]
+                                                  "jx_chapoly.h", "jx_hpke_suites.h", "jx_p256.h", "jx_keyreg.h",
+                                                  "jx_hpke_open.h", "jx_k1_plan.h")]
 OUT = os.path.join(_HERE, "lib", "libjanus_prio3.so")
 # jx_mp64.hip: keep the LDS for the AES table (the AMDGPU backend would otherwise move a small private
 # array of the out-of-line helpers into LDS, +16 KiB per workgroup, one workgroup less per CU)
@@ -36,22 +40,23 @@ def build(force: bool = False, verbose: bool = False) -> str:
         return OUT
     os.makedirs(os.path.dirname(out), exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objs = []
-    # compile the translation units in parallel
-    procs = []
-    for src in SOURCES:
-        obj = os.path.join(os.path.dirname(out), os.path.basename(src) + ".o")
+    objs = [os.path.join(os.path.dirname(out), os.path.basename(src) + ".o") for src in SOURCES]
+
+    def compile_one(src, obj):
         cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-c", src, "-o", obj]
         cmd += EXTRA_FLAGS.get(os.path.basename(src), [])
-        procs.append((subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT), cmd))
-        objs.append(obj)
-    for p, cmd in procs:
-        log, _ = p.communicate()
-        if p.returncode != 0:
-            sys.stderr.write(log.decode())
+        p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+        return p.returncode, p.stdout.decode(), cmd
+
+    # one hipcc per translation unit, at most 16 at a time
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), 16)) as pool:
+        results = list(pool.map(compile_one, SOURCES, objs))
+    for rc, log, cmd in results:
+        if rc != 0:
+            sys.stderr.write(log)
             raise RuntimeError(f"hipcc failed: {' '.join(cmd)}")
         if verbose and log:
-            sys.stderr.write(log.decode())
+            sys.stderr.write(log)
     tmp = f"{out}.{os.getpid()}.tmp"  # link aside, then rename: a reader never sees a partial library
     cmd = [hipcc, f"--offload-arch={ARCH}", "-shared", "-fPIC", "-o", tmp] + objs
     subprocess.run(cmd, check=True)

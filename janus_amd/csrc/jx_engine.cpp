@@ -671,42 +671,13 @@ int32_t jxi::prep_core(jx_engine* e, uint64_t n, const uint8_t* nonces, const ui
   b.msgs = msgs;
   b.consts = e->d_consts;
   b.force_slow = e->force_slow;
-  b.k1_split = e->k1_split;
-  b.k1_lds = lanes_lds_bytes(e->lanes_wg_cap);
-  // A helper launch that would give the fused two-sponge K1 less than one wave per SIMD is bound by
-  // the per-report sponge latency, not by issue: the lane-split kernel runs it in twice the waves
-  // (FixedPointBoundedL2VecSum 16 x 10000, 24,576 reports: 153 -> 92 ms on MI355X), below one
-  // lane-split wave per SIMD the lane-pair kernel splits every sponge over two lanes, and up to one
-  // report-wave per SIMD the word-per-lane kernel spreads it over 25 (round_reports: the fused kernel's
-  // two waves per SIMD, 4 x that many lane-split or 8 x lane-pair lanes; profiles/r05_words_sweep.jsonl).
+  // which helper K1 runs, and whether the launch splits in two: jx_k1_plan.h
   const bool wide = c.bits > 32 && (c.algo == ALGO_SUM || c.algo == ALGO_SUMVEC);
-  if (e->k1_split == 0 && !leader && !wide && e->round_reports) {
-    if (128 * n <= e->round_reports)  // a report per wave, <= one wave per SIMD (1,024 on MI355X): 2.6 vs 3.6 ms
-      b.k1_split = 7;
-    else if (4 * n <= e->round_reports)
-      b.k1_split = 6;
-    else if (2 * n <= e->round_reports)
-      b.k1_split = 3;
-  }
-  // the lane pairs with unrolled rounds while each pair-wave has a SIMD to itself (<= 16,384 reports on MI355X)
-  if (b.k1_split == 6 && 8 * n <= e->round_reports) b.k1_split = 8;
-  // A lane-pair launch of at most half the CUs' workgroups (<= 8,192 reports on MI355X: the coalescer's launches
-  // of Janus-sized jobs, two in flight) reserves LDS for one workgroup per CU, so a second such launch lands on
-  // other CUs instead of doubling up SIMDs with the first (profiles/r06_jobs_*: K1 3.6 ms alone, 4.5 ms beside
-  // another launch on shared CUs).
-  if ((b.k1_split == 8 || b.k1_split == 6) && e->k1_split == 0 && 16 * n <= e->round_reports)
-    b.k1_pairs_lds = lanes_lds_bytes(1);
-  // A lane-split launch past one wave per SIMD puts two of its long chains on some SIMDs and the launch waits
-  // for those. Instead the first round_reports / 4 reports (a lane-split wave per SIMD) run lane-split and the
-  // rest as lane pairs beside them on the side stream: FixedPointBoundedL2VecSum 16 x 10000, 40,960 reports,
-  // 148.4 -> 123.5 ms (tools/kernel_probe fpmix, profiles/r05_fp_mixed_k1.jsonl). Only while no other engine
-  // on the device has a large K1 launch in flight: beside the leader's 640 K1 waves (configs[4] with two jobs in
-  // flight) the 1,536 mixed waves pack worse than 1,280 lane-split ones (helper K1 154 -> 161 ms, every split
-  // point tried; profiles/r05_fp_mixed_k1.jsonl).
-  const uint64_t split_at = e->round_reports / 4 / 64 * 64;
-  const bool big = split_at && n > split_at;
-  const bool mixed = e->k1_split == 0 && b.k1_split == 3 && !wide && big && c.algo != ALGO_COUNT &&
-                     c.algo != ALGO_SUMVEC_F64_MULTIPROOF && !arena_big_busy(e->arena, e);
+  const bool big = k1_big(n, e->round_reports);
+  const bool no_split = c.algo == ALGO_COUNT || c.algo == ALGO_SUMVEC_F64_MULTIPROOF;
+  K1Plan plan = k1_plan(n, e->round_reports, e->k1_forced, leader, wide, no_split, e->lanes_wg_cap, false);
+  if (plan.split && arena_big_busy(e->arena, e))  // asked only of a launch that would split
+    plan = k1_plan(n, e->round_reports, e->k1_forced, leader, wide, no_split, e->lanes_wg_cap, true);
   hipEvent_t ev = nullptr;
   if (c.algo == ALGO_COUNT) {
     HIPCHK(e, stage_begin(e, &ev));
@@ -726,22 +697,21 @@ int32_t jxi::prep_core(jx_engine* e, uint64_t n, const uint8_t* nonces, const ui
     HIPCHK(e, stage_end(e, ST_FLP, ev));
   } else {
     HIPCHK(e, stage_begin(e, &ev));
-    if (mixed) {
+    if (plan.split) {
       if (!e->side) HIPCHK(e, hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
       if (!e->ev_fork) HIPCHK(e, hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
       if (!e->ev_side) HIPCHK(e, hipEventCreateWithFlags(&e->ev_side, hipEventDisableTiming));
-      Bufs head = b, tail = bufs_tail(c, b, split_at);
-      head.n = split_at;
-      tail.k1_split = 8 * tail.n <= e->round_reports ? 8u : 6u;
-      tail.k1_pairs_lds = 0;
+      Bufs head = b;
+      const Bufs tail = bufs_tail(c, b, plan.split);
+      head.n = plan.split;
       HIPCHK(e, hipEventRecord(e->ev_fork, e->stream));
       HIPCHK(e, hipStreamWaitEvent(e->side, e->ev_fork, 0));
-      HIPCHK(e, launch_xof(c, head, e->stream));
-      HIPCHK(e, launch_xof(c, tail, e->side));
+      HIPCHK(e, launch_xof(c, head, plan.head, e->stream));
+      HIPCHK(e, launch_xof(c, tail, plan.tail, e->side));
       HIPCHK(e, hipEventRecord(e->ev_side, e->side));
       HIPCHK(e, hipStreamWaitEvent(e->stream, e->ev_side, 0));
     } else {
-      HIPCHK(e, launch_xof(c, b, e->stream));
+      HIPCHK(e, launch_xof(c, b, plan.head, e->stream));
     }
     if (big) HIPCHK(e, arena_big_record(e->arena, e, e->stream));
     HIPCHK(e, stage_end(e, ST_XOF, ev));
@@ -1088,7 +1058,7 @@ static int32_t pipes_acquire(jx_engine* e, uint32_t P, uint64_t chunk, uint32_t 
   for (uint32_t k = 0; k < P; k++) {
     jx_engine* q = e->pipes[k];
     q->force_slow = e->force_slow;
-    q->k1_split = e->k1_split;
+    q->k1_forced = e->k1_forced;
     q->lanes_wg_cap = e->lanes_wg_cap;
     q->timing = e->timing;
     q->acc_chunks = e->acc_chunks;
@@ -1176,7 +1146,7 @@ int32_t jx_engine_create_ex(const jx_prio3_params* params, const uint8_t* verify
   // (two roles, e.g. leader and helper, still fit on one MI355X). Staging is checked out of the device
   // arena per call, so this sizes launches, not what an idle engine holds. Debug option 5 overrides it.
   const uint64_t per = per_report_bytes(e->cfg);
-  e->round_reports = k1_round_reports(e->cfg, device, 0);
+  e->round_reports = k1_round_reports(e->cfg, device);
   uint64_t budget = 48ull << 30;
   size_t mem_free = 0, mem_total = 0;
   if (hipMemGetInfo(&mem_free, &mem_total) == hipSuccess && e->round_reports && e->round_reports * per > budget) {
@@ -2268,11 +2238,11 @@ int32_t jx_engine_debug(jx_engine* e, int32_t option, int64_t value) {
     return JX_OK;
   }
   if (option == 3) {  // helper K1 kernel
-    if (value != 0 && value != 3 && value != 5 && value != 6 && value != 7) return JX_E_INVALID;
+    if (!k1_forceable(value)) return JX_E_INVALID;
     // 0: automatic (fused; lane-split below one fused wave per SIMD, lane pairs below one lane-split
     // wave per SIMD, a word per lane for the smallest launches), 3: lane-split, 5: fused, 6: lane pairs,
     // 7: a word per lane (6, 7: bits <= 32)
-    e->k1_split = (uint32_t)value;
+    e->k1_forced = (K1Kernel)value;
     return JX_OK;
   }
   if (option == 4) {  // pipelines of the fused device path: 0 automatic, 1 single stream, 2..4

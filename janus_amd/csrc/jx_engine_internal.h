@@ -284,7 +284,7 @@ struct jx_engine {
   double ms[jxi::NST] = {0, 0, 0, 0};
   uint64_t launches[jxi::NST] = {0, 0, 0, 0};
   uint32_t force_slow = 0;
-  uint32_t k1_split = 0;  // helper K1: 0 automatic, 3 lane-split, 5 fused, 6 lane pairs (debug option 3)
+  jx::K1Kernel k1_forced = jx::K1_AUTO;  // helper K1 kernel (debug option 3; jx_k1_plan.h)
   uint32_t lanes_wg_cap = 2;  // lane-split K1 workgroups per CU (debug option 6; 0: no cap)
   // producer / consumer ordering (jx_engine_wait_stream / jx_engine_join_stream): reused events
   hipEvent_t ev_wait = nullptr, ev_join = nullptr;

@@ -568,4 +568,52 @@ JX_HD uint64_t pow64_h(uint64_t a, uint64_t e) {
   return r;
 }
 
+// ----------------------------------------------------------------------------
+// Field128 helpers of the kernels (device code: uint4 is HIP's)
+#if defined(__HIPCC__) || defined(__HIP__)
+
+__device__ __forceinline__ f128 u4_to_f(uint4 v) {
+  return make128((uint64_t)v.x | ((uint64_t)v.y << 32), (uint64_t)v.z | ((uint64_t)v.w << 32));
+}
+__device__ __forceinline__ uint4 f_to_u4(f128 a) { return make_uint4(lo32(a.lo), hi32(a.lo), lo32(a.hi), hi32(a.hi)); }
+__device__ __forceinline__ f128 w4_to_f(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+  return make128((uint64_t)a | ((uint64_t)b << 32), (uint64_t)c | ((uint64_t)d << 32));
+}
+// Montgomery exponentiation, uniform exponent
+__device__ inline f128 mpow(f128 aR, uint32_t e) {
+  f128 r = make128(R1_128_LO, R1_128_HI);
+  while (e) {
+    if (e & 1) r = mont128(r, aR);
+    aR = mont128(aR, aR);
+    e >>= 1;
+  }
+  return r;
+}
+__device__ __forceinline__ f128 msqr_n(f128 a, int n) {
+  for (int i = 0; i < n; i++) a = mont128(a, a);
+  return a;
+}
+// Montgomery inverse: (aR)^(p-2) via an addition chain for p-2 = (2^64-29)*2^64 + (2^64-1)
+__device__ inline f128 minv(f128 a) {
+  f128 x2 = mont128(mont128(a, a), a);    // 2^2-1
+  f128 x4 = mont128(msqr_n(x2, 2), x2);   // 2^4-1
+  f128 x8 = mont128(msqr_n(x4, 4), x4);   // 2^8-1
+  f128 x16 = mont128(msqr_n(x8, 8), x8);  // 2^16-1
+  f128 x32 = mont128(msqr_n(x16, 16), x16);
+  f128 x64 = mont128(msqr_n(x32, 32), x32);
+  f128 x48 = mont128(msqr_n(x32, 16), x16);
+  f128 y = mont128(msqr_n(x48, 8), x8);  // 2^56-1
+  // append the 8 low bits of 0xE3 = 1110 0011
+  const uint32_t tail = 0xE3u;
+  for (int i = 7; i >= 0; i--) {
+    y = mont128(y, y);
+    if ((tail >> i) & 1) y = mont128(y, a);
+  }
+  // y = a^(2^64 - 29); result = y^(2^64) * a^(2^64-1)
+  y = msqr_n(y, 64);
+  return mont128(y, x64);
+}
+
+#endif  // __HIPCC__
+
 }  // namespace jx

@@ -1,7 +1,7 @@
 // jx_hpke_suites.h — the RFC 9180 base-mode key schedule for every suite Janus accepts (core/src/
 // hpke.rs dispatches on HpkeConfig's kem_id, kdf_id and aead_id; messages/src/lib.rs:768-846):
 // KEM 0x0020 (X25519) or 0x0010 (P-256, whose decapsulation is here too, over jx_p256.h) with KDF HKDF-SHA256 /
-// -SHA384 / -SHA512 (1, 2, 3) and AEAD AES-128-GCM / AES-256-GCM / ChaCha20Poly1305 (1, 2, 3). The default suite (1, 1) keeps its own register-resident code in jx_hpke.hip; this
+// -SHA384 / -SHA512 (1, 2, 3) and AEAD AES-128-GCM / AES-256-GCM / ChaCha20Poly1305 (1, 2, 3). The default suite (1, 1) keeps its own register-resident code in jx_hpke_default.hip; this
 // is what the suite kernels run, one report per lane, each lane with the suite of ITS key.
 // __host__ __device__: tests/csrc/hosttest_hpke_suites.cpp runs the same code on the CPU.
 //

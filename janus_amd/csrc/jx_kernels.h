@@ -1,9 +1,11 @@
-// jx_kernels.h — kernel argument structs and launchers shared by jx_kernels.hip and
-// jx_engine.cpp.  See DESIGN.md for the HBM layout.
+// jx_kernels.h — kernel argument structs and launchers shared by the kernel units (jx_kernels.hip, jx_flp.hip,
+// jx_accumulate.hip, jx_mp64.hip) and jx_engine.cpp, and the device helpers that address the interleaved staging.
+// See DESIGN.md for the HBM layout.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "jx_k1_plan.h"
 #include "jx_keyreg.h"
 
 namespace jx {
@@ -124,12 +126,6 @@ struct Bufs {
   uint8_t* msgs;
   const uint4* consts;
   uint32_t force_slow;  // debug: route every report through the slow XOF kernel
-  uint32_t k1_split;    // helper K1 kernel: 3 = lane-split (xof_lanes_kernel), 6 = lane pairs (xof_pairs_kernel,
-                        // bits <= 32), 8 = lane pairs with unrolled rounds, 7 = a word per lane (xof_words_kernel,
-                        // bits <= 32), otherwise the fused kernel
-  uint32_t k1_lds;      // dynamic LDS of the lane-split kernel: caps its workgroups per CU (lanes_lds_bytes)
-  uint32_t k1_pairs_lds;  // dynamic LDS of the lane-pair kernel (0: none): one workgroup per CU, so two small
-                          // launches in flight (coalesced jobs) take disjoint CUs instead of sharing SIMDs
 };
 
 struct AccArgs {
@@ -182,9 +178,10 @@ hipError_t launch_accumulate_segmented(const Cfg& c, const SegArgs& a, uint32_t 
 // multiproof coefficient slots (canonical Field64), per proof
 enum : uint32_t { MCOEF_L = 0, MCOEF_C0 = 1, MCOEF_HALFSUM = 2, MCOEF_T = 3, MCOEF_R = 4, MCOEF_K = 5 };
 
-// launchers (jx_kernels.hip)
+// launchers (jx_kernels.hip: K0, K1; jx_flp.hip: K3, leader finish; jx_accumulate.hip: the rest)
 hipError_t launch_count(const Cfg& c, const Bufs& b, hipStream_t s);
-hipError_t launch_xof(const Cfg& c, const Bufs& b, hipStream_t s);
+// the helper K1 that k1_plan chose (jx_k1_plan.h); a leader launch (b.leader) runs the leader kernels
+hipError_t launch_xof(const Cfg& c, const Bufs& b, K1Launch k1, hipStream_t s);
 hipError_t launch_xof_slow(const Cfg& c, const Bufs& b, hipStream_t s);
 hipError_t launch_leader_finish(const Cfg& c, const Bufs& b, const uint8_t* prep_msgs, const uint8_t* peer,
                                 hipStream_t s);
@@ -268,15 +265,89 @@ struct HpkeRowsArgs {
   uint8_t* status;  // out: JX_OPEN_* per report
 };
 
-// multiproof Field64 SumVec (jx_mp64.hip)
-uint64_t k1_round_reports(const Cfg& c, int device, uint32_t k1_split = 0);
+// the helper K1 (jx_kernels.hip)
+uint64_t k1_round_reports(const Cfg& c, int device);
 // The helper reports [S, b.n) of a launch as Bufs of their own (S a multiple of 64: every staging array is
 // interleaved by 64-report blocks), for a K1 launch over part of the reports.
 Bufs bufs_tail(const Cfg& c, const Bufs& b, uint64_t S);
-uint32_t lanes_lds_bytes(uint32_t wgs_per_cu);
+// multiproof Field64 SumVec (jx_mp64.hip)
 uint64_t mp_k1_round_reports(int device);
 hipError_t launch_mp_xof(const Cfg& c, const Bufs& b, hipStream_t s);
 hipError_t launch_mp_slow(const Cfg& c, const Bufs& b, hipStream_t s);
 hipError_t launch_mp_flp(const Cfg& c, const Bufs& b, hipStream_t s);
 
+inline uint32_t nblk_of(uint64_t n) { return (uint32_t)((n + 63) / 64); }  // 64-report blocks of a launch
+
 }  // namespace jx
+
+// ---- the staging layout as the kernels address it (device code: jx_kernels.hip, jx_flp.hip, jx_accumulate.hip)
+#if defined(__HIPCC__) || defined(__HIP__)
+#include "jx_field.h"
+
+namespace jx {
+
+// interleaved staging address
+__device__ __forceinline__ uint64_t il_idx(uint64_t blk, uint32_t len, uint32_t e, uint32_t lane) {
+  return (blk * len + e) * IL + lane;
+}
+// (the staging is global memory: the address-space casts keep these global_load/store even inside the
+// non-inlined XOF tail, where a generic pointer would make them flat accesses that wait with vmcnt(0) and
+// lgkmcnt(0) each)
+// global (not flat) pointers for the staging in the non-inlined XOF tail: flat accesses count in both
+// vmcnt and lgkmcnt and force full waits; the host pass of hipcc keeps plain pointers
+#ifdef __HIP_DEVICE_COMPILE__
+typedef __attribute__((address_space(1))) uint4 g_uint4;
+#else
+typedef uint4 g_uint4;
+#endif
+__device__ __forceinline__ f128 ld_il(const uint4* base, uint64_t blk, uint32_t len, uint32_t e, uint32_t lane) {
+  return u4_to_f(((const g_uint4*)base)[il_idx(blk, len, e, lane)]);
+}
+__device__ __forceinline__ void st_il(uint4* base, uint64_t blk, uint32_t len, uint32_t e, uint32_t lane, f128 v) {
+  ((g_uint4*)base)[il_idx(blk, len, e, lane)] = f_to_u4(v);
+}
+// The measurement share as the FLP kernels read it: the interleaved staging (element e of the lane's
+// report at p[e * IL]) or, for the leader, its explicit input share in place (p[e], report-major).
+struct MeasView {
+  const uint4* p;
+  uint32_t es;  // element stride in uint4
+  __device__ __forceinline__ const uint4& operator[](uint64_t e) const { return p[e * es]; }
+};
+__device__ __forceinline__ MeasView meas_view(const Cfg& c, const Bufs& b, uint64_t blk, uint32_t lane) {
+  if (b.meas_rs) {
+    const uint64_t r0 = blk * 64 + lane, r = r0 < b.n ? r0 : b.n - 1;
+    return MeasView{reinterpret_cast<const uint4*>(b.meas_src + r * b.meas_rs), 1u};
+  }
+  return MeasView{b.meas + il_idx(blk, c.meas_len, 0, lane), (uint32_t)IL};
+}
+__device__ __forceinline__ void load16(const uint8_t* p, uint32_t w[4]) {
+  uint4 v = *reinterpret_cast<const uint4*>(p);
+  w[0] = v.x;
+  w[1] = v.y;
+  w[2] = v.z;
+  w[3] = v.w;
+}
+
+// the verify key of report r: its row of the per-report keys of a coalesced launch, or the engine's
+__device__ __forceinline__ void load_vk(const Cfg& c, const Bufs& b, uint64_t r, uint32_t vk[4]) {
+  if (b.vkeys) {
+    load16(b.vkeys + 16 * r, vk);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 4; i++) vk[i] = c.vk[i];
+  }
+}
+
+// 192-bit add of x << sh (sh < 64) into the accumulator
+__device__ __forceinline__ void trunc_add(acc192& a, f128 x, uint32_t sh) {
+  uint64_t w0 = x.lo << sh;
+  uint64_t w1 = sh ? ((x.hi << sh) | (x.lo >> (64 - sh))) : x.hi;
+  uint64_t w2 = sh ? (x.hi >> (64 - sh)) : 0;
+  uint32_t cc = 0;
+  a.w0 = addc64(a.w0, w0, cc);
+  a.w1 = addc64(a.w1, w1, cc);
+  a.w2 = a.w2 + w2 + cc;
+}
+
+}  // namespace jx
+#endif  // __HIPCC__

@@ -15,6 +15,10 @@
 //                      i.e. BatchAggregation::merged_with (models.rs:1275-1330).
 //
 // Prio3Count (Field64, 3 permutations) runs as one lane-per-report kernel.
+//
+// This unit holds K0 (Count) and K1; K3 is in jx_flp.hip and K4 with what follows it in jx_accumulate.hip, so that
+// the three compile side by side. What they share: the field helpers of jx_field.h and the staging layout of
+// jx_kernels.h.
 // Algorithm: draft-irtf-cfrg-vdaf-08 as implemented by prio 0.16.1; see DESIGN.md.
 #include <cstdlib>
 #include <stdlib.h>
@@ -27,102 +31,6 @@
 #include "jx_sha256.h"
 
 namespace jx {
-
-// ---------------------------------------------------------------------------- helpers
-
-__device__ __forceinline__ f128 u4_to_f(uint4 v) {
-  return make128((uint64_t)v.x | ((uint64_t)v.y << 32), (uint64_t)v.z | ((uint64_t)v.w << 32));
-}
-__device__ __forceinline__ uint4 f_to_u4(f128 a) { return make_uint4(lo32(a.lo), hi32(a.lo), lo32(a.hi), hi32(a.hi)); }
-__device__ __forceinline__ f128 w4_to_f(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-  return make128((uint64_t)a | ((uint64_t)b << 32), (uint64_t)c | ((uint64_t)d << 32));
-}
-// interleaved staging address
-__device__ __forceinline__ uint64_t il_idx(uint64_t blk, uint32_t len, uint32_t e, uint32_t lane) {
-  return (blk * len + e) * IL + lane;
-}
-// (the staging is global memory: the address-space casts keep these global_load/store even inside the
-// non-inlined XOF tail, where a generic pointer would make them flat accesses that wait with vmcnt(0) and
-// lgkmcnt(0) each)
-// global (not flat) pointers for the staging in the non-inlined XOF tail: flat accesses count in both
-// vmcnt and lgkmcnt and force full waits; the host pass of hipcc keeps plain pointers
-#ifdef __HIP_DEVICE_COMPILE__
-typedef __attribute__((address_space(1))) uint4 g_uint4;
-#else
-typedef uint4 g_uint4;
-#endif
-__device__ __forceinline__ f128 ld_il(const uint4* base, uint64_t blk, uint32_t len, uint32_t e, uint32_t lane) {
-  return u4_to_f(((const g_uint4*)base)[il_idx(blk, len, e, lane)]);
-}
-__device__ __forceinline__ void st_il(uint4* base, uint64_t blk, uint32_t len, uint32_t e, uint32_t lane, f128 v) {
-  ((g_uint4*)base)[il_idx(blk, len, e, lane)] = f_to_u4(v);
-}
-// The measurement share as the FLP kernels read it: the interleaved staging (element e of the lane's
-// report at p[e * IL]) or, for the leader, its explicit input share in place (p[e], report-major).
-struct MeasView {
-  const uint4* p;
-  uint32_t es;  // element stride in uint4
-  __device__ __forceinline__ const uint4& operator[](uint64_t e) const { return p[e * es]; }
-};
-__device__ __forceinline__ MeasView meas_view(const Cfg& c, const Bufs& b, uint64_t blk, uint32_t lane) {
-  if (b.meas_rs) {
-    const uint64_t r0 = blk * 64 + lane, r = r0 < b.n ? r0 : b.n - 1;
-    return MeasView{reinterpret_cast<const uint4*>(b.meas_src + r * b.meas_rs), 1u};
-  }
-  return MeasView{b.meas + il_idx(blk, c.meas_len, 0, lane), (uint32_t)IL};
-}
-__device__ __forceinline__ void load16(const uint8_t* p, uint32_t w[4]) {
-  uint4 v = *reinterpret_cast<const uint4*>(p);
-  w[0] = v.x;
-  w[1] = v.y;
-  w[2] = v.z;
-  w[3] = v.w;
-}
-
-// the verify key of report r: its row of the per-report keys of a coalesced launch, or the engine's
-__device__ __forceinline__ void load_vk(const Cfg& c, const Bufs& b, uint64_t r, uint32_t vk[4]) {
-  if (b.vkeys) {
-    load16(b.vkeys + 16 * r, vk);
-  } else {
-#pragma unroll
-    for (int i = 0; i < 4; i++) vk[i] = c.vk[i];
-  }
-}
-
-// Montgomery exponentiation, uniform exponent
-__device__ f128 mpow(f128 aR, uint32_t e) {
-  f128 r = make128(R1_128_LO, R1_128_HI);
-  while (e) {
-    if (e & 1) r = mont128(r, aR);
-    aR = mont128(aR, aR);
-    e >>= 1;
-  }
-  return r;
-}
-__device__ __forceinline__ f128 msqr_n(f128 a, int n) {
-  for (int i = 0; i < n; i++) a = mont128(a, a);
-  return a;
-}
-// Montgomery inverse: (aR)^(p-2) via an addition chain for p-2 = (2^64-29)*2^64 + (2^64-1)
-__device__ f128 minv(f128 a) {
-  f128 x2 = mont128(mont128(a, a), a);    // 2^2-1
-  f128 x4 = mont128(msqr_n(x2, 2), x2);   // 2^4-1
-  f128 x8 = mont128(msqr_n(x4, 4), x4);   // 2^8-1
-  f128 x16 = mont128(msqr_n(x8, 8), x8);  // 2^16-1
-  f128 x32 = mont128(msqr_n(x16, 16), x16);
-  f128 x64 = mont128(msqr_n(x32, 32), x32);
-  f128 x48 = mont128(msqr_n(x32, 16), x16);
-  f128 y = mont128(msqr_n(x48, 8), x8);  // 2^56-1
-  // append the 8 low bits of 0xE3 = 1110 0011
-  const uint32_t tail = 0xE3u;
-  for (int i = 7; i >= 0; i--) {
-    y = mont128(y, y);
-    if ((tail >> i) & 1) y = mont128(y, a);
-  }
-  // y = a^(2^64 - 29); result = y^(2^64) * a^(2^64-1)
-  y = msqr_n(y, 64);
-  return mont128(y, x64);
-}
 
 // ---------------------------------------------------------------------------- Field64 helpers (Count)
 
@@ -274,17 +182,6 @@ struct Trunc {
   acc192 a;
   uint32_t j, i;
 };
-
-// 192-bit add of x << sh (sh < 64) into the accumulator
-__device__ __forceinline__ void trunc_add(acc192& a, f128 x, uint32_t sh) {
-  uint64_t w0 = x.lo << sh;
-  uint64_t w1 = sh ? ((x.hi << sh) | (x.lo >> (64 - sh))) : x.hi;
-  uint64_t w2 = sh ? (x.hi >> (64 - sh)) : 0;
-  uint32_t cc = 0;
-  a.w0 = addc64(a.w0, w0, cc);
-  a.w1 = addc64(a.w1, w1, cc);
-  a.w2 = a.w2 + w2 + cc;
-}
 
 // A value the optimizer cannot see through (no instruction is emitted): keeps x * 2^j a single
 // v_mad_u64_u32 (x * 2^j + T) instead of the zero-extend + 64-bit shift + 64-bit add it would
@@ -851,7 +748,7 @@ __device__ __forceinline__ uint32_t lower_to_upper(uint32_t v) {
 
 // Registers: the XOF tail is inlined (xof_tail<true>) and the kernel is built for two waves per SIMD, so
 // nothing spills (no scratch); how many of its workgroups share a CU is capped at launch by dynamic LDS
-// it does not use (Bufs::k1_lds, jx_engine_debug option 6), the placement the two-jobs shape wants
+// it does not use (K1Launch::lds, jx_engine_debug option 6), the placement the two-jobs shape wants
 // (chain-latency-bound waves, at most two per SIMD).
 template <bool WIDE>  // WIDE (bits > 32) carries 4 more truncation words
 __global__ __launch_bounds__(64 * K1_WAVES, 2) void xof_lanes_kernel(Cfg c, Bufs b) {
@@ -1217,7 +1114,7 @@ __device__ __forceinline__ void sponge_oneblock_half(uint32_t* s, const Block& m
 
 // UNR: the rounds of the block loop unrolled (round constants as literals): 4.03 -> 3.59 ms for launches of
 // at most one pair-wave per SIMD, but slower with several waves per SIMD (64 x 1,000-report coalesced jobs:
-// 12.5 -> 15.2 ms per launch), so the engine picks it only for the former (prep_core, k1_split 8).
+// 12.5 -> 15.2 ms per launch), so the engine picks it only for the former (k1_plan, K1_PAIRS_UNROLLED).
 template <bool UNR>
 __global__ __launch_bounds__(64 * K1_WAVES, 2) void xof_pairs_kernel(Cfg c, Bufs b) {
   const uint32_t lane = threadIdx.x & 63;
@@ -2076,1359 +1973,7 @@ __global__ __launch_bounds__(64) void xof_slow_kernel(Cfg c, Bufs b) {
   b.flags[r0] = flags & ~FLAG_SLOW;
 }
 
-// ---------------------------------------------------------------------------- K3: FLP query + decide
-
-__device__ __forceinline__ f128 ld_lead(const Bufs& b, const Cfg& c, uint64_t r, uint32_t idx, bool& dfail) {
-  uint4 v = *reinterpret_cast<const uint4*>(b.lps + (uint64_t)c.lps_bytes * r + 16u * idx);
-  f128 x = u4_to_f(v);
-  dfail |= ge_p128(x);
-  return x;
-}
-
-// Prio3Sum: gadget PolyEval(x^2 - x), arity 1, `bits` calls; one report per lane.
-// LEADER: writes the leader's verifier share [v, W0, G(t)] as its prep share.
-template <bool LEADER>
-__global__ __launch_bounds__(256) void flp_sum_kernel(Cfg c, Bufs b) {
-  const uint32_t lane = threadIdx.x & 63;
-  const uint64_t blk = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  const uint64_t nblk = (b.n + 63) / 64;
-  if (blk >= nblk) return;
-  const uint64_t r0 = blk * 64 + lane;
-  const uint64_t r = r0 < b.n ? r0 : b.n - 1;
-  const uint32_t NC = c.ncoef, C = c.calls;
-  const uint4* omega = b.consts + c.c_omega;
-  f128 LR = ld_il(b.coef, blk, NC, COEF_L, lane), c0R = ld_il(b.coef, blk, NC, COEF_C0, lane);
-  f128 tR = ld_il(b.coef, blk, NC, COEF_T, lane), rR = ld_il(b.coef, blk, NC, COEF_R, lane);
-  acc192 ao;
-  acc_zero(ao);
-  const MeasView mv = meas_view(c, b, blk, lane);
-  for (uint32_t k = 1; k <= C; k++) {
-    f128 x = u4_to_f(mv[k - 1]);
-    uint64_t lo, hi;
-    uint32_t top;
-    mont128_lazy(x, ld_il(b.coef, blk, NC, COEF_K + k - 1, lane), lo, hi, top);
-    acc_add(ao, lo, hi, top);
-  }
-  f128 s0 = ld_il(b.proof, blk, c.proof_len, 0, lane);
-  f128 W0 = mont128(add128(mont128(s0, c0R), acc_reduce(ao)), LR);
-  // v = sum_{k=1..C} r^k g(w^k). The spec evaluates the gadget polynomial g (GL = 2P - 1
-  // coefficients) at every w^k by Horner: C * GL products and proof-share reads. Since w^P = 1,
-  // g(w^k) = sum_{j<P} g'_j w^{kj} with g'_j = g_j + g_{j+P}, so
-  //   v = sum_{j<P} g'_j S_j,   S_j = sum_{k=1..C} q_j^k,   q_j = r w^j.
-  // w^{P/2} = -1 gives q_{j+P/2} = -q_j, so with E_j / O_j the even / odd-power parts of S_j,
-  // S_j = E + O and S_{j+P/2} = E - O. With Q = q^2 and s = sum_{m=1..n} Q^m, n = floor(C/2):
-  // E = s, O = q (1 + s - [C even] Q^n); s and Q^n come from the bits of n by doubling
-  // (s_2n = s_n + Q^n s_n, Q^2n = (Q^n)^2; s_n+1 = s_n + Q^n+1). ~2 log2(C) products per pair of
-  // j (identity checked in Python for C = 1..91), every proof coefficient read once.
-  const uint32_t GL = c.gpoly_len, P = c.P, H = c.P / 2, n = C / 2;
-  const f128 R1 = make128(R1_128_LO, R1_128_HI);
-  f128 v = make128(0, 0);
-  const f128 w1 = u4_to_f(omega[1 % P]);
-  f128 wj = u4_to_f(omega[0]);  // w^j R
-  for (uint32_t j = 0; j < H; j++) {
-    f128 ga = ld_il(b.proof, blk, c.proof_len, 1 + j, lane);
-    if (j + P < GL) ga = add128(ga, ld_il(b.proof, blk, c.proof_len, 1 + j + P, lane));
-    f128 gb = ld_il(b.proof, blk, c.proof_len, 1 + j + H, lane);
-    if (j + H + P < GL) gb = add128(gb, ld_il(b.proof, blk, c.proof_len, 1 + j + H + P, lane));
-    const f128 q = mont128(rR, wj);  // r w^j, Montgomery form
-    f128 sq = make128(0, 0), pq = R1;  // s_n, Q^n
-    if (n > 0) {
-      const f128 Q = mont128(q, q);
-      sq = Q;
-      pq = Q;
-      const uint32_t top = 31u - (uint32_t)__builtin_clz(n);
-      for (int bit = (int)top - 1; bit >= 0; bit--) {
-        sq = add128(sq, mont128(pq, sq));
-        pq = mont128(pq, pq);
-        if ((n >> bit) & 1u) {
-          pq = mont128(pq, Q);
-          sq = add128(sq, pq);
-        }
-      }
-    }
-    const f128 O = mont128(q, add128(R1, (C & 1u) ? sq : sub128(sq, pq)));
-    v = add128(v, mont128(ga, add128(sq, O)));
-    v = add128(v, mont128(gb, sub128(sq, O)));
-    wj = mont128(wj, w1);
-  }
-  f128 G = make128(0, 0);
-  for (uint32_t m = GL; m-- > 0;) G = add128(mont128(G, tR), ld_il(b.proof, blk, c.proof_len, 1 + m, lane));
-  if (LEADER) {
-    if (r0 < b.n) {
-      uint4* o = reinterpret_cast<uint4*>(b.lps_out + (uint64_t)c.lps_bytes * r);
-      o[0] = f_to_u4(v);
-      o[1] = f_to_u4(W0);
-      o[2] = f_to_u4(G);
-      b.verdicts[r0] = (b.flags[r] & (FLAG_INIT_FAIL | FLAG_INPUT_FAIL)) ? 1 : 0;
-    }
-    return;
-  }
-  bool dfail = false;
-  f128 lv = ld_lead(b, c, r, 0, dfail), lw = ld_lead(b, c, r, 1, dfail), lg = ld_lead(b, c, r, 2, dfail);
-  const uint32_t flags = b.flags[r];
-  uint32_t verdict = 0;
-  if (flags & FLAG_INIT_FAIL)
-    verdict = 1;
-  else if (dfail)
-    verdict = 2;
-  else {
-    f128 V0 = add128(v, lv), V1 = add128(W0, lw), VG = add128(G, lg);
-    // (V1^2 - V1) == VG, compared in the R^-1 scaled domain
-    f128 lhs = sub128(mont128(V1, V1), mont128(V1, make128(1, 0)));
-    if (!is_zero128(V0) || !eq128(lhs, mont128(VG, make128(1, 0))))
-      verdict = 3;
-    else if (flags & FLAG_NEXT_FAIL)
-      verdict = 4;
-  }
-  if (r0 < b.n) b.verdicts[r0] = (uint8_t)verdict;
-}
-
-// The part kernels' common end: the calls kf+1..C (the ragged last call, or every call of a padded
-// group) with guarded direct loads, then the wires at t, the leader's verifier share and the gadget
-// polynomial's share of v and G(t) for group g of block blk.
-template <int PPW, bool HIST, bool LEADER>
-__device__ __forceinline__ void psum_group_finish(const Cfg& c, const Bufs& b, uint64_t blk, uint32_t g, uint32_t lane,
-                                                  const f128* E, const f128* O, f128 sxr);
-template <int PPW, bool HIST, bool LEADER>
-__device__ __forceinline__ void psum_part_finish(const Cfg& c, const Bufs& b, uint64_t blk, uint32_t g, uint32_t lane,
-                                                 uint32_t kf, wacc26* ae, wacc26* ao, acc192& sx) {
-  const uint32_t NG = c.ngroups;
-  const uint64_t r0 = blk * 64 + lane;
-  const uint64_t r = r0 < b.n ? r0 : b.n - 1;
-  const uint32_t NC = c.ncoef, C = c.calls, chunk = c.chunk, M = c.meas_len, A = 2 * chunk;
-  const uint32_t j0 = g * PPW;
-  const uint4* coefb = b.coef + il_idx(blk, NC, 0, lane);
-  const MeasView measb = meas_view(c, b, blk, lane);
-#pragma unroll 1
-  for (uint32_t k = kf + 1; k <= C; k++) {  // the ragged last call(s), or every call of a padded group
-    const limbs26 ck = to_limbs26(u4_to_f(coefb[(COEF_K + 2 * (k - 1)) * IL]));
-    const limbs26 dk = to_limbs26(u4_to_f(coefb[(COEF_K + 2 * (k - 1) + 1) * IL]));
-    const uint32_t nb = (k - 1) * chunk + j0;
-#pragma unroll
-    for (int i = 0; i < PPW; i++) {
-      if (j0 + i < chunk && nb + i < M) {
-        const f128 x = u4_to_f(measb[nb + i]);
-        const limbs26 xl = to_limbs26(x);
-        wacc_mac(ae[i], xl, dk);
-        wacc_mac(ao[i], xl, ck);
-        if (HIST) acc_add128(sx, x);
-      }
-    }
-    if (((k - kf) & 511u) == 0) {
-#pragma unroll
-      for (int i = 0; i < PPW; i++) {
-        wacc_normalize(ae[i]);
-        wacc_normalize(ao[i]);
-      }
-    }
-  }
-  f128 E[PPW], O[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; i++) {
-    E[i] = wacc_reduce(ae[i]);
-    O[i] = wacc_reduce(ao[i]);
-  }
-  psum_group_finish<PPW, HIST, LEADER>(c, b, blk, g, lane, E, O, HIST ? acc_reduce(sx) : make128(0, 0));
-}
-
-// The group finish from the reduced wire sums E_i = (sum_k d_k x_{k,i}) R, O_i = (sum_k c_k x_{k,i}) R of
-// its PPW slots: wires at t (plus the leader's verifier share), this group's share of v and G(t), written
-// as the four partial sums of the group (Histogram: sxr = its sum of x).
-template <int PPW, bool HIST, bool LEADER>
-__device__ __forceinline__ void psum_group_finish(const Cfg& c, const Bufs& b, uint64_t blk, uint32_t g, uint32_t lane,
-                                                  const f128* E, const f128* O, f128 sxr) {
-  const uint32_t NG = c.ngroups;
-  const uint64_t r0 = blk * 64 + lane;
-  const uint64_t r = r0 < b.n ? r0 : b.n - 1;
-  const uint32_t NC = c.ncoef, chunk = c.chunk, A = 2 * chunk;
-  const uint32_t j0 = g * PPW;
-  const uint4* coefb = b.coef + il_idx(blk, NC, 0, lane);
-  // ---- wires at t for this group's slots, plus the leader's verifier share. K1 scaled the constants by
-  // L (xof_tail): Lc = L canonical, c0LR = c_0 L R, hsL = L (sum c_k)/2, rpowL_j = L r^(j+1), so
-  //   wire_even(t) = L (c_0 se + r^(j+1) sum_k d_k x) = mont(se, c0LR) + mont(E, rpowL_j)
-  //   wire_odd(t)  = L (c_0 so + sum_k c_k x - (sum c_k)/2) = mont(so, c0LR) + mont(O, Lc) - hsL
-  // (E, O are R-scaled: c_k, d_k are stored in Montgomery form).
-  const f128 Lc = u4_to_f(coefb[COEF_L * IL]), c0LR = u4_to_f(coefb[COEF_C0 * IL]);
-  const f128 hsL = u4_to_f(coefb[COEF_HALFSUM * IL]);
-  bool dfail = false;
-  f128 prod = make128(0, 0);
-#pragma unroll
-  for (int i = 0; i < PPW; i++) {
-    const uint32_t j = j0 + i;
-    if (j < chunk) {
-      f128 se = ld_il(b.proof, blk, c.proof_len, 2 * j, lane);
-      f128 so = ld_il(b.proof, blk, c.proof_len, 2 * j + 1, lane);
-      const f128 rpowL = u4_to_f(coefb[(c.c_rpow + j) * IL]);
-      const f128 We = add128(mont128(se, c0LR), mont128(E[i], rpowL));
-      const f128 Wo = sub128(add128(mont128(so, c0LR), mont128(O[i], Lc)), hsL);
-      if (LEADER) {  // the leader's verifier share: wire values at t
-        if (r0 < b.n) {
-          uint4* o = reinterpret_cast<uint4*>(b.lps_out + (uint64_t)c.lps_bytes * r);
-          o[1 + 2 * j] = f_to_u4(We);
-          o[2 + 2 * j] = f_to_u4(Wo);
-        }
-      } else {
-        f128 Ve = add128(We, ld_lead(b, c, r, 1 + 2 * j, dfail));
-        f128 Vo = add128(Wo, ld_lead(b, c, r, 2 + 2 * j, dfail));
-        prod = add128(prod, mont128(Ve, Vo));
-      }
-    }
-  }
-  // ---- gadget polynomial: v-part = sum_m g_m * S_m and the G(t) part over this group's m-range
-  const uint32_t GL = c.gpoly_len;
-  const uint32_t per = (GL + NG - 1) / NG;
-  const uint32_t m0 = g * per, m1 = min(GL, m0 + per);
-  const uint4* Sm = b.consts + c.c_S;
-  f128 vpart = make128(0, 0), gpart = make128(0, 0);
-  if (m0 < m1) {
-    const f128 tR = u4_to_f(coefb[COEF_T * IL]);
-    for (uint32_t m = m1; m-- > m0;) {
-      f128 gm = ld_il(b.proof, blk, c.proof_len, A + m, lane);
-      vpart = add128(vpart, mont128(gm, u4_to_f(Sm[m])));
-      gpart = add128(mont128(gpart, tR), gm);
-    }
-    gpart = mont128(gpart, u4_to_f(coefb[(c.c_tpow + g) * IL]));  // t^m0 R (K1's table)
-  }
-  uint4* pp = b.part + ((blk * c.ngt + g) * 4) * IL + lane;
-  pp[0] = f_to_u4(prod);
-  pp[IL] = f_to_u4(vpart);
-  pp[2 * IL] = f_to_u4(gpart);
-  if (HIST) pp[3 * IL] = f_to_u4(sxr);
-  if (dfail && r0 < b.n) atomicOr(&b.flags[r0], FLAG_DFAIL);
-}
-
-// Prio3SumVec / Prio3Histogram: gadget ParallelSum(Mul, chunk), arity 2*chunk.
-//
-// Phase 1 (flp_psum_part_kernel): one wave per (64-report block, slot group). Lanes are
-// reports (the interleaved staging makes every load a coalesced 1 KiB). Group g owns the
-// chunk slots [g*PPW, (g+1)*PPW) -- 2*PPW lazy wire accumulators per lane, small enough to
-// stay in registers at >= 3 waves/SIMD -- and the gadget-polynomial coefficients
-// [g*per, (g+1)*per). It writes four partial sums per report: sum_i Ve_i*Vo_i over its
-// slots, its share of v (sum_m g_m S_m), its share of G(t), and (Histogram) sum of x.
-// Phase 2 (flp_psum_final_kernel): one report per lane; adds the partials, the leader's
-// v and G(t), and decides.
-// PF: calls whose loads are in flight ahead of the one being multiplied (1: deeper register
-// prefetch measured no faster). Used for PPW = 1; PPW = 2 takes the LDS-DMA ring kernel below.
-template <int PPW, bool HIST, bool LEADER, int PF = 1>
-__global__ __launch_bounds__(64, 4) void flp_psum_part_kernel(Cfg c, Bufs b) {
-  const uint32_t NG = c.ngroups;
-  // Workgroup ids are dispatched round-robin over the 8 XCDs; map them so that the NG
-  // groups of one block run back to back on one XCD and share its L2 (coefficients,
-  // leader share).
-  const uint32_t bid = blockIdx.x;
-  const uint32_t xcd = bid & 7u, q = bid >> 3;
-  const uint32_t g = q % NG;
-  const uint64_t blk = (uint64_t)(q / NG) * 8 + xcd;
-  const uint64_t nblk = (b.n + 63) / 64;
-  if (blk >= nblk) return;
-  const uint32_t lane = threadIdx.x;
-  const uint32_t NC = c.ncoef, C = c.calls, chunk = c.chunk, M = c.meas_len;
-  const uint32_t j0 = g * PPW;
-
-  // wire sums over the calls: ae[i] = sum_k d_k x_{k,i} * R, ao[i] = sum_k c_k x_{k,i} * R
-  // (c_k, d_k are stored in Montgomery form), as unreduced 26-bit-limb column sums.
-  wacc26 ae[PPW], ao[PPW];
-  acc192 sx;
-#pragma unroll
-  for (int i = 0; i < PPW; i++) {
-    wacc_zero(ae[i]);
-    wacc_zero(ao[i]);
-  }
-  acc_zero(sx);
-  const uint4* coefb = b.coef + il_idx(blk, NC, 0, lane);
-  const MeasView measb = meas_view(c, b, blk, lane);
-  // calls whose PPW slots of this group are all real measurement elements run branch-free;
-  // the rest (the ragged last chunk, slots beyond chunk) take the guarded tail loop
-  uint32_t kf = 0;
-  if (j0 + PPW <= chunk && M >= j0 + PPW) kf = min(C, (M - j0 - PPW) / chunk + 1);
-  for (uint32_t k0 = 1; k0 <= kf; k0 += 512) {  // <= 5 * 512 limb products (< 2^52) per column
-    const uint32_t k1 = min(kf, k0 + 511);
-    // software pipeline: the loads of calls k+1 .. k+PF are in flight while call k multiplies
-    uint4 cr[PF], dr[PF], xr[PF][PPW];
-#pragma unroll
-    for (int u = 0; u < PF; u++) {
-      const uint32_t k = k0 + u;
-      if (k <= k1) {
-        cr[u] = coefb[(COEF_K + 2 * (k - 1)) * IL];
-        dr[u] = coefb[(COEF_K + 2 * (k - 1) + 1) * IL];
-#pragma unroll
-        for (int i = 0; i < PPW; i++) xr[u][i] = measb[(uint64_t)((k - 1) * chunk + j0 + i)];
-      }
-    }
-#pragma unroll 1
-    for (uint32_t kb = k0; kb <= k1; kb += PF) {
-#pragma unroll
-      for (int u = 0; u < PF; u++) {
-        const uint32_t k = kb + u;
-        if (k <= k1) {
-          const limbs26 ck = to_limbs26(u4_to_f(cr[u]));
-          const limbs26 dk = to_limbs26(u4_to_f(dr[u]));
-          f128 x[PPW];
-#pragma unroll
-          for (int i = 0; i < PPW; i++) x[i] = u4_to_f(xr[u][i]);
-          const uint32_t kn = k + PF;
-          if (kn <= k1) {
-            cr[u] = coefb[(COEF_K + 2 * (kn - 1)) * IL];
-            dr[u] = coefb[(COEF_K + 2 * (kn - 1) + 1) * IL];
-#pragma unroll
-            for (int i = 0; i < PPW; i++) xr[u][i] = measb[(uint64_t)((kn - 1) * chunk + j0 + i)];
-          }
-#pragma unroll
-          for (int i = 0; i < PPW; i++) {
-            const limbs26 xl = to_limbs26(x[i]);
-            wacc_mac(ae[i], xl, dk);
-            wacc_mac(ao[i], xl, ck);
-            if (HIST) acc_add128(sx, x[i]);
-          }
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < PPW; i++) {
-      wacc_normalize(ae[i]);
-      wacc_normalize(ao[i]);
-    }
-  }
-  psum_part_finish<PPW, HIST, LEADER>(c, b, blk, g, lane, kf, ae, ao, sx);
-}
-
-// s_waitcnt vmcnt(N) alone (expcnt / lgkmcnt left unconstrained)
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  static_assert(N >= 0 && N < 64, "vmcnt is 6 bits");
-  __builtin_amdgcn_s_waitcnt(0x3f70 | (N & 15) | ((N >> 4) << 14));
-}
-__device__ __forceinline__ void glds16(const uint4* src, uint4* lds_row) {
-  __builtin_amdgcn_global_load_lds((const void*)src, (void*)lds_row, 16, 0, 0);
-}
-
-// K3 with an LDS-DMA ring of depth D (4). A workgroup is K3W waves = K3W consecutive slot
-// groups of one 64-report block. Per call k, wave 0 streams c_k and wave 1 d_k (one
-// global_load_lds_dwordx4 each: 1 KiB, the block's 64 reports) into ring slot (k-1) % D, and every
-// wave its own PPW measurement elements; the coefficients are fetched once per K3W groups instead of
-// once per group, and D-1 calls stay in flight without holding VGPRs. One s_barrier per call: after it,
-// every wave's loads of call k have landed (each waited for its own with vmcnt) and every wave has
-// finished reading call k-1's slot, which the next issue overwrites. Every call runs in the ring: an
-// element past the share (the ragged last call) or of a padded slot is loaded from a zero constant, so
-// it adds nothing, and a padding group's wave only keeps the barriers.
-constexpr uint32_t K3W = 4;
-// LDS address of a __shared__ object
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-  return (uint32_t)(size_t)(const __attribute__((address_space(3))) uint8_t*)p;
-}
-// Four 16-byte LDS reads and one wait, in asm: the compiler's LDS-DMA wait tracking cannot tell which
-// ring slot a read touches and would otherwise drain every outstanding global_load_lds (vmcnt(0))
-// before each read, serialising the ring; the explicit wait_vmcnt + s_barrier order the reads here.
-__device__ __forceinline__ void lds_read4(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3, uint4& v0, uint4& v1,
-                                          uint4& v2, uint4& v3) {
-  asm volatile(
-      "ds_read_b128 %0, %4\n\t"
-      "ds_read_b128 %1, %5\n\t"
-      "ds_read_b128 %2, %6\n\t"
-      "ds_read_b128 %3, %7\n\t"
-      "s_waitcnt lgkmcnt(0)"
-      : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3)
-      : "v"(a0), "v"(a1), "v"(a2), "v"(a3)
-      : "memory");
-}
-// W: waves (slot groups) per workgroup
-// RING_ONLY (a measurement variant, instantiated only by tools/kernel_probe.hip): the ring, then a hash of
-// the column sums instead of the group finish (results wrong by design), to time the finish by difference.
-template <int PPW, bool HIST, bool LEADER, int D, int W = K3W, bool RING_ONLY = false>
-__global__ __launch_bounds__(64 * W, 4) void flp_psum_part_glds_kernel(Cfg c, Bufs b) {
-  static_assert(PPW == 2, "lds_read4 reads c, d and two measurement rows");
-  constexpr int ROWS = 2 + W * PPW;  // c_k, d_k, then x[wave][i]
-  __shared__ uint4 ring[D][ROWS][64];
-  const uint32_t NG = c.ngroups, NW = (NG + W - 1) / W;
-  const uint32_t bid = blockIdx.x, xcd = bid & 7u, q = bid >> 3;
-  const uint32_t wg = q % NW;
-  const uint64_t blk = (uint64_t)(q / NW) * 8 + xcd;
-  const uint64_t nblk = (b.n + 63) / 64;
-  if (blk >= nblk) return;  // uniform over the workgroup
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const uint32_t g = wg * W + wave;
-  const uint32_t C = c.calls, chunk = c.chunk, M = c.meas_len;
-  const uint32_t j0 = g * PPW;
-  const uint4* coefb = b.coef + il_idx(blk, c.ncoef, 0, lane);
-  const MeasView measb = meas_view(c, b, blk, lane);
-  const uint4* zero = b.consts + c.c_misc + MISC_ZERO;
-  const uint32_t kfw = C;  // every call (see above)
-  bool real[PPW];          // slot j0 + i exists (a padding group's wave has none)
-#pragma unroll
-  for (int i = 0; i < PPW; i++) real[i] = g < NG && j0 + i < chunk;
-
-  wacc26 ae[PPW], ao[PPW];
-  acc192 sx;
-#pragma unroll
-  for (int i = 0; i < PPW; i++) {
-    wacc_zero(ae[i]);
-    wacc_zero(ao[i]);
-  }
-  acc_zero(sx);
-  // The leader reads its explicit measurement share in place (report-major rows, Bufs::meas_rs): per call
-  // the workgroup needs the W*PPW = 8 consecutive elements (128 bytes) of its slots from each of the 64
-  // rows. Loaded per lane as the staged layout is (one 16-byte element of 64 rows per instruction) every
-  // instruction touches 64 lines for 16 bytes each, and the other waves' parts of those lines come back
-  // from HBM once L1/L2 have dropped them (4.0 MB of traffic per FixedPoint 16 x 10000 report against
-  // 2.67 MB for the helper's staged stream). Here instruction q (wave q / PPW) reads rows 8q..8q+7 whole:
-  // lane l = 8 pp + a takes row 8q + a, part p = pp ^ (q & 1), so eight lanes cover one row's 128 bytes.
-  // The part swap on odd q puts rows r and r + 8 in opposite halves of a 256-byte LDS bank window, so the
-  // consumers' ds_read_b128 (16 lanes per pass, lane = row) stay conflict-free.
-  const bool inpl = LEADER && !HIST && b.meas_rs != 0;
-  // loads of call k into ring slot (k - 1) % D
-  auto issue = [&](uint32_t k) {
-    const uint32_t sl = (k - 1) % D;
-    if (wave < 2) glds16(coefb + (uint64_t)(COEF_K + 2 * (k - 1) + wave) * IL, &ring[sl][wave][0]);
-    if (inpl) {
-      static_assert(W * PPW == 8, "one 128-byte row segment per report per call");
-#pragma unroll
-      for (int u = 0; u < PPW; u++) {
-        const uint32_t q = wave * PPW + u, a = lane & 7u, p = (lane >> 3) ^ (q & 1u);
-        const uint32_t slot = wg * (W * PPW) + p, e = (k - 1) * chunk + slot;
-        const uint64_t r0 = blk * 64 + 8 * q + a, r = r0 < b.n ? r0 : b.n - 1;
-        const uint4* src = slot < chunk && e < M ? reinterpret_cast<const uint4*>(b.meas_src + r * b.meas_rs) + e : zero;
-        glds16(src, &ring[sl][2 + q][0]);
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < PPW; i++) {
-        const uint32_t e = (k - 1) * chunk + j0 + i;
-        glds16(real[i] && e < M ? &measb[e] : zero, &ring[sl][2 + wave * PPW + i][0]);
-      }
-    }
-  };
-  // loads a wave issues per call: 1 (coefficient, waves 0/1) + PPW (measurement)
-  auto wait_call = [&](bool tail) {
-    if (tail) {
-      wait_vmcnt<0>();
-    } else if (wave < 2) {
-      wait_vmcnt<(D - 2) * (PPW + 1)>();
-    } else {
-      wait_vmcnt<(D - 2) * PPW>();
-    }
-  };
-  for (uint32_t k = 1; k < D && k <= kfw; k++) issue(k);
-  const uint32_t ring_base = lds_addr(&ring[0][0][lane]);
-  constexpr uint32_t SLOT_BYTES = ROWS * 64 * 16, ROW_BYTES = 64 * 16;
-  // this lane's measurement elements in a ring slot (relative to ring_base)
-  uint32_t xoff[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; i++) {
-    const uint32_t q = lane >> 3, p = wave * PPW + i;
-    xoff[i] = inpl ? (2 + q) * ROW_BYTES + ((8 * (p ^ (q & 1u)) + (lane & 7u)) * 16) - lane * 16
-                   : (2 + wave * PPW + i) * ROW_BYTES;
-  }
-#pragma unroll 1
-  for (uint32_t k = 1; k <= kfw; k++) {
-    wait_call(k + D - 2 > kfw);  // near the end fewer calls are in flight: wait for all
-    __builtin_amdgcn_s_barrier();
-    if (k + D - 1 <= kfw) issue(k + D - 1);
-    if (g < NG) {
-      const uint32_t a = ring_base + ((k - 1) % D) * SLOT_BYTES;
-      uint4 cv, dv, xv[PPW];
-      lds_read4(a, a + ROW_BYTES, a + xoff[0], a + xoff[1], cv, dv, xv[0], xv[1]);
-      const limbs26 ck = to_limbs26(u4_to_f(cv));
-      const limbs26 dk = to_limbs26(u4_to_f(dv));
-#pragma unroll
-      for (int i = 0; i < PPW; i++) {
-        const f128 x = u4_to_f(xv[i]);
-        const limbs26 xl = to_limbs26(x);
-        wacc_mac(ae[i], xl, dk);
-        wacc_mac(ao[i], xl, ck);
-        if (HIST) acc_add128(sx, x);
-      }
-      if ((k & 511u) == 0) {  // <= 5 * 512 limb products (< 2^52) per column
-#pragma unroll
-        for (int i = 0; i < PPW; i++) {
-          wacc_normalize(ae[i]);
-          wacc_normalize(ao[i]);
-        }
-      }
-    }
-  }
-  if (g >= NG) return;
-  if constexpr (RING_ONLY) {
-    uint64_t h = 0;
-#pragma unroll
-    for (int i = 0; i < PPW; i++)
-#pragma unroll
-      for (int q = 0; q < 9; q++) h ^= ae[i].col[q] ^ ao[i].col[q];
-    b.part[((blk * c.ngt + g) * 4) * IL + lane] = make_uint4((uint32_t)h, (uint32_t)(h >> 32), 0, 0);
-    return;
-  }
-  psum_part_finish<PPW, HIST, LEADER>(c, b, blk, g, lane, C, ae, ao, sx);
-}
-
-template <bool HIST, bool LEADER>
-__global__ __launch_bounds__(256) void flp_psum_final_kernel(Cfg c, Bufs b) {
-  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= b.n) return;
-  const uint64_t blk = r / 64;
-  const uint32_t lane = r % 64, NG = c.ngroups, A = 2 * c.chunk;
-  f128 P = make128(0, 0), V = make128(0, 0), G = make128(0, 0), SX = make128(0, 0);
-  const uint4* pp = b.part + (blk * c.ngt * 4) * IL + lane;
-  for (uint32_t g = 0; g < NG; g++, pp += 4 * IL) {
-    P = add128(P, u4_to_f(pp[0]));
-    V = add128(V, u4_to_f(pp[IL]));
-    G = add128(G, u4_to_f(pp[2 * IL]));
-    if (HIST) SX = add128(SX, u4_to_f(pp[3 * IL]));
-  }
-  f128 vh = V;
-  if (HIST) {
-    // v = jr1 * range_check + jr1^2 * (sum(x) - 1/2)
-    const f128 r2R = ld_il(b.coef, blk, c.ncoef, COEF_R2, lane);
-    const f128 half = u4_to_f(b.consts[c.c_misc + 1]);
-    f128 sc = sub128(SX, half);
-    vh = add128(mont128(V, r2R), mont128(sc, mont128(r2R, r2R)));
-  }
-  const uint32_t flags = b.flags[r];
-  if (LEADER) {  // verifier share [v, wires(t)..., G(t)]; wires were written by the part kernel
-    uint4* o = reinterpret_cast<uint4*>(b.lps_out + (uint64_t)c.lps_bytes * r);
-    o[0] = f_to_u4(vh);
-    o[A + 1] = f_to_u4(G);
-    b.verdicts[r] = (flags & (FLAG_INIT_FAIL | FLAG_INPUT_FAIL)) ? 1 : 0;
-    return;
-  }
-  bool df = (flags & FLAG_DFAIL) != 0;
-  f128 lv = ld_lead(b, c, r, 0, df), lg = ld_lead(b, c, r, A + 1, df);
-  uint32_t verdict = 0;
-  if (flags & FLAG_INIT_FAIL)
-    verdict = 1;
-  else if (df)
-    verdict = 2;
-  else {
-    f128 V0 = add128(vh, lv), VG = add128(G, lg);
-    if (!is_zero128(V0) || !eq128(P, mont128(VG, make128(1, 0))))
-      verdict = 3;
-    else if (flags & FLAG_NEXT_FAIL)
-      verdict = 4;
-  }
-  b.verdicts[r] = (uint8_t)verdict;
-}
-
-// Prio3FixedPointBoundedL2VecSum, gadget 1: ParallelSum(PolyEval(p), chunk1) over the decoded entries
-// y (= the output share, already truncated by K1), p(y) = 2^(2n-2) - 2^n y + y^2. One wave per
-// (64-report block, group of PPW slots). Wire j at t1 is the barycentric sum
-//   W_j = L1 (c'_0 s_j + sum_k c'_k y_{(k-1) chunk1 + j} + [short last chunk] c'_last 2^(n-2)),
-// the padding value 2^(n-2) being the share of the encoded 0.0 (2^(n-1) / num_shares). The group
-// also writes its share of v's gadget-1 part (sum_m g_m S1_m) and of G1(t1), and (helper) the sum of
-// p(V_j) over its slots, V_j = own + leader wire, in the R^-1 domain of the decide compare.
-template <int PPW, bool LEADER>
-__global__ __launch_bounds__(64, 4) void flp_norm_part_kernel(Cfg c, Bufs b) {
-  const uint32_t NG = c.ngroups1;
-  const uint32_t bid = blockIdx.x;
-  const uint32_t xcd = bid & 7u, q = bid >> 3;
-  const uint32_t g = q % NG;
-  const uint64_t blk = (uint64_t)(q / NG) * 8 + xcd;
-  const uint64_t nblk = (b.n + 63) / 64;
-  if (blk >= nblk) return;
-  const uint32_t lane = threadIdx.x;
-  const uint64_t r0 = blk * 64 + lane;
-  const uint64_t r = r0 < b.n ? r0 : b.n - 1;
-  const uint32_t NC = c.ncoef, C = c.calls1, ch = c.chunk1, E = c.out_len, B = c.coef1;
-  const uint32_t j0 = g * PPW;
-  const uint4* coefb = b.coef + il_idx(blk, NC, 0, lane);
-  const uint4* outb = b.outs + il_idx(blk, E, 0, lane);
-  wacc26 ao[PPW];
-#pragma unroll
-  for (int i = 0; i < PPW; i++) wacc_zero(ao[i]);
-#pragma unroll 1
-  for (uint32_t k = 1; k <= C; k++) {
-    const limbs26 ck = to_limbs26(u4_to_f(coefb[(B + G1_K + k - 1) * IL]));
-    const uint32_t nb = (k - 1) * ch + j0;
-#pragma unroll
-    for (int i = 0; i < PPW; i++) {
-      if (j0 + i < ch && nb + i < E) wacc_mac(ao[i], to_limbs26(u4_to_f(outb[(uint64_t)(nb + i) * IL])), ck);
-    }
-    if ((k & 511u) == 0) {
-#pragma unroll
-      for (int i = 0; i < PPW; i++) wacc_normalize(ao[i]);
-    }
-  }
-  const uint4* misc = b.consts + c.c_misc;
-  const f128 LR = u4_to_f(coefb[(B + G1_L) * IL]), c0R = u4_to_f(coefb[(B + G1_C0) * IL]);
-  const f128 tR = u4_to_f(coefb[(B + G1_T) * IL]);
-  const f128 cl = u4_to_f(coefb[(B + G1_K + C - 1) * IL]);  // c'_calls1 (the possibly short last call)
-  const f128 pad = mont128(u4_to_f(misc[6]), cl);          // 2^(n-2) c'_last, canonical
-  const f128 twon = u4_to_f(misc[4]), K = u4_to_f(misc[5]);
-  const uint32_t A0 = 2 * c.chunk;  // gadget 0's arity: gadget 1's wires follow it in the verifier
-  bool dfail = false;
-  f128 prod = make128(0, 0);
-#pragma unroll
-  for (int i = 0; i < PPW; i++) {
-    const uint32_t j = j0 + i;
-    if (j < ch) {
-      const f128 s = ld_il(b.proof, blk, c.proof_len, c.proof1_off + j, lane);
-      f128 O = mont128(wacc_reduce(ao[i]), make128(1, 0));  // sum_k c'_k y (canonical)
-      if ((C - 1) * ch + j >= E) O = add128(O, pad);
-      const f128 W = mont128(add128(mont128(s, c0R), O), LR);
-      if (LEADER) {
-        if (r0 < b.n) reinterpret_cast<uint4*>(b.lps_out + (uint64_t)c.lps_bytes * r)[A0 + 2 + j] = f_to_u4(W);
-      } else {
-        const f128 V = add128(W, ld_lead(b, c, r, A0 + 2 + j, dfail));
-        // p(V) R^-1 = V^2 R^-1 - 2^n V R^-1 + 2^(2n-2) R^-1
-        prod = add128(prod, add128(sub128(mont128(V, V), mont128(V, twon)), K));
-      }
-    }
-  }
-  const uint32_t GL = c.gpoly1_len;
-  const uint32_t per = (GL + NG - 1) / NG;
-  const uint32_t m0 = g * per, m1 = min(GL, m0 + per);
-  const uint4* Sm = b.consts + c.c_S1;
-  const uint32_t goff = c.proof1_off + ch;
-  f128 vpart = make128(0, 0), gpart = make128(0, 0);
-  if (m0 < m1) {
-    for (uint32_t m = m1; m-- > m0;) {
-      f128 gm = ld_il(b.proof, blk, c.proof_len, goff + m, lane);
-      vpart = add128(vpart, mont128(gm, u4_to_f(Sm[m])));
-      gpart = add128(mont128(gpart, tR), gm);
-    }
-    gpart = mont128(gpart, mpow(tR, m0));
-  }
-  uint4* pp = b.part + ((blk * c.ngt + c.ngroups + g) * 4) * IL + lane;
-  pp[0] = f_to_u4(prod);
-  pp[IL] = f_to_u4(vpart);
-  pp[2 * IL] = f_to_u4(gpart);
-  if (dfail && r0 < b.n) atomicOr(&b.flags[r0], FLAG_DFAIL);
-}
-
-// FixedPoint decide: v = jr1 * range_check + jr1^2 * (computed_norm - claimed_norm) where range_check
-// = sum_m g0_m S0_m and computed_norm = sum_m g1_m S1_m (the circuit's gadget outputs, as shares) and
-// claimed_norm = sum_b 2^b x[entries*n + b]; then both gadgets' G(wires(t_g)) == gadget_poly_g(t_g).
-template <bool LEADER>
-__global__ __launch_bounds__(256) void flp_fp_final_kernel(Cfg c, Bufs b) {
-  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= b.n) return;
-  const uint64_t blk = r / 64;
-  const uint32_t lane = r % 64, NG0 = c.ngroups, NG1 = c.ngroups1, A0 = 2 * c.chunk, A1 = c.chunk1;
-  f128 P0 = make128(0, 0), V0 = P0, G0 = P0, P1 = P0, V1 = P0, G1 = P0;
-  const uint4* pp = b.part + (blk * c.ngt * 4) * IL + lane;
-  for (uint32_t g = 0; g < NG0; g++, pp += 4 * IL) {
-    P0 = add128(P0, u4_to_f(pp[0]));
-    V0 = add128(V0, u4_to_f(pp[IL]));
-    G0 = add128(G0, u4_to_f(pp[2 * IL]));
-  }
-  for (uint32_t g = 0; g < NG1; g++, pp += 4 * IL) {
-    P1 = add128(P1, u4_to_f(pp[0]));
-    V1 = add128(V1, u4_to_f(pp[IL]));
-    G1 = add128(G1, u4_to_f(pp[2 * IL]));
-  }
-  // claimed squared norm: the trailing norm_bits measurement elements, LE bits
-  acc192 cn;
-  acc_zero(cn);
-  const uint32_t nb0 = c.trunc_len;
-  const MeasView mv = meas_view(c, b, blk, lane);
-  for (uint32_t i = 0; i < c.norm_bits; i++) trunc_add(cn, u4_to_f(mv[nb0 + i]), i);
-  const f128 claimed = acc_reduce(cn);
-  const f128 r2R = ld_il(b.coef, blk, c.ncoef, COEF_R2, lane);
-  const f128 vh = add128(mont128(V0, r2R), mont128(sub128(V1, claimed), mont128(r2R, r2R)));
-  const uint32_t flags = b.flags[r];
-  if (LEADER) {
-    uint4* o = reinterpret_cast<uint4*>(b.lps_out + (uint64_t)c.lps_bytes * r);
-    o[0] = f_to_u4(vh);
-    o[A0 + 1] = f_to_u4(G0);
-    o[A0 + 2 + A1] = f_to_u4(G1);
-    b.verdicts[r] = (flags & (FLAG_INIT_FAIL | FLAG_INPUT_FAIL)) ? 1 : 0;
-    return;
-  }
-  bool df = (flags & FLAG_DFAIL) != 0;
-  const f128 lv = ld_lead(b, c, r, 0, df), lg0 = ld_lead(b, c, r, A0 + 1, df), lg1 = ld_lead(b, c, r, A0 + 2 + A1, df);
-  uint32_t verdict = 0;
-  if (flags & FLAG_INIT_FAIL)
-    verdict = 1;
-  else if (df)
-    verdict = 2;
-  else {
-    const f128 one = make128(1, 0);
-    if (!is_zero128(add128(vh, lv)) || !eq128(P0, mont128(add128(G0, lg0), one)) ||
-        !eq128(P1, mont128(add128(G1, lg1), one)))
-      verdict = 3;
-    else if (flags & FLAG_NEXT_FAIL)
-      verdict = 4;
-  }
-  b.verdicts[r] = (uint8_t)verdict;
-}
-
-// ---------------------------------------------------------------------------- leader prepare_next
-// leader_continued on PingPongMessage::Finish{prep_msg} (aggregation_job_driver.rs:588-602):
-// prio prepare_next fails unless prep_msg equals the corrected joint-rand seed of the state.
-// peer (nullable): the helper's verdicts; a report the helper rejected (PrepareStepResult::Reject)
-// fails on the leader too (helper_step_failure, aggregation_job_driver.rs:646-660).
-__global__ __launch_bounds__(256) void leader_finish_kernel(Cfg c, Bufs b, const uint8_t* prep_msgs,
-                                                            const uint8_t* peer) {
-  const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= b.n) return;
-  if (b.verdicts[r] != 0) return;
-  if (peer && peer[r] != 0) {
-    b.verdicts[r] = 5;  // JX_HELPER_STEP_FAILURE
-    return;
-  }
-  if (c.jr_len == 0) return;
-  for (uint32_t o = 0; o < c.seed; o += 16) {
-    const uint4 m = *reinterpret_cast<const uint4*>(prep_msgs + c.seed * r + o);
-    const uint4 k = *reinterpret_cast<const uint4*>(b.msgs + c.seed * r + o);
-    if (m.x != k.x || m.y != k.y || m.z != k.z || m.w != k.w) b.verdicts[r] = 4;
-  }
-}
-
-// ---------------------------------------------------------------------------- K4: accumulate
-
-// selection + count + checksum. Grid-stride over reports (grid capped at SELECT_WGS
-// workgroups): each thread folds its reports' SHA-256(id) and selections in registers, the
-// workgroup reduces through LDS, and only one set of atomics per workgroup reaches L2 (one
-// set per wave serialised ~15k atomics on the same 40 bytes for 1M Count reports).
-__global__ __launch_bounds__(256) void select_kernel(AccArgs a, uint8_t* sel) {
-  const uint64_t padded = ((a.n + 63) / 64) * 64;
-  uint32_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t cnt = 0;
-  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < padded; r += (uint64_t)gridDim.x * blockDim.x) {
-    bool s = false;
-    if (r < a.n) s = a.verdicts[r] == 0 && (!a.mask || a.mask[r]) && (!a.seg || a.seg[r] == a.seg_id);
-    sel[r] = s;
-    if (s) {
-      uint32_t id[4], h[8];
-      load16(a.nonces + 16 * r, id);
-      sha256_16(id, h);
-#pragma unroll
-      for (int k = 0; k < 8; k++) d[k] ^= h[k];
-      cnt++;
-    }
-  }
-  // wave XOR / sum reduce, then across the 4 waves of the workgroup in LDS
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    uint32_t v = d[k];
-    for (int off = 32; off > 0; off >>= 1) v ^= __shfl_xor(v, off);
-    d[k] = v;
-  }
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-  __shared__ uint32_t red[4][9];
-  const uint32_t w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) red[w][k] = d[k];
-    red[w][8] = cnt;
-  }
-  __syncthreads();
-  if (threadIdx.x < 9) {
-    const uint32_t k = threadIdx.x;
-    uint32_t v = 0;
-    for (uint32_t q = 0; q < blockDim.x / 64; q++) v = k < 8 ? (v ^ red[q][k]) : (v + red[q][k]);
-    if (v) {
-      if (k < 8)
-        atomicXor(&a.checksum[k], v);
-      else
-        atomicAdd(a.count, (unsigned long long)v);
-    }
-  }
-}
-
-__global__ __launch_bounds__(256) void accumulate_kernel(AccArgs a, const uint8_t* sel) {
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= a.out_len) return;
-  const uint64_t nblk = (a.n + 63) / 64;
-  const uint64_t b0 = (uint64_t)blockIdx.y * a.blocks_per_chunk;
-  const uint64_t b1 = (b0 + a.blocks_per_chunk < nblk) ? b0 + a.blocks_per_chunk : nblk;
-  acc192 acc;
-  acc_zero(acc);
-  // four blocks' loads in flight per iteration (one dependent load per trip left HBM idle)
-  uint64_t bk = b0;
-  for (; bk + 4 <= b1; bk += 4) {
-    uint4 v[4];
-    uint8_t s4[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      s4[u] = sel[(bk + u) * 64 + lane];
-      v[u] = a.outs[il_idx(bk + u, a.out_len, i, lane)];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++)
-      if (s4[u]) acc_add128(acc, u4_to_f(v[u]));
-  }
-  for (; bk < b1; bk++) {
-    if (sel[bk * 64 + lane]) acc_add128(acc, u4_to_f(a.outs[il_idx(bk, a.out_len, i, lane)]));
-  }
-  // wave reduction of the 192-bit accumulators
-  for (int off = 32; off > 0; off >>= 1) {
-    uint64_t o0 = ((uint64_t)__shfl_xor((uint32_t)(acc.w0 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w0, off);
-    uint64_t o1 = ((uint64_t)__shfl_xor((uint32_t)(acc.w1 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w1, off);
-    uint64_t o2 = ((uint64_t)__shfl_xor((uint32_t)(acc.w2 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w2, off);
-    uint32_t cc = 0;
-    acc.w0 = addc64(acc.w0, o0, cc);
-    acc.w1 = addc64(acc.w1, o1, cc);
-    acc.w2 = acc.w2 + o2 + cc;
-  }
-  if (lane == 0) {
-    uint64_t* p = a.partials + ((uint64_t)blockIdx.y * a.out_len + i) * 3;
-    p[0] = acc.w0;
-    p[1] = acc.w1;
-    p[2] = acc.w2;
-  }
-}
-
-
-// one wave per output element: lanes stride over the report chunks' partial sums, then a
-// shuffle reduction (Count / Sum use up to 4096 chunks of a single element)
-__global__ __launch_bounds__(256) void reduce_partials_kernel(Cfg c, const uint64_t* partials, uint32_t nchunks,
-                                                              uint4* agg) {
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= c.out_len) return;
-  acc192 acc;
-  acc_zero(acc);
-  for (uint32_t q = lane; q < nchunks; q += 64) {
-    const uint64_t* p = partials + ((uint64_t)q * c.out_len + i) * 3;
-    uint32_t cc = 0;
-    acc.w0 = addc64(acc.w0, p[0], cc);
-    acc.w1 = addc64(acc.w1, p[1], cc);
-    acc.w2 = acc.w2 + p[2] + cc;
-  }
-  for (int off = 32; off > 0; off >>= 1) {
-    uint64_t o0 = ((uint64_t)__shfl_xor((uint32_t)(acc.w0 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w0, off);
-    uint64_t o1 = ((uint64_t)__shfl_xor((uint32_t)(acc.w1 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w1, off);
-    uint64_t o2 = ((uint64_t)__shfl_xor((uint32_t)(acc.w2 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w2, off);
-    uint32_t cc = 0;
-    acc.w0 = addc64(acc.w0, o0, cc);
-    acc.w1 = addc64(acc.w1, o1, cc);
-    acc.w2 = acc.w2 + o2 + cc;
-  }
-  if (lane != 0) return;
-  acc_add128(acc, u4_to_f(agg[i]));
-  if (c.fb == 8) {
-    uint64_t v = reduce192_p64(acc.w0, acc.w1, acc.w2);
-    agg[i] = make_uint4(lo32(v), hi32(v), 0, 0);
-  } else {
-    agg[i] = f_to_u4(acc_reduce(acc));
-  }
-}
-
-// K4 for a small batch (<= ACC_SMALL reports, e.g. one Janus aggregation job): one kernel instead of select +
-// accumulate + reduce_partials, nothing staged. Wave w of the grid sums output element w over the selected
-// reports and adds it into the aggregation; every thread also folds a grid-stride share of the selected
-// reports' SHA-256(id) and count, reduced per workgroup into one set of atomics (as select_kernel).
-__device__ __forceinline__ bool acc_selected(const AccArgs& a, uint64_t r) {
-  return a.verdicts[r] == 0 && (!a.mask || a.mask[r]) && (!a.seg || a.seg[r] == a.seg_id);
-}
-__global__ __launch_bounds__(256) void accumulate_small_kernel(Cfg c, AccArgs a, uint4* agg) {
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i < a.out_len) {
-    acc192 acc;
-    acc_zero(acc);
-    const uint64_t nblk = (a.n + 63) / 64;
-    for (uint64_t bk = 0; bk < nblk; bk++) {
-      const uint64_t r = bk * 64 + lane;
-      if (r < a.n && acc_selected(a, r)) acc_add128(acc, u4_to_f(a.outs[il_idx(bk, a.out_len, i, lane)]));
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      uint64_t o0 = ((uint64_t)__shfl_xor((uint32_t)(acc.w0 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w0, off);
-      uint64_t o1 = ((uint64_t)__shfl_xor((uint32_t)(acc.w1 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w1, off);
-      uint64_t o2 = ((uint64_t)__shfl_xor((uint32_t)(acc.w2 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w2, off);
-      uint32_t cc = 0;
-      acc.w0 = addc64(acc.w0, o0, cc);
-      acc.w1 = addc64(acc.w1, o1, cc);
-      acc.w2 = acc.w2 + o2 + cc;
-    }
-    if (lane == 0) {
-      acc_add128(acc, u4_to_f(agg[i]));
-      if (c.fb == 8) {
-        const uint64_t v = reduce192_p64(acc.w0, acc.w1, acc.w2);
-        agg[i] = make_uint4(lo32(v), hi32(v), 0, 0);
-      } else {
-        agg[i] = f_to_u4(acc_reduce(acc));
-      }
-    }
-  }
-  uint32_t d[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t cnt = 0;
-  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.n; r += (uint64_t)gridDim.x * blockDim.x) {
-    if (acc_selected(a, r)) {
-      uint32_t id[4], h[8];
-      load16(a.nonces + 16 * r, id);
-      sha256_16(id, h);
-#pragma unroll
-      for (int k = 0; k < 8; k++) d[k] ^= h[k];
-      cnt++;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    uint32_t v = d[k];
-    for (int off = 32; off > 0; off >>= 1) v ^= __shfl_xor(v, off);
-    d[k] = v;
-  }
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-  __shared__ uint32_t red[4][9];
-  const uint32_t w = threadIdx.x >> 6;
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) red[w][k] = d[k];
-    red[w][8] = cnt;
-  }
-  __syncthreads();
-  if (threadIdx.x < 9) {
-    const uint32_t k = threadIdx.x;
-    uint32_t v = 0;
-    for (uint32_t q = 0; q < 4; q++) v = k < 8 ? (v ^ red[q][k]) : (v + red[q][k]);
-    if (v) {
-      if (k < 8)
-        atomicXor(&a.checksum[k], v);
-      else
-        atomicAdd(a.count, (unsigned long long)v);
-    }
-  }
-}
-
-// K4 for up to ACC_MULTI_MAX small batches into one aggregation (the engine's deferred jx_accumulate calls,
-// flushed together: one launch instead of one per aggregation job). Workgroup i < out_len sums output element
-// i over every batch's finished reports, its wave w taking batches w, w + 4, ... (each 64-report block read
-// as one coalesced 1 KiB row), the four waves' 192-bit sums reduced through LDS and added into the
-// aggregation. Each workgroup past out_len folds one batch into the count and the ReportIdChecksum.
-__global__ __launch_bounds__(256) void accumulate_multi_kernel(Cfg c, AccMultiArgs a) {
-  const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (blockIdx.x < c.out_len) {
-    const uint32_t i = blockIdx.x;
-    acc192 acc;
-    acc_zero(acc);
-    for (uint32_t k = w; k < a.nb; k += 4) {
-      const AccDesc d = a.d[k];
-      const uint64_t nblk = (d.n + 63) / 64;
-      for (uint64_t bk = 0; bk < nblk; bk++) {
-        const uint64_t r = bk * 64 + lane;
-        if (r < d.n && d.verdicts[r] == 0) acc_add128(acc, u4_to_f(d.outs[il_idx(bk, c.out_len, i, lane)]));
-      }
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      uint64_t o0 = ((uint64_t)__shfl_xor((uint32_t)(acc.w0 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w0, off);
-      uint64_t o1 = ((uint64_t)__shfl_xor((uint32_t)(acc.w1 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w1, off);
-      uint64_t o2 = ((uint64_t)__shfl_xor((uint32_t)(acc.w2 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w2, off);
-      uint32_t cc = 0;
-      acc.w0 = addc64(acc.w0, o0, cc);
-      acc.w1 = addc64(acc.w1, o1, cc);
-      acc.w2 = acc.w2 + o2 + cc;
-    }
-    __shared__ uint64_t red[4][3];
-    if (lane == 0) {
-      red[w][0] = acc.w0;
-      red[w][1] = acc.w1;
-      red[w][2] = acc.w2;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      for (int q = 1; q < 4; q++) {
-        uint32_t cc = 0;
-        acc.w0 = addc64(acc.w0, red[q][0], cc);
-        acc.w1 = addc64(acc.w1, red[q][1], cc);
-        acc.w2 = acc.w2 + red[q][2] + cc;
-      }
-      acc_add128(acc, u4_to_f(a.agg[i]));
-      if (c.fb == 8) {
-        const uint64_t v = reduce192_p64(acc.w0, acc.w1, acc.w2);
-        a.agg[i] = make_uint4(lo32(v), hi32(v), 0, 0);
-      } else {
-        a.agg[i] = f_to_u4(acc_reduce(acc));
-      }
-    }
-    return;
-  }
-  const AccDesc d = a.d[blockIdx.x - c.out_len];
-  uint32_t h8[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t cnt = 0;
-  for (uint64_t r = threadIdx.x; r < d.n; r += 256) {
-    if (d.verdicts[r] == 0) {
-      uint32_t id[4], h[8];
-      load16(d.nonces + 16 * r, id);
-      sha256_16(id, h);
-#pragma unroll
-      for (int k = 0; k < 8; k++) h8[k] ^= h[k];
-      cnt++;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 8; k++) {
-    uint32_t v = h8[k];
-    for (int off = 32; off > 0; off >>= 1) v ^= __shfl_xor(v, off);
-    h8[k] = v;
-  }
-  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
-  __shared__ uint32_t redc[4][9];
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) redc[w][k] = h8[k];
-    redc[w][8] = cnt;
-  }
-  __syncthreads();
-  if (threadIdx.x < 9) {
-    const uint32_t k = threadIdx.x;
-    uint32_t v = 0;
-    for (uint32_t q = 0; q < 4; q++) v = k < 8 ? (v ^ redc[q][k]) : (v + redc[q][k]);
-    if (v) {
-      if (k < 8)
-        atomicXor(&a.checksum[k], v);
-      else
-        atomicAdd(a.count, (unsigned long long)v);
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------- K4 segmented
-// One pass for any number of batch aggregations: a device counting sort of the selected reports by
-// segment (LDS histograms, one global atomic per (workgroup, segment)), work items of <= L sorted
-// positions that never straddle a segment, per-item 192-bit partial sums, then one reduction per
-// (segment, element). The gathered loads are coalesced whenever a segment's reports are contiguous
-// (the usual case: Janus jobs group reports by batch), and cost 64-byte sectors per lane otherwise.
-__device__ __forceinline__ bool seg_sel(const SegArgs& a, uint64_t r, uint32_t& d) {
-  if (r >= a.n || a.verdicts[r] != 0 || (a.mask && !a.mask[r])) return false;
-  d = a.seg[r] - a.s0;
-  return d < a.ns;
-}
-
-__global__ __launch_bounds__(256) void seg_count_kernel(SegArgs a) {
-  __shared__ uint32_t h[SEG_MAX];
-  for (uint32_t t = threadIdx.x; t < a.ns; t += blockDim.x) h[t] = 0;
-  __syncthreads();
-  for (uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; r < a.n; r += (uint64_t)gridDim.x * blockDim.x) {
-    uint32_t d;
-    if (seg_sel(a, r, d)) atomicAdd(&h[d], 1u);
-  }
-  __syncthreads();
-  for (uint32_t t = threadIdx.x; t < a.ns; t += blockDim.x)
-    if (h[t]) atomicAdd(&a.cnt[t], h[t]);
-}
-
-// one workgroup: segment offsets, scatter cursors and the work-item table
-__global__ __launch_bounds__(1024) void seg_plan_kernel(SegArgs a) {
-  __shared__ uint32_t items_base;
-  if (threadIdx.x == 0) {
-    uint32_t pos = 0, w = 0;
-    for (uint32_t s = 0; s < a.ns; s++) {
-      const uint32_t c = a.cnt[s];
-      a.off[s] = pos;
-      a.cursor[s] = pos;
-      a.ioff[s] = w;
-      pos += c;
-      w += (c + a.L - 1) / a.L;
-    }
-    a.ioff[a.ns] = w;
-    a.nitems[0] = w;
-    a.nitems[1] = pos;  // selected reports = sorted positions in use
-    items_base = w;
-  }
-  __syncthreads();
-  for (uint32_t s = threadIdx.x; s < a.ns; s += blockDim.x) {
-    const uint32_t c = a.cnt[s], p0 = a.off[s];
-    uint32_t w = a.ioff[s];
-    for (uint32_t q = 0; q < c; q += a.L, w++) a.items[w] = make_uint4(s, p0 + q, p0 + min(c, q + a.L), 0);
-  }
-}
-
-__global__ __launch_bounds__(256) void seg_scatter_kernel(SegArgs a) {
-  __shared__ uint32_t h[SEG_MAX];
-  for (uint32_t t = threadIdx.x; t < a.ns; t += blockDim.x) h[t] = 0;
-  __syncthreads();
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  const uint64_t r_first = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (uint64_t r = r_first; r < a.n; r += stride) {
-    uint32_t d;
-    if (seg_sel(a, r, d)) atomicAdd(&h[d], 1u);
-  }
-  __syncthreads();
-  for (uint32_t t = threadIdx.x; t < a.ns; t += blockDim.x)
-    if (h[t]) h[t] = atomicAdd(&a.cursor[t], h[t]);  // this workgroup's range of segment t
-  __syncthreads();
-  for (uint64_t r = r_first; r < a.n; r += stride) {
-    uint32_t d;
-    if (seg_sel(a, r, d)) a.perm[atomicAdd(&h[d], 1u)] = (uint32_t)r;
-  }
-}
-
-__device__ __forceinline__ void acc192_wave_reduce(acc192& acc) {
-  for (int off = 32; off > 0; off >>= 1) {
-    uint64_t o0 = ((uint64_t)__shfl_xor((uint32_t)(acc.w0 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w0, off);
-    uint64_t o1 = ((uint64_t)__shfl_xor((uint32_t)(acc.w1 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w1, off);
-    uint64_t o2 = ((uint64_t)__shfl_xor((uint32_t)(acc.w2 >> 32), off) << 32) | __shfl_xor((uint32_t)acc.w2, off);
-    uint32_t cc = 0;
-    acc.w0 = addc64(acc.w0, o0, cc);
-    acc.w1 = addc64(acc.w1, o1, cc);
-    acc.w2 = acc.w2 + o2 + cc;
-  }
-}
-
-// wave per (output element, work item): lanes walk the item's sorted positions
-__global__ __launch_bounds__(256) void seg_accumulate_kernel(SegArgs a) {
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const uint32_t w = blockIdx.y;
-  if (i >= a.out_len || w >= *a.nitems) return;
-  const uint4 it = a.items[w];
-  acc192 acc;
-  acc_zero(acc);
-  uint32_t p = it.y + lane;
-  for (; p + 192 < it.z; p += 256) {  // four gathers in flight
-    uint4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-      const uint32_t r = a.perm[p + 64 * u];
-      v[u] = a.outs[il_idx(r >> 6, a.out_len, i, r & 63)];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; u++) acc_add128(acc, u4_to_f(v[u]));
-  }
-  for (; p < it.z; p += 64) {
-    const uint32_t r = a.perm[p];
-    acc_add128(acc, u4_to_f(a.outs[il_idx(r >> 6, a.out_len, i, r & 63)]));
-  }
-  acc192_wave_reduce(acc);
-  if (lane == 0) {
-    uint64_t* q = a.partials + ((uint64_t)w * a.out_len + i) * 3;
-    q[0] = acc.w0;
-    q[1] = acc.w1;
-    q[2] = acc.w2;
-  }
-}
-
-// ReportIdChecksum per segment: thread per sorted position; a wave whose 64 positions share a
-// segment (all but the boundary waves) folds them and issues one set of atomics
-__global__ __launch_bounds__(256) void seg_checksum_kernel(SegArgs a) {
-  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t total = a.nitems[1];
-  uint32_t h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  uint32_t d = 0xFFFFFFFFu;
-  if (p < total) {
-    const uint32_t r = a.perm[p];
-    uint32_t id[4];
-    load16(a.nonces + 16ull * r, id);
-    sha256_16(id, h);
-    d = a.seg[r] - a.s0;
-  }
-  const uint32_t d0 = __shfl(d, 0);
-  const bool uniform = __all(d == d0);
-  if (uniform) {
-    if (d0 == 0xFFFFFFFFu) return;
-#pragma unroll
-    for (int k = 0; k < 8; k++) {
-      uint32_t v = h[k];
-      for (int off = 32; off > 0; off >>= 1) v ^= __shfl_xor(v, off);
-      h[k] = v;
-    }
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-      for (int k = 0; k < 8; k++) atomicXor(&a.checksums[d0][k], h[k]);
-  } else if (d != 0xFFFFFFFFu) {
-#pragma unroll
-    for (int k = 0; k < 8; k++) atomicXor(&a.checksums[d][k], h[k]);
-  }
-}
-
-// wave per (output element, segment): sum the segment's work-item partials into its aggregate
-__global__ __launch_bounds__(256) void seg_reduce_kernel(SegArgs a) {
-  const uint32_t lane = threadIdx.x & 63;
-  const uint32_t i = blockIdx.x * 4 + (threadIdx.x >> 6);
-  const uint32_t s = blockIdx.y;
-  if (i >= a.out_len || s >= a.ns) return;
-  acc192 acc;
-  acc_zero(acc);
-  for (uint32_t w = a.ioff[s] + lane; w < a.ioff[s + 1]; w += 64) {
-    const uint64_t* q = a.partials + ((uint64_t)w * a.out_len + i) * 3;
-    uint32_t cc = 0;
-    acc.w0 = addc64(acc.w0, q[0], cc);
-    acc.w1 = addc64(acc.w1, q[1], cc);
-    acc.w2 = acc.w2 + q[2] + cc;
-  }
-  acc192_wave_reduce(acc);
-  if (lane != 0) return;
-  uint4* agg = a.aggs[s];
-  acc_add128(acc, u4_to_f(agg[i]));
-  if (a.fb == 8) {
-    const uint64_t v = reduce192_p64(acc.w0, acc.w1, acc.w2);
-    agg[i] = make_uint4(lo32(v), hi32(v), 0, 0);
-  } else {
-    agg[i] = f_to_u4(acc_reduce(acc));
-  }
-  if (i == 0) *a.counts[s] += a.cnt[s];
-}
-
-// multi-GPU combine: sum nparts encoded aggregate shares (LE bytes) mod p
-// err: set to 1 if an input element is not canonical (>= p): the host merge rejects such a share
-// (Field decode, janus_amd/distributed.py merge_aggregate_shares); the engine reports it on sync.
-__global__ void combine_kernel(Cfg c, const uint8_t* parts, uint32_t nparts, uint8_t* out, uint32_t* err) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= c.out_len) return;
-  const uint32_t fb = c.fb;
-  const uint64_t stride = (uint64_t)c.out_len * fb;
-  if (fb == 8) {
-    uint64_t s = 0;
-    for (uint32_t q = 0; q < nparts; q++) {
-      const uint8_t* p = parts + q * stride + (uint64_t)i * 8;
-      uint64_t v = 0;
-      for (int k = 7; k >= 0; k--) v = (v << 8) | p[k];
-      if (v >= P64) {
-        atomicOr(err, 1u);
-        v -= P64;
-      }
-      s = add64(s, v);
-    }
-    for (int k = 0; k < 8; k++) out[(uint64_t)i * 8 + k] = (uint8_t)(s >> (8 * k));
-  } else {
-    f128 s = make128(0, 0);
-    for (uint32_t q = 0; q < nparts; q++) {
-      const uint8_t* p = parts + q * stride + (uint64_t)i * 16;
-      uint64_t lo = 0, hi = 0;
-      for (int k = 7; k >= 0; k--) lo = (lo << 8) | p[k];
-      for (int k = 15; k >= 8; k--) hi = (hi << 8) | p[k];
-      f128 v = make128(lo, hi);
-      if (ge_p128(v)) {
-        atomicOr(err, 1u);
-        v = sub128(v, make128(P128_LO, P128_HI));
-      }
-      s = add128(s, v);
-    }
-    for (int k = 0; k < 8; k++) out[(uint64_t)i * 16 + k] = (uint8_t)(s.lo >> (8 * k));
-    for (int k = 0; k < 8; k++) out[(uint64_t)i * 16 + 8 + k] = (uint8_t)(s.hi >> (8 * k));
-  }
-}
-
-// shard record = encoded aggregate share || count (u64 LE) || checksum (32 B), see
-// janus_amd/distributed.py. Thread i < out_len writes element i; thread out_len the tail.
-// blockIdx.y = record: ns records from contiguous segment state (agg [ns][out_len], count [ns],
-// checksum [ns][8]) to ns back-to-back records
-__global__ void record_export_kernel(Cfg c, const uint4* agg, const unsigned long long* count,
-                                     const uint32_t* checksum, uint8_t* dst) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t fb = c.fb, y = blockIdx.y;
-  agg += (uint64_t)y * c.out_len;
-  count += y;
-  checksum += 8 * y;
-  dst += (uint64_t)y * (c.out_len * fb + 40u);
-  if (i < c.out_len) {
-    uint4 v = agg[i];
-    for (uint32_t k = 0; k < fb; k++) {
-      uint32_t w = k < 4 ? v.x : k < 8 ? v.y : k < 12 ? v.z : v.w;
-      dst[(uint64_t)i * fb + k] = (uint8_t)(w >> (8 * (k & 3)));
-    }
-  } else if (i == c.out_len) {
-    uint8_t* t = dst + (uint64_t)c.out_len * fb;
-    const unsigned long long n = *count;
-    for (int k = 0; k < 8; k++) t[k] = (uint8_t)(n >> (8 * k));
-    for (int k = 0; k < 32; k++) t[8 + k] = (uint8_t)(checksum[k >> 2] >> (8 * (k & 3)));
-  }
-}
-
-// merge nparts shard records (compute_aggregate_share, aggregate_share.rs:87-95):
-// mod-p sum of the aggregate shares, sum of the counts, XOR of the checksums.
-__global__ void record_combine_kernel(Cfg c, const uint8_t* parts, uint32_t nparts, uint8_t* out, uint32_t* err) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t fb = c.fb;
-  const uint64_t stride = (uint64_t)c.out_len * fb + 40;
-  if (i < c.out_len) {
-    if (fb == 8) {
-      uint64_t s = 0;
-      for (uint32_t q = 0; q < nparts; q++) {
-        const uint8_t* p = parts + q * stride + (uint64_t)i * 8;
-        uint64_t v = 0;
-        for (int k = 7; k >= 0; k--) v = (v << 8) | p[k];
-        if (v >= P64) {
-          atomicOr(err, 1u);
-          v -= P64;
-        }
-        s = add64(s, v);
-      }
-      for (int k = 0; k < 8; k++) out[(uint64_t)i * 8 + k] = (uint8_t)(s >> (8 * k));
-    } else {
-      f128 s = make128(0, 0);
-      for (uint32_t q = 0; q < nparts; q++) {
-        const uint8_t* p = parts + q * stride + (uint64_t)i * 16;
-        uint64_t lo = 0, hi = 0;
-        for (int k = 7; k >= 0; k--) lo = (lo << 8) | p[k];
-        for (int k = 15; k >= 8; k--) hi = (hi << 8) | p[k];
-        f128 v = make128(lo, hi);
-        if (ge_p128(v)) {
-          atomicOr(err, 1u);
-          v = sub128(v, make128(P128_LO, P128_HI));
-        }
-        s = add128(s, v);
-      }
-      for (int k = 0; k < 8; k++) out[(uint64_t)i * 16 + k] = (uint8_t)(s.lo >> (8 * k));
-      for (int k = 0; k < 8; k++) out[(uint64_t)i * 16 + 8 + k] = (uint8_t)(s.hi >> (8 * k));
-    }
-  } else if (i == c.out_len) {
-    const uint64_t tail = (uint64_t)c.out_len * fb;
-    uint64_t n = 0;
-    uint8_t cs[32];
-    for (int k = 0; k < 32; k++) cs[k] = 0;
-    for (uint32_t q = 0; q < nparts; q++) {
-      const uint8_t* p = parts + q * stride + tail;
-      uint64_t v = 0;
-      for (int k = 7; k >= 0; k--) v = (v << 8) | p[k];
-      n += v;
-      for (int k = 0; k < 32; k++) cs[k] ^= p[8 + k];
-    }
-    for (int k = 0; k < 8; k++) out[tail + k] = (uint8_t)(n >> (8 * k));
-    for (int k = 0; k < 32; k++) out[tail + 8 + k] = cs[k];
-  }
-}
-
-// interleaved output shares -> [r][i] LE bytes
-__global__ void transpose_out_kernel(Cfg c, const uint4* outs, uint64_t n, uint8_t* dst) {
-  const uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t r = t / c.out_len;
-  const uint32_t i = t % c.out_len;
-  if (r >= n) return;
-  uint4 v = outs[il_idx(r / 64, c.out_len, i, r % 64)];
-  if (c.fb == 8) {
-    *reinterpret_cast<uint2*>(dst + t * 8) = make_uint2(v.x, v.y);
-  } else {
-    *reinterpret_cast<uint4*>(dst + t * 16) = v;
-  }
-}
-
-// Coalesced launches (jx_coalesce.cpp): copy job j's slice [first, first + n) of the launch's staging into
-// the job's own resident batch, so every job keeps an independent batch (interleaved output shares
-// re-based to lane 0, verdicts, prep messages / leader seeds, report ids). blockIdx.y = job; the threads of
-// a job stride over its destination elements (coalesced writes, reads shifted by first % 64).
-__global__ __launch_bounds__(256) void scatter_jobs_kernel(Cfg c, const JobSlice* jobs, const uint4* outs,
-                                                           const uint8_t* verdicts, const uint8_t* msgs,
-                                                           const uint8_t* nonces) {
-  const JobSlice j = jobs[blockIdx.y];
-  const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-  const uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const uint64_t nblk = (j.n + 63) / 64;
-  const uint64_t total = nblk * c.out_len * 64;
-  for (uint64_t t = t0; t < total; t += stride) {
-    const uint64_t blk = t / ((uint64_t)c.out_len * 64);
-    const uint32_t rem = (uint32_t)(t % ((uint64_t)c.out_len * 64));
-    const uint32_t e = rem / 64, l = rem % 64;
-    const uint64_t i = blk * 64 + l;
-    if (i >= j.n) continue;
-    const uint64_t r = j.first + i;
-    j.outs[t] = outs[il_idx(r / 64, c.out_len, e, r % 64)];
-  }
-  const uint32_t mb = c.seed;  // prep message / seed bytes: 16 or 32
-  for (uint64_t i = t0; i < j.n; i += stride) {
-    const uint64_t r = j.first + i;
-    j.verdicts[i] = verdicts[r];
-    const uint4* sm = reinterpret_cast<const uint4*>(msgs + r * mb);
-    uint4* dm = reinterpret_cast<uint4*>(j.msgs + i * mb);
-    dm[0] = sm[0];
-    if (mb == 32) dm[1] = sm[1];
-    reinterpret_cast<uint4*>(j.nonces)[i] = reinterpret_cast<const uint4*>(nonces)[r];
-  }
-}
-
-__global__ void agg_encode_kernel(Cfg c, const uint4* agg, uint8_t* dst) {
-  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= c.out_len) return;
-  uint4 v = agg[i];
-  if (c.fb == 8)
-    *reinterpret_cast<uint2*>(dst + (uint64_t)i * 8) = make_uint2(v.x, v.y);
-  else
-    *reinterpret_cast<uint4*>(dst + (uint64_t)i * 16) = v;
-}
-
 // ---------------------------------------------------------------------------- launchers
-
-static inline uint32_t nblk_of(uint64_t n) { return (uint32_t)((n + 63) / 64); }
 
 hipError_t launch_count(const Cfg& c, const Bufs& b, hipStream_t s) {
   uint32_t nb = nblk_of(b.n);
@@ -3438,7 +1983,8 @@ hipError_t launch_count(const Cfg& c, const Bufs& b, hipStream_t s) {
     hipLaunchKernelGGL(count_kernel<false>, dim3((nb * 64 + 255) / 256), dim3(256), 0, s, c, b);
   return hipGetLastError();
 }
-hipError_t launch_xof(const Cfg& c, const Bufs& b, hipStream_t s) {
+// k1: from k1_plan, which never names the word or pair kernels (bits <= 32) for a wide instance
+hipError_t launch_xof(const Cfg& c, const Bufs& b, K1Launch k1, hipStream_t s) {
   uint32_t nb = nblk_of(b.n);
   const dim3 grid((nb + K1_WAVES - 1) / K1_WAVES), block(64 * K1_WAVES);
   const bool wide = c.bits > 32 && (c.algo == ALGO_SUM || c.algo == ALGO_SUMVEC);
@@ -3450,24 +1996,23 @@ hipError_t launch_xof(const Cfg& c, const Bufs& b, hipStream_t s) {
     hipLaunchKernelGGL((xof_leader_kernel<false, true>), grid, block, 0, s, c, b);
   else if (b.leader)
     hipLaunchKernelGGL((xof_leader_kernel<false, false>), grid, block, 0, s, c, b);
-  else if (b.k1_split == 7 && !wide) {  // a word per lane: one report per wave, then the truncation
+  else if (k1.kernel == K1_WORDS) {  // a word per lane: one report per wave, then the truncation
     hipLaunchKernelGGL(xof_words_kernel, dim3((uint32_t)((b.n + KW_WAVES - 1) / KW_WAVES)), dim3(64 * KW_WAVES), 0, s, c, b);
     const uint32_t nout = c.out_is_meas ? 0u : (c.trunc_len < c.meas_len ? c.trunc_len : c.meas_len) / c.bits;
     if (nout) {
       const uint64_t threads = (uint64_t)nblk_of(b.n) * 64 * nout;
       hipLaunchKernelGGL(trunc_kernel, dim3((uint32_t)((threads + 255) / 256)), dim3(256), 0, s, c, b, nout);
     }
-  } else if (b.k1_split == 8 && !wide)  // lane pairs, unrolled rounds (<= one pair-wave per SIMD)
-    hipLaunchKernelGGL(xof_pairs_kernel<true>, dim3((4 * nb + K1_WAVES - 1) / K1_WAVES), block, b.k1_pairs_lds, s, c, b);
-  else if (b.k1_split == 6 && !wide)  // lane pairs: 16 reports per wave
-    hipLaunchKernelGGL(xof_pairs_kernel<false>, dim3((4 * nb + K1_WAVES - 1) / K1_WAVES), block, b.k1_pairs_lds, s, c,
-                       b);
-  else if (b.k1_split == 3) {  // lane-split: 32 reports per wave
+  } else if (k1.kernel == K1_PAIRS_UNROLLED)  // lane pairs, unrolled rounds (<= one pair-wave per SIMD)
+    hipLaunchKernelGGL(xof_pairs_kernel<true>, dim3((4 * nb + K1_WAVES - 1) / K1_WAVES), block, k1.lds, s, c, b);
+  else if (k1.kernel == K1_PAIRS)  // lane pairs: 16 reports per wave
+    hipLaunchKernelGGL(xof_pairs_kernel<false>, dim3((4 * nb + K1_WAVES - 1) / K1_WAVES), block, k1.lds, s, c, b);
+  else if (k1.kernel == K1_LANES) {  // lane-split: 32 reports per wave
     const dim3 g2((2 * nb + K1_WAVES - 1) / K1_WAVES);
     if (wide)
-      hipLaunchKernelGGL((xof_lanes_kernel<true>), g2, block, b.k1_lds, s, c, b);
+      hipLaunchKernelGGL((xof_lanes_kernel<true>), g2, block, k1.lds, s, c, b);
     else
-      hipLaunchKernelGGL((xof_lanes_kernel<false>), g2, block, b.k1_lds, s, c, b);
+      hipLaunchKernelGGL((xof_lanes_kernel<false>), g2, block, k1.lds, s, c, b);
   } else if (wide)
     hipLaunchKernelGGL((xof_kernel<true>), grid, block, 0, s, c, b);
   else
@@ -3498,18 +2043,11 @@ Bufs bufs_tail(const Cfg& c, const Bufs& b, uint64_t S) {
   return t;
 }
 
-// Dynamic LDS that caps the lane-split kernel at `wgs_per_cu` workgroups per CU (0: no cap).
-uint32_t lanes_lds_bytes(uint32_t wgs_per_cu) {
-  if (wgs_per_cu == 0) return 0;
-  constexpr uint32_t LDS_PER_CU = 160u << 10;
-  return (LDS_PER_CU / (wgs_per_cu + 1) + 1024u) / 1024u * 1024u;
-}
-
 // Reports that occupy every K1 wave slot of the device exactly once: CUs x resident
 // workgroups per CU (from the kernel's register/LDS footprint) x 64 reports per wave. K1 waves
 // all run the same length, so a launch runs in ceil(reports / this) equal "rounds"; the
 // engine sizes its launches in whole rounds so only the last launch has a partial one.
-uint64_t k1_round_reports(const Cfg& c, int device, uint32_t k1_split) {
+uint64_t k1_round_reports(const Cfg& c, int device) {
   if (c.algo == ALGO_SUMVEC_F64_MULTIPROOF) return mp_k1_round_reports(device);
   int cus = 0, wgs = 0;
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || cus <= 0) return 0;
@@ -3518,258 +2056,14 @@ uint64_t k1_round_reports(const Cfg& c, int device, uint32_t k1_split) {
   uint32_t per_wg = threads;  // reports per workgroup
   if (c.algo == ALGO_COUNT) {
     st = hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, count_kernel<false>, threads, 0);
-  } else if (k1_split == 3) {
-    st = hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, xof_lanes_kernel<false>, threads, lanes_lds_bytes(2));
-    per_wg = threads / 2;
-  } else if (k1_split == 6) {
-    st = hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, xof_pairs_kernel<false>, threads, 0);
-    per_wg = threads / 4;
   } else {
     st = hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgs, xof_kernel<false>, threads, 0);
   }
   if (st != hipSuccess || wgs <= 0) return 0;
   return (uint64_t)cus * (uint64_t)wgs * per_wg;
 }
-hipError_t launch_leader_finish(const Cfg& c, const Bufs& b, const uint8_t* prep_msgs, const uint8_t* peer,
-                                hipStream_t s) {
-  hipLaunchKernelGGL(leader_finish_kernel, dim3((uint32_t)((b.n + 255) / 256)), dim3(256), 0, s, c, b, prep_msgs,
-                     peer);
-  return hipGetLastError();
-}
 hipError_t launch_xof_slow(const Cfg& c, const Bufs& b, hipStream_t s) {
   hipLaunchKernelGGL(xof_slow_kernel, dim3((uint32_t)((b.n + 63) / 64)), dim3(64), 0, s, c, b);
-  return hipGetLastError();
-}
-
-// Slots per FLP group. Each slot holds two 9-column wide accumulators (36 VGPRs); PPW = 2
-// (152 VGPRs, 3 waves/SIMD) measured fastest on MI355X for SumVec(8x1000/88): K3 11.8 ms vs
-// 13.6 (PPW 1) and 12.5 (PPW 4, spills) per 312,500 reports. PPW = 1 only when it wastes
-// fewer padded slot-lanes (chunk_length 1). (4 and 8 slots per wave spill, 0.3-4 KB/lane: removed.)
-int psum_ppw(uint32_t chunk) {
-  const int cands[] = {2, 1};
-  int best = 2, best_cost = 1 << 30;
-  for (int p : cands) {
-    int ng = (int)((chunk + p - 1) / p);
-    int cost = ng * p + 3 * ng;
-    if (cost < best_cost) {
-      best = p;
-      best_cost = cost;
-    }
-  }
-  return best;
-}
-
-// K3 phase 1: the depth-4 LDS-DMA ring (K3W slot groups per workgroup) for PPW = 2; the per-wave
-// register-prefetch kernel for PPW = 1 (chunk_length 1). Measured and removed:
-// 2 / 3 calls of register prefetch, 3-waves/SIMD builds, a depth-3 ring, 8 groups per workgroup.
-template <int PPW, bool HIST, bool LEADER>
-static void launch_psum_part(const Cfg& c, const Bufs& b, hipStream_t s, uint32_t grid) {
-  if constexpr (PPW == 2) {
-    const uint32_t g2 = grid / c.ngroups * ((c.ngroups + K3W - 1) / K3W);
-    hipLaunchKernelGGL((flp_psum_part_glds_kernel<PPW, HIST, LEADER, 4>), dim3(g2), dim3(64 * K3W), 0, s, c, b);
-  } else {
-    hipLaunchKernelGGL((flp_psum_part_kernel<PPW, HIST, LEADER>), dim3(grid), dim3(64), 0, s, c, b);
-  }
-}
-template <int PPW, bool HIST, bool LEADER>
-static void launch_psum_r(const Cfg& c, const Bufs& b, hipStream_t s) {
-  const uint32_t nb = nblk_of(b.n);
-  launch_psum_part<PPW, HIST, LEADER>(c, b, s, ((nb + 7) / 8) * 8 * c.ngroups);
-  hipLaunchKernelGGL((flp_psum_final_kernel<HIST, LEADER>), dim3((uint32_t)((b.n + 255) / 256)), dim3(256), 0, s,
-                     c, b);
-}
-template <int PPW>
-static hipError_t launch_psum_t(const Cfg& c, const Bufs& b, hipStream_t s) {
-  const bool hist = c.algo == ALGO_HISTOGRAM;
-  if (hist && b.leader)
-    launch_psum_r<PPW, true, true>(c, b, s);
-  else if (hist)
-    launch_psum_r<PPW, true, false>(c, b, s);
-  else if (b.leader)
-    launch_psum_r<PPW, false, true>(c, b, s);
-  else
-    launch_psum_r<PPW, false, false>(c, b, s);
-  return hipGetLastError();
-}
-
-template <int PPW, bool LEADER>
-static void launch_fp_r(const Cfg& c, const Bufs& b, hipStream_t s) {
-  const uint32_t nb = nblk_of(b.n);
-  launch_psum_part<PPW, false, LEADER>(c, b, s, ((nb + 7) / 8) * 8 * c.ngroups);
-  hipLaunchKernelGGL((flp_norm_part_kernel<2, LEADER>), dim3(((nb + 7) / 8) * 8 * c.ngroups1), dim3(64), 0, s, c,
-                     b);
-  hipLaunchKernelGGL((flp_fp_final_kernel<LEADER>), dim3((uint32_t)((b.n + 255) / 256)), dim3(256), 0, s, c, b);
-}
-
-hipError_t launch_flp(const Cfg& c, const Bufs& b, hipStream_t s) {
-  if (c.algo == ALGO_FIXEDPOINT_L2) {
-    if (c.ppw == 2) {
-      if (b.leader)
-        launch_fp_r<2, true>(c, b, s);
-      else
-        launch_fp_r<2, false>(c, b, s);
-    } else if (c.ppw == 1) {
-      if (b.leader)
-        launch_fp_r<1, true>(c, b, s);
-      else
-        launch_fp_r<1, false>(c, b, s);
-    } else {
-      return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
-  }
-  if (c.algo == ALGO_SUM) {
-    uint32_t nb = nblk_of(b.n);
-    if (b.leader)
-      hipLaunchKernelGGL(flp_sum_kernel<true>, dim3((nb + 3) / 4), dim3(256), 0, s, c, b);
-    else
-      hipLaunchKernelGGL(flp_sum_kernel<false>, dim3((nb + 3) / 4), dim3(256), 0, s, c, b);
-    return hipGetLastError();
-  }
-  switch (c.ppw) {
-    case 2:
-      return launch_psum_t<2>(c, b, s);
-    case 1:
-      return launch_psum_t<1>(c, b, s);
-    default:
-      return hipErrorInvalidValue;
-  }
-}
-
-hipError_t launch_accumulate(const Cfg& c, const AccArgs& a, uint4* agg, hipStream_t s) {
-  // sel lives at the tail of the partials allocation (see engine)
-  uint8_t* sel = reinterpret_cast<uint8_t*>(a.partials + (size_t)a.nchunks * c.out_len * 3);
-  uint64_t nthreads = ((a.n + 63) / 64) * 64;
-  uint64_t swg = (nthreads + 255) / 256;
-  if (swg > SELECT_WGS) swg = SELECT_WGS;
-  hipLaunchKernelGGL(select_kernel, dim3((uint32_t)swg), dim3(256), 0, s, a, sel);
-  hipLaunchKernelGGL(accumulate_kernel, dim3((c.out_len + 3) / 4, a.nchunks), dim3(256), 0, s, a,
-                     (const uint8_t*)sel);
-  hipLaunchKernelGGL(reduce_partials_kernel, dim3((c.out_len + 3) / 4), dim3(256), 0, s, c,
-                     (const uint64_t*)a.partials, a.nchunks, agg);
-  return hipGetLastError();
-}
-
-hipError_t launch_accumulate_small(const Cfg& c, const AccArgs& a, uint4* agg, hipStream_t s) {
-  hipLaunchKernelGGL(accumulate_small_kernel, dim3((c.out_len + 3) / 4), dim3(256), 0, s, c, a, agg);
-  return hipGetLastError();
-}
-
-__global__ __launch_bounds__(64) void host_signal_kernel(uint32_t* flag, uint32_t seq) {
-  if (threadIdx.x == 0) __hip_atomic_store(flag + threadIdx.x, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-hipError_t launch_host_signal(uint32_t* flag, uint32_t seq, hipStream_t s) {
-  hipLaunchKernelGGL(host_signal_kernel, dim3(1), dim3(64), 0, s, flag, seq);
-  return hipGetLastError();
-}
-
-__global__ __launch_bounds__(256) void copy_regions_kernel(CopyArgs a) {
-  const CopyRegion g = a.r[blockIdx.y];
-  const uint64_t step = (uint64_t)gridDim.x * blockDim.x;
-  const uint64_t t0 = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const bool vec = ((g.width | g.dst_stride | g.src_stride | (uint64_t)(uintptr_t)g.dst | (uint64_t)(uintptr_t)g.src) & 15) == 0;
-  if (vec) {
-    const uint64_t cpr = g.width / 16, total = cpr * g.rows;
-    for (uint64_t t = t0; t < total; t += step) {
-      const uint64_t row = t / cpr, ch = t - row * cpr;
-      *reinterpret_cast<uint4*>(g.dst + row * g.dst_stride + 16 * ch) =
-          *reinterpret_cast<const uint4*>(g.src + row * g.src_stride + 16 * ch);
-    }
-  } else if (g.rows == 1 && (((uint64_t)(uintptr_t)g.dst | (uint64_t)(uintptr_t)g.src) & 15) == 0) {
-    // one flat run of a length that is not a multiple of 16 (a launch's verdicts, open statuses): 16-byte vectors
-    // and a byte tail, not one PCIe write per byte
-    const uint64_t nv = g.width / 16;
-    for (uint64_t t = t0; t < nv; t += step)
-      reinterpret_cast<uint4*>(g.dst)[t] = reinterpret_cast<const uint4*>(g.src)[t];
-    if (t0 < g.width - 16 * nv) g.dst[16 * nv + t0] = g.src[16 * nv + t0];
-  } else {
-    const uint64_t total = g.width * g.rows;
-    for (uint64_t t = t0; t < total; t += step) {
-      const uint64_t row = t / g.width, bt = t - row * g.width;
-      g.dst[row * g.dst_stride + bt] = g.src[row * g.src_stride + bt];
-    }
-  }
-}
-hipError_t launch_copy_regions(const CopyArgs& a, hipStream_t s) {
-  if (a.nr == 0) return hipSuccess;
-  if (a.nr > COPY_MAX_REGIONS) return hipErrorInvalidValue;
-  uint64_t most = 0;
-  for (uint32_t k = 0; k < a.nr; k++) {
-    const CopyRegion& g = a.r[k];
-    const bool vec = ((g.width | g.dst_stride | g.src_stride | (uint64_t)(uintptr_t)g.dst | (uint64_t)(uintptr_t)g.src) & 15) == 0;
-    const bool flat16 = g.rows == 1 && (((uint64_t)(uintptr_t)g.dst | (uint64_t)(uintptr_t)g.src) & 15) == 0;
-    const uint64_t items = vec ? g.width / 16 * g.rows : flat16 ? g.width / 16 + 16 : g.width * g.rows;
-    if (items > most) most = items;
-  }
-  // PCIe-bound: a few hundred waves keep enough reads in flight, and a big launch's K1 keeps the rest of the
-  // SIMDs (JX_COPY_WGS overrides the cap for measurement)
-  static const uint64_t cap = [] {
-    const char* e = getenv("JX_COPY_WGS");
-    const long v = e ? atol(e) : 0;
-    return v >= 1 && v <= 4096 ? (uint64_t)v : (uint64_t)64;
-  }();
-  uint64_t gx = (most + 255) / 256;
-  if (gx > cap) gx = cap;
-  if (gx == 0) gx = 1;
-  hipLaunchKernelGGL(copy_regions_kernel, dim3((uint32_t)gx, a.nr), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_accumulate_multi(const Cfg& c, const AccMultiArgs& a, hipStream_t s) {
-  if (a.nb == 0) return hipSuccess;
-  if (a.nb > ACC_MULTI_MAX) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(accumulate_multi_kernel, dim3(c.out_len + a.nb), dim3(256), 0, s, c, a);
-  return hipGetLastError();
-}
-
-// grid: workgroups of the count/scatter passes (the same for both: each workgroup re-walks its reports)
-hipError_t launch_accumulate_segmented(const Cfg& c, const SegArgs& a, uint32_t grid, hipStream_t s) {
-  (void)c;
-  hipLaunchKernelGGL(seg_count_kernel, dim3(grid), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(seg_plan_kernel, dim3(1), dim3(1024), 0, s, a);
-  hipLaunchKernelGGL(seg_scatter_kernel, dim3(grid), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(seg_accumulate_kernel, dim3((a.out_len + 3) / 4, a.wmax), dim3(256), 0, s, a);
-  // one thread per possible sorted position (n bounds the selected count); the rest return at once
-  hipLaunchKernelGGL(seg_checksum_kernel, dim3((uint32_t)((a.n + 255) / 256)), dim3(256), 0, s, a);
-  hipLaunchKernelGGL(seg_reduce_kernel, dim3((a.out_len + 3) / 4, a.ns), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t launch_combine(const Cfg& c, const uint8_t* parts, uint32_t nparts, uint8_t* out, uint32_t* err,
-                          hipStream_t s) {
-  hipLaunchKernelGGL(combine_kernel, dim3((c.out_len + 255) / 256), dim3(256), 0, s, c, parts, nparts, out, err);
-  return hipGetLastError();
-}
-hipError_t launch_record_export(const Cfg& c, const uint4* agg, const unsigned long long* count,
-                                const uint32_t* checksum, uint8_t* dst, hipStream_t s, uint32_t ns) {
-  hipLaunchKernelGGL(record_export_kernel, dim3((c.out_len + 1 + 255) / 256, ns), dim3(256), 0, s, c, agg, count,
-                     checksum, dst);
-  return hipGetLastError();
-}
-hipError_t launch_record_combine(const Cfg& c, const uint8_t* parts, uint32_t nparts, uint8_t* out, uint32_t* err,
-                                 hipStream_t s) {
-  hipLaunchKernelGGL(record_combine_kernel, dim3((c.out_len + 1 + 255) / 256), dim3(256), 0, s, c, parts, nparts,
-                     out, err);
-  return hipGetLastError();
-}
-hipError_t launch_transpose_out(const Cfg& c, const uint4* outs, uint64_t n, uint8_t* dst, hipStream_t s) {
-  uint64_t t = n * c.out_len;
-  hipLaunchKernelGGL(transpose_out_kernel, dim3((uint32_t)((t + 255) / 256)), dim3(256), 0, s, c, outs, n, dst);
-  return hipGetLastError();
-}
-hipError_t launch_scatter_jobs(const Cfg& c, const JobSlice* d_jobs, uint32_t njobs, uint64_t max_job_reports,
-                               const uint4* outs, const uint8_t* verdicts, const uint8_t* msgs, const uint8_t* nonces,
-                               hipStream_t s) {
-  if (njobs == 0) return hipSuccess;
-  const uint64_t elems = (max_job_reports + 63) / 64 * 64 * c.out_len;
-  uint64_t gx = (elems + 255) / 256;
-  if (gx > 1024) gx = 1024;
-  hipLaunchKernelGGL(scatter_jobs_kernel, dim3((uint32_t)gx, njobs), dim3(256), 0, s, c, d_jobs, outs, verdicts, msgs,
-                     nonces);
-  return hipGetLastError();
-}
-hipError_t launch_agg_encode(const Cfg& c, const uint4* agg, uint8_t* dst, hipStream_t s) {
-  hipLaunchKernelGGL(agg_encode_kernel, dim3((c.out_len + 255) / 256), dim3(256), 0, s, c, agg, dst);
   return hipGetLastError();
 }
 

@@ -118,13 +118,6 @@ __device__ __forceinline__ void load32_u2(const uint8_t* p, uint32_t w[8]) {
     w[2 * i + 1] = v.y;
   }
 }
-__device__ __forceinline__ void load16(const uint8_t* p, uint32_t w[4]) {
-  const uint4 v = *reinterpret_cast<const uint4*>(p);
-  w[0] = v.x;
-  w[1] = v.y;
-  w[2] = v.z;
-  w[3] = v.w;
-}
 
 // ---------------------------------------------------------------------------- XofHmacSha256Aes128
 // init(seed, dst): HMAC key = seed; message = byte(len(dst)) || dst || binder...
@@ -986,8 +979,6 @@ __global__ __launch_bounds__(256) void mp_flp_final_kernel(Cfg c, Bufs b) {
   }
   b.verdicts[r] = (uint8_t)verdict;
 }
-
-inline uint32_t nblk_of(uint64_t n) { return (uint32_t)((n + 63) / 64); }
 
 template <int PPW, bool LEADER>
 void launch_mp_flp_r(const Cfg& c, const Bufs& b, hipStream_t s) {

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the batched HPKE open under DHKEM(P-256, HKDF-SHA256) on one MI355X (janus_amd/csrc/jx_hpke.hip:
+"""Cost of the batched HPKE open under DHKEM(P-256, HKDF-SHA256) on one MI355X (janus_amd/csrc/jx_hpke_p256.hip:
 hpke_open_p256_kernel) against the X25519 default suite (hpke_open_kernel), and the run-to-run spread of the
 X25519 default suite on another build of the library (the parent commit's), which is what the unchanged path has
 to stay within.

@@ -20,7 +20,7 @@ import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, "janus_amd", "csrc", "jx_kernels.hip")
+SRC = os.path.join(ROOT, "janus_amd", "csrc", "jx_flp.hip")
 
 
 def asm() -> list[str]:

@@ -22,6 +22,7 @@
 
 #include "../janus_amd/csrc/jx_engine_internal.h"
 #include "../janus_amd/csrc/jx_kernels.hip"
+#include "../janus_amd/csrc/jx_flp.hip"
 
 #define CK(x)                                                                 \
   do {                                                                        \
@@ -92,12 +93,10 @@ static int sweep() {
   const uint64_t sizes[] = {16, 100, 256, 512, 1024, 2048, 3072, 4096, 6400, 8192, 16384, 32768};
   for (uint64_t n : sizes) {
     b.n = n;
-    b.k1_split = 8;  // the lane pairs as the engine picks them below one pair-wave per SIMD (unrolled rounds)
-    const double pairs = time_ms([&] { CK(jx::launch_xof(c, b, s)); }, 3, s);
-    b.k1_split = 6;
-    const double pairs_loop = time_ms([&] { CK(jx::launch_xof(c, b, s)); }, 3, s);
-    b.k1_split = 7;
-    const double words = time_ms([&] { CK(jx::launch_xof(c, b, s)); }, 3, s);
+    // the lane pairs as the engine picks them below one pair-wave per SIMD (unrolled rounds)
+    const double pairs = time_ms([&] { CK(jx::launch_xof(c, b, {jx::K1_PAIRS_UNROLLED, 0}, s)); }, 3, s);
+    const double pairs_loop = time_ms([&] { CK(jx::launch_xof(c, b, {jx::K1_PAIRS, 0}, s)); }, 3, s);
+    const double words = time_ms([&] { CK(jx::launch_xof(c, b, {jx::K1_WORDS, 0}, s)); }, 3, s);
     printf("{\"reports\": %llu, \"pairs_ms\": %.3f, \"pairs_looped_ms\": %.3f, \"words_ms\": %.3f}\n",
            (unsigned long long)n, pairs, pairs_loop, words);
     fflush(stdout);
@@ -131,7 +130,6 @@ static int fpmix() {
   b.msgs = (uint8_t*)dalloc(N * 16, 12);
   b.consts = e->d_consts;
   b.lis_rs = c.lis_bytes;
-  b.k1_lds = jx::lanes_lds_bytes(2);
   CK(hipDeviceSynchronize());
   hipStream_t s1, s2;
   CK(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking));
@@ -159,18 +157,16 @@ static int fpmix() {
     t.msgs += S * 16;
     return t;
   };
-  auto run = [&](uint64_t S, uint32_t split_b, int reps) {
+  auto run = [&](uint64_t S, jx::K1Kernel tail_kernel, int reps) {
     float best = 1e30f;
     for (int it = 0; it < reps + 1; it++) {
       jx::Bufs a = b, t = tail(S);
       a.n = S;
-      a.k1_split = 3;
-      t.k1_split = split_b;
       CK(hipEventRecord(t0, s1));
       CK(hipEventRecord(fork, s1));
       CK(hipStreamWaitEvent(s2, fork, 0));
-      if (S) CK(jx::launch_xof(c, a, s1));
-      if (S < N) CK(jx::launch_xof(c, t, s2));
+      if (S) CK(jx::launch_xof(c, a, {jx::K1_LANES, jx::lanes_lds_bytes(2)}, s1));
+      if (S < N) CK(jx::launch_xof(c, t, {tail_kernel, 0}, s2));
       CK(hipEventRecord(join, s2));
       CK(hipStreamWaitEvent(s1, join, 0));
       CK(hipEventRecord(t1, s1));
@@ -182,11 +178,11 @@ static int fpmix() {
     return (double)best;
   };
   const uint64_t splits[] = {40960, 36864, 34816, 32768, 30720, 28672, 0};
-  for (uint32_t pk : {8u, 6u}) {  // the lane-pair part with unrolled (8) or looped (6) rounds
+  for (jx::K1Kernel pk : {jx::K1_PAIRS_UNROLLED, jx::K1_PAIRS}) {  // the lane-pair part with unrolled or looped rounds
     for (uint64_t S : splits) {
       const double ms = run(S, pk, 2);
       printf("{\"lane_split_reports\": %llu, \"lane_pair_reports\": %llu, \"pairs_unrolled\": %s, \"ms\": %.2f}\n",
-             (unsigned long long)S, (unsigned long long)(N - S), pk == 8 ? "true" : "false", ms);
+             (unsigned long long)S, (unsigned long long)(N - S), pk == jx::K1_PAIRS_UNROLLED ? "true" : "false", ms);
       fflush(stdout);
     }
   }
@@ -220,7 +216,6 @@ int main(int argc, char** argv) {
   b.msgs = (uint8_t*)dalloc(n * 16, 12);
   b.consts = e->d_consts;
   b.lis_rs = c.lis_bytes;
-  b.k1_split = 5;
   CK(hipDeviceSynchronize());
   hipStream_t s;
   CK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
