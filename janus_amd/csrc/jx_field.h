@@ -473,6 +473,8 @@ JX_HD f128 wacc_reduce(wacc26 a) {
 // Field64 (Goldilocks) p = 2^64 - 2^32 + 1, canonical representation
 
 constexpr uint64_t P64 = 0xFFFFFFFF00000001ull;
+// an 8-byte encoding (lo, hi words) that is not a Field64 element: >= p
+JX_HD bool ge_p64(uint32_t lo, uint32_t hi) { return hi == 0xFFFFFFFFu && lo != 0u; }
 
 JX_HD uint64_t add64(uint64_t a, uint64_t b) {
   uint64_t s = a + b;
@@ -568,6 +570,11 @@ JX_HD uint64_t pow64_h(uint64_t a, uint64_t e) {
   return r;
 }
 
+// a Field128 encoding from its four little-endian words
+JX_HD f128 w4_to_f(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+  return make128((uint64_t)a | ((uint64_t)b << 32), (uint64_t)c | ((uint64_t)d << 32));
+}
+
 // ----------------------------------------------------------------------------
 // Field128 helpers of the kernels (device code: uint4 is HIP's)
 #if defined(__HIPCC__) || defined(__HIP__)
@@ -576,9 +583,6 @@ __device__ __forceinline__ f128 u4_to_f(uint4 v) {
   return make128((uint64_t)v.x | ((uint64_t)v.y << 32), (uint64_t)v.z | ((uint64_t)v.w << 32));
 }
 __device__ __forceinline__ uint4 f_to_u4(f128 a) { return make_uint4(lo32(a.lo), hi32(a.lo), lo32(a.hi), hi32(a.hi)); }
-__device__ __forceinline__ f128 w4_to_f(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
-  return make128((uint64_t)a | ((uint64_t)b << 32), (uint64_t)c | ((uint64_t)d << 32));
-}
 // Montgomery exponentiation, uniform exponent
 __device__ inline f128 mpow(f128 aR, uint32_t e) {
   f128 r = make128(R1_128_LO, R1_128_HI);

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "jx_flags.h"
 #include "jx_k1_plan.h"
 #include "jx_keyreg.h"
 
@@ -24,15 +25,6 @@ enum Algo : uint32_t {
   ALGO_FIXEDPOINT_L2 = 5,
 };
 constexpr uint32_t MP_MAX_PROOFS = 8;  // num_proofs supported by the multiproof kernels
-
-// per-report flag bits written by the XOF stage, consumed by the FLP stage
-enum : uint32_t {
-  FLAG_INIT_FAIL = 1u,  // query randomness t is a P-th root of unity -> prepare_init_failure
-  FLAG_NEXT_FAIL = 2u,  // leader's joint-rand part disagrees with the public share -> prepare_next_failure
-  FLAG_SLOW = 4u,       // a rejected XOF sample shifted a stream: the slow kernel redoes this report
-  FLAG_DFAIL = 8u,      // a leader verifier element is >= p -> leader_prep_share_decode_failure
-  FLAG_INPUT_FAIL = 16u,  // leader: an explicit input-share element is >= p -> prepare_init_failure
-};
 
 // Interleaved staging: element e of report r lives at [(r/64)][e][r%64] (16 bytes each),
 // so a wave (64 reports, one per lane) touching element e moves one coalesced 1 KiB.

@@ -28,6 +28,7 @@
 #include "jx_field.h"
 #include "jx_kernels.h"
 #include "jx_keccak.h"
+#include "jx_sample.h"
 #include "jx_sha256.h"
 
 namespace jx {
@@ -42,26 +43,6 @@ __device__ uint64_t pow64(uint64_t a, uint64_t e) {
     e >>= 1;
   }
   return r;
-}
-
-// first N accepted Field64 samples from a stream whose first block is in S
-template <int N>
-__device__ void sample64(uint32_t* S, uint64_t out[N]) {
-  int cnt = 0;
-#pragma unroll 1
-  for (int guard = 0; guard < 64; guard++) {
-#pragma unroll
-    for (int ci = 0; ci < 21; ci++) {
-      uint64_t x = (uint64_t)S[2 * ci] | ((uint64_t)S[2 * ci + 1] << 32);
-      bool acc = x < P64;
-#pragma unroll
-      for (int i = 0; i < N; i++)
-        if (acc && cnt == i) out[i] = x;
-      cnt += acc ? 1 : 0;
-    }
-    if (cnt >= N) break;
-    keccak_p12(S);
-  }
 }
 
 // ---------------------------------------------------------------------------- K0: Prio3Count
@@ -211,10 +192,6 @@ __device__ __forceinline__ f128 truncw_value(const TruncW& t) {
   const uint64_t w2 = (t.T[3] >> 32) + c;
   return reduce192_small(w0, w1, w2);  // V < 2^(128 + bits), bits <= 32
 }
-// Conservative ">= p" screen for a sampled Field128 element: true for every x >= p (and for
-// the 2^-59-probable x in [2^128 - 2^69, p), which the slow kernel then redoes exactly).
-// Tracked as a running max so that one compare per block decides.
-__device__ __forceinline__ uint32_t ge_screen(uint4 v) { return v.w & (v.z | 0x1Fu); }
 
 // h * 2^32 mod p (the high half of a > 32-bit truncation)
 __device__ __forceinline__ f128 shl32_mod(f128 h) {
@@ -319,35 +296,6 @@ __device__ f128 bary_coeffs(uint4* coef, uint64_t blk, uint32_t NC, uint32_t lan
   }
   st_il(coef, blk, NC, s0, lane, inv);  // c_0 = 1/(t - 1)
   return sumc;
-}
-
-// `cnt` (<= 2) Field128 samples from an XOF stream whose first block is in S. Fast path: the first
-// two 16-byte chunks, FLAG_SLOW if one is >= p; slow path: rejection sampling (a rejection stays in
-// the first block except with probability ~2^-600, beyond which chunks straddling blocks are skipped).
-// Every index is static (the chunks are unrolled and a sample lands in out[0] / out[1] by select), so
-// the state and the samples stay in registers: a data-dependent index would put both in scratch.
-__device__ __forceinline__ void sample2_f128(uint32_t* S, f128 out[2], uint32_t cnt, bool slow, uint32_t& flags) {
-  if (!slow) {
-    out[0] = w4_to_f(S[0], S[1], S[2], S[3]);
-    out[1] = w4_to_f(S[4], S[5], S[6], S[7]);
-    if (ge_p128(out[0]) || (cnt > 1 && ge_p128(out[1]))) flags |= FLAG_SLOW;
-    return;
-  }
-  f128 o0 = make128(0, 0), o1 = make128(0, 0);
-  uint32_t k = 0;
-  for (int guard = 0; guard < 64 && k < cnt; guard++) {
-#pragma unroll
-    for (int ci = 0; ci < 10; ci++) {
-      const f128 v = w4_to_f(S[4 * ci], S[4 * ci + 1], S[4 * ci + 2], S[4 * ci + 3]);
-      const bool take = k < cnt && !ge_p128(v);
-      if (take && k == 0) o0 = v;
-      if (take && k == 1) o1 = v;
-      k += take ? 1u : 0u;
-    }
-    if (k < cnt) keccak_p12(S);
-  }
-  out[0] = o0;
-  out[1] = o1;
 }
 
 // Tail of the XOF stage shared by the fast and slow kernels: joint randomness,
@@ -497,11 +445,6 @@ __device__ uint32_t xof_tail(const Cfg& c, const Bufs& b, uint64_t blk, uint32_t
     }
   }
   return flags;
-}
-
-// Exact ">= p" test (decoding an explicit Field128 element, VDAF-08 decode rejects x >= p).
-__device__ __forceinline__ bool ge_exact(uint4 v) {
-  return v.w == 0xFFFFFFFFu && (v.z > 0xFFFFFFE4u || (v.z == 0xFFFFFFE4u && (v.x | v.y) != 0u));
 }
 
 // K1, helper (agg_id 1, aggregator.rs:1947), large launches: the measurement and proof shares are
@@ -1852,34 +1795,6 @@ __global__ __launch_bounds__(64 * K1_WAVES) void xof_leader_kernel(Cfg c, Bufs b
 // General byte-stream implementation with rejection sampling at any position. Runs only
 // for reports flagged FLAG_SLOW (a sampled chunk was >= p; ~1e-14 per SumVec report).
 
-struct ByteXof {
-  uint32_t s[50];
-  uint32_t pos;
-};
-__device__ uint32_t bx_byte(ByteXof& x) {
-  if (x.pos == 168) {
-    keccak_p12(x.s);
-    x.pos = 0;
-  }
-  uint32_t v = (x.s[x.pos >> 2] >> (8 * (x.pos & 3))) & 0xffu;
-  x.pos++;
-  return v;
-}
-__device__ f128 bx_elem128(ByteXof& x) {
-  uint32_t w[4];
-  for (int i = 0; i < 4; i++) {
-    uint32_t v = 0;
-    for (int k = 0; k < 4; k++) v |= bx_byte(x) << (8 * k);
-    w[i] = v;
-  }
-  return w4_to_f(w[0], w[1], w[2], w[3]);
-}
-__device__ f128 bx_sample128(ByteXof& x) {
-  for (;;) {
-    f128 v = bx_elem128(x);
-    if (!ge_p128(v)) return v;
-  }
-}
 struct ByteAbs {
   uint32_t s[50];
   uint32_t pos;

@@ -96,7 +96,6 @@ __device__ __forceinline__ void aes_enc_fast(const TTab& T, const uint32_t rk[44
 
 __device__ __forceinline__ uint64_t u2v(uint2 v) { return (uint64_t)v.x | ((uint64_t)v.y << 32); }
 __device__ __forceinline__ uint2 v2u(uint64_t v) { return make_uint2(lo32(v), hi32(v)); }
-__device__ __forceinline__ bool ge_p64(uint32_t lo, uint32_t hi) { return hi == 0xFFFFFFFFu && lo != 0u; }
 
 __device__ __forceinline__ void load32(const uint8_t* p, uint32_t w[8]) {
   const uint4 a = *reinterpret_cast<const uint4*>(p), b = *reinterpret_cast<const uint4*>(p + 16);

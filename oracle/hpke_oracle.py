@@ -98,6 +98,8 @@ def _make_sbox():
 
 
 SBOX = _make_sbox()
+_MUL2 = [_gmul(x, 2) for x in range(256)]  # MixColumns' two multipliers, tabulated
+_MUL3 = [_gmul(x, 3) for x in range(256)]
 
 
 def aes128_expand(key: bytes) -> list[bytes]:
@@ -121,10 +123,10 @@ def aes128_encrypt_block(rk: list[bytes], block: bytes) -> bytes:
             t = []
             for c in range(4):
                 a = s[4 * c:4 * c + 4]
-                t += [_gmul(a[0], 2) ^ _gmul(a[1], 3) ^ a[2] ^ a[3],
-                      a[0] ^ _gmul(a[1], 2) ^ _gmul(a[2], 3) ^ a[3],
-                      a[0] ^ a[1] ^ _gmul(a[2], 2) ^ _gmul(a[3], 3),
-                      _gmul(a[0], 3) ^ a[1] ^ a[2] ^ _gmul(a[3], 2)]
+                t += [_MUL2[a[0]] ^ _MUL3[a[1]] ^ a[2] ^ a[3],
+                      a[0] ^ _MUL2[a[1]] ^ _MUL3[a[2]] ^ a[3],
+                      a[0] ^ a[1] ^ _MUL2[a[2]] ^ _MUL3[a[3]],
+                      _MUL3[a[0]] ^ a[1] ^ a[2] ^ _MUL2[a[3]]]
             s = t
         s = [s[i] ^ rk[rnd][i] for i in range(16)]
     return bytes(s)

@@ -9,6 +9,7 @@
 #include "../../janus_amd/csrc/jx_sha256.h"
 #include "../../janus_amd/csrc/jx_hpke.h"
 #include "../../janus_amd/csrc/jx_sha_aes.h"
+#include "../../janus_amd/csrc/jx_sample.h"
 
 using namespace jx;
 
@@ -21,6 +22,15 @@ static f128 ld(const uint8_t* p) {
 static void st(uint8_t* p, f128 v) {
   memcpy(p, &v.lo, 8);
   memcpy(p + 8, &v.hi, 8);
+}
+static void st_to_words(const uint64_t st64[25], uint32_t s[50]) {
+  for (int i = 0; i < 25; i++) {
+    s[2 * i] = (uint32_t)st64[i];
+    s[2 * i + 1] = (uint32_t)(st64[i] >> 32);
+  }
+}
+static void st_from_words(const uint32_t s[50], uint64_t st64[25]) {
+  for (int i = 0; i < 25; i++) st64[i] = (uint64_t)s[2 * i] | ((uint64_t)s[2 * i + 1] << 32);
 }
 
 extern "C" {
@@ -239,4 +249,51 @@ uint64_t ht_wacc64_dot(const uint64_t* xs, const uint64_t* cs, int n) {
   return add64(acc, wacc64_reduce(a));
 }
 uint64_t ht_reduce192_p64(const uint64_t w[3]) { return reduce192_p64(w[0], w[1], w[2]); }
+// ---- exact ">= p" predicates and rejection sampling (jx_field.h, jx_sample.h)
+int ht_ge_p128(const uint8_t* a) { return ge_p128(ld(a)) ? 1 : 0; }
+int ht_ge_p64(uint32_t lo, uint32_t hi) { return ge_p64(lo, hi) ? 1 : 0; }
+int ht_ge_exact(const uint8_t* a) {
+  uint4 v;
+  memcpy(&v, a, 16);
+  return ge_exact(v) ? 1 : 0;
+}
+// the running max of ge_screen over n 16-byte elements, as the XOF kernels keep it per block
+uint32_t ht_ge_screen_max(const uint8_t* a, int n) {
+  uint32_t gmax = 0;
+  for (int i = 0; i < n; i++) {
+    uint4 v;
+    memcpy(&v, a + 16 * i, 16);
+    gmax = gmax > ge_screen(v) ? gmax : ge_screen(v);
+  }
+  return gmax;
+}
+// sample64<N> (N = 1 | 5) on a Keccak state whose first block is ready; the state is left as sampling left it
+void ht_sample64(int n, uint64_t st64[25], uint64_t* out) {
+  uint32_t s[50];
+  st_to_words(st64, s);
+  if (n == 1) {
+    sample64<1>(s, out);
+  } else {
+    sample64<5>(s, out);
+  }
+  st_from_words(s, st64);
+}
+void ht_sample2_f128(uint64_t st64[25], uint32_t cnt, int slow, uint8_t out[32], uint32_t* flags) {
+  uint32_t s[50];
+  st_to_words(st64, s);
+  f128 o[2] = {make128(0, 0), make128(0, 0)};
+  sample2_f128(s, o, cnt, slow != 0, *flags);
+  st(out, o[0]);
+  st(out + 16, o[1]);
+  st_from_words(s, st64);
+}
+// n elements from the byte stream that starts at byte `pos` of the block in st64; returns the final position
+uint32_t ht_bx_sample128(uint64_t st64[25], uint32_t pos, int n, uint8_t* out) {
+  ByteXof x;
+  st_to_words(st64, x.s);
+  x.pos = pos;
+  for (int i = 0; i < n; i++) st(out + 16 * i, bx_sample128(x));
+  st_from_words(x.s, st64);
+  return x.pos;
+}
 }

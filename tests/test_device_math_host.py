@@ -21,7 +21,8 @@ def ht():
     src = os.path.join(HERE, "csrc", "hosttest.cpp")
     so = os.path.join(HERE, "csrc", "libjx_hosttest.so")
     hdrs = [os.path.join(HERE, "..", "janus_amd", "csrc", h) for h in ("jx_field.h", "jx_keccak.h", "jx_sha256.h",
-                                                                         "jx_hpke.h", "jx_sha_aes.h")]
+                                                                         "jx_hpke.h", "jx_sha_aes.h", "jx_sample.h",
+                                                                         "jx_flags.h")]
     if not os.path.exists(so) or any(os.path.getmtime(h) > os.path.getmtime(so) for h in hdrs + [src]):
         tmp = f"{so}.{os.getpid()}.tmp"  # atomic: pytest-xdist workers may build concurrently
         subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", tmp, src], check=True)
@@ -51,6 +52,15 @@ def ht():
     L.ht_wacc64_dot.restype = ctypes.c_uint64
     L.ht_reduce192_p64.argtypes = [vp]
     L.ht_reduce192_p64.restype = ctypes.c_uint64
+    L.ht_ge_p128.argtypes = [vp]
+    L.ht_ge_exact.argtypes = [vp]
+    L.ht_ge_p64.argtypes = [ctypes.c_uint32, ctypes.c_uint32]
+    L.ht_ge_screen_max.argtypes = [vp, ctypes.c_int]
+    L.ht_ge_screen_max.restype = ctypes.c_uint32
+    L.ht_sample64.argtypes = [ctypes.c_int, vp, vp]
+    L.ht_sample2_f128.argtypes = [vp, ctypes.c_uint32, ctypes.c_int, vp, vp]
+    L.ht_bx_sample128.argtypes = [vp, ctypes.c_uint32, ctypes.c_int, vp]
+    L.ht_bx_sample128.restype = ctypes.c_uint32
     return L
 
 
@@ -337,3 +347,205 @@ def test_reduce192_p64(ht):
             w = [2**64 - 1] * 3
         a = (ctypes.c_uint64 * 3)(*w)
         assert ht.ht_reduce192_p64(a) == (w[0] + (w[1] << 64) + (w[2] << 128)) % P64
+
+
+# ---------------------------------------------------------------------------- ">= p" and rejection sampling
+# (jx_field.h ge_p128 / ge_p64, jx_sample.h): the decode bounds and the skip branches that a real stream
+# reaches once in 2^32 (Field64) or 2^59 (Field128) elements, on hand-built values and Keccak states.
+
+M64 = 2**64 - 1
+HI128 = 0xFFFFFFFFFFFFFFE4  # high half of p128 (its low half is 1)
+BOUND128 = [P128 - 1, P128, P128 + 1, (HI128 << 64) | 2**32, (HI128 + 1) << 64, ((HI128 - 1) << 64) | M64,
+            2**128 - 1, HI128 << 64, (HI128 << 64) | 2, (HI128 << 64) | 2**63, 0, 1, 2**64, 2**127,
+            ((HI128 - 1) << 64) | 1, (0xFFFFFFFF << 96) | 1, (0xFFFFFFFFFFFFFFFF << 64)]
+BOUND64 = [P64 - 1, P64, P64 + 1, 0xFFFFFFFF80000000, 0xFFFFFFFEFFFFFFFF, M64, 0xFFFFFFFF00000000, 0xFFFFFFFF00010000,
+           0xFFFFFFFE00000001, 0, 1, 2**32, 2**63]
+
+
+@pytest.mark.parametrize("fn", ["ht_ge_p128", "ht_ge_exact"])
+def test_ge_p128_exact(ht, fn):
+    """ge_p128 (f128, the samplers and the verifier decode) and ge_exact (uint4, the leader's decode of its
+    explicit input share) against Python integers."""
+    rnd = random.Random(41)
+    vals = BOUND128 + [rnd.randrange(2**128) for _ in range(300)]
+    vals += [(HI128 << 64) | rnd.randrange(2**64) for _ in range(50)]            # only the low half decides
+    vals += [(rnd.randrange(HI128 - 3, 2**64) << 64) | rnd.randrange(4) for _ in range(100)]
+    for v in vals:
+        assert getattr(ht, fn)(_b(v)) == int(v >= P128), hex(v)
+
+
+def test_ge_p64_exact(ht):
+    rnd = random.Random(42)
+    vals = BOUND64 + [rnd.randrange(2**64) for _ in range(300)]
+    vals += [(0xFFFFFFFF << 32) | rnd.randrange(2**32) for _ in range(50)]
+    vals += [(0xFFFFFFFF << 32) | (1 << k) for k in range(32)]                   # any one low bit decides
+    vals += [(rnd.randrange(2**32 - 4, 2**32) << 32) | rnd.randrange(3) for _ in range(100)]
+    for v in vals:
+        assert ht.ht_ge_p64(v & 0xFFFFFFFF, v >> 32) == int(v >= P64), hex(v)
+
+
+def test_ge_screen_is_a_superset_and_survives_the_running_max(ht):
+    """ge_screen == 0xFFFFFFFF for every v >= p128 (it may also fire just below p), and the per-block running
+    max still says so with any number of smaller elements before and after."""
+    rnd = random.Random(43)
+    ge = [v for v in BOUND128 if v >= P128] + [rnd.randrange(P128, 2**128) for _ in range(300)]
+    ge += [(hi << 64) | lo for hi in range(HI128, 2**64) for lo in (0, 1, 2, 2**32, M64) if (hi << 64) | lo >= P128]
+    for v in ge:
+        assert ht.ht_ge_screen_max(_b(v), 1) == 0xFFFFFFFF, hex(v)
+    for v in [0, 1, 2**64, 2**127, (0xFFFFFFFF << 96) - 1, (0xFFFFFFFE << 96) | (2**96 - 1)]:  # far below p: quiet
+        assert ht.ht_ge_screen_max(_b(v), 1) != 0xFFFFFFFF, hex(v)
+    for v in ge[:40]:
+        for k in (0, 3, 7):
+            elems = [rnd.randrange(2**126) for _ in range(8)]
+            elems[k] = v
+            buf = ctypes.create_string_buffer(b"".join(e.to_bytes(16, "little") for e in elems), 128)
+            assert ht.ht_ge_screen_max(buf, 8) == 0xFFFFFFFF
+    quiet = ctypes.create_string_buffer(b"".join(rnd.randrange(2**126).to_bytes(16, "little") for _ in range(8)), 128)
+    assert ht.ht_ge_screen_max(quiet, 8) != 0xFFFFFFFF
+
+
+def _state(rnd, field_bytes):
+    """25 random lanes whose rate part holds no encoding >= p (so every rejection is one the test placed)."""
+    st = [rnd.randrange(2**64) for _ in range(25)]
+    for i in range(21):
+        if field_bytes == 8 and st[i] >> 32 == 0xFFFFFFFF:
+            st[i] &= 2**63 - 1
+        if field_bytes == 16 and i % 2 == 1:
+            st[i] &= 2**63 - 1
+    return st
+
+
+def _model_take(st, nbytes, count, p, pos=0, whole_chunks=0):
+    """Rejection sampling over the sponge's byte stream from byte `pos` of the block in st (168-byte rate,
+    Keccak-p[1600,12] between blocks), by the oracle's permutation. whole_chunks > 0: only that many
+    aligned chunks of each block are looked at (the kernels' register-resident samplers). Returns
+    (samples, final state, final position)."""
+    out, st = [], list(st)
+    while True:
+        blk = b"".join(x.to_bytes(8, "little") for x in st[:21])
+        limit = whole_chunks * nbytes if whole_chunks else 168
+        while pos + nbytes <= limit and len(out) < count:
+            x = int.from_bytes(blk[pos:pos + nbytes], "little")
+            pos += nbytes
+            if x < p:
+                out.append(x)
+        if len(out) >= count:
+            return out, st, pos
+        assert whole_chunks or pos + nbytes > 168
+        carry = blk[pos:168] if not whole_chunks else b""
+        st = O.keccak_p1600(st, 12)
+        pos = 0
+        if carry:  # an element straddling two blocks
+            blk = b"".join(x.to_bytes(8, "little") for x in st[:21])
+            need = nbytes - len(carry)
+            x = int.from_bytes(carry + blk[:need], "little")
+            pos = need
+            if x < p:
+                out.append(x)
+                if len(out) >= count:
+                    return out, st, pos
+
+
+def _u64s(vals):
+    return (ctypes.c_uint64 * len(vals))(*vals)
+
+
+GE64 = [P64, M64, 0xFFFFFFFF80000000, P64 + 1, 0xFFFFFFFF00010000]
+
+
+@pytest.mark.parametrize("n", [1, 5])
+def test_sample64_skips_rejected_chunks(ht, n):
+    rnd = random.Random(50 + n)
+    cases = [[k] for k in range(21)]                                    # one rejection at every position
+    cases += [[0, 1], [0, 1, 2, 3], [3, 4, 5, 9], [19, 20], list(range(0, 17)), list(range(1, 21)),
+              list(range(21 - n + 1)),                                  # fewer than n left: the next block is needed
+              list(range(21))]                                          # none left
+    permuted = 0
+    for ci, rej in enumerate(cases):
+        st = _state(rnd, 8)
+        for j, k in enumerate(rej):
+            st[k] = GE64[(ci + j) % len(GE64)]
+        want, st_after, _ = _model_take(st, 8, n, P64, whole_chunks=21)
+        buf, out = _u64s(st), (ctypes.c_uint64 * 5)()
+        ht.ht_sample64(n, buf, out)
+        assert list(out)[:n] == want, (n, rej)
+        assert list(buf) == st_after, (n, rej)
+        permuted += st_after != st
+    assert permuted >= 2
+    # the largest element is taken, not skipped
+    st = _state(rnd, 8)
+    st[0] = P64 - 1
+    buf, out = _u64s(st), (ctypes.c_uint64 * 5)()
+    ht.ht_sample64(n, buf, out)
+    assert out[0] == P64 - 1
+
+
+GE128 = [P128, P128 + 1, 2**128 - 1, (HI128 << 64) | 2**32, (HI128 + 1) << 64]
+
+
+def _set128(st, chunk, v):
+    st[2 * chunk], st[2 * chunk + 1] = v & M64, v >> 64
+
+
+@pytest.mark.parametrize("cnt", [1, 2])
+def test_sample2_f128_fast_flags_and_slow_skips(ht, cnt):
+    FLAG_SLOW, other = 4, 16
+    rnd = random.Random(60 + cnt)
+    for rej in ([], [0], [1], [0, 1], [2], [0, 2], [1, 2, 3], [0, 1, 2, 3, 4, 5, 6, 7, 8]):
+        for gi, g in enumerate(GE128):
+            st = _state(rnd, 16)
+            for j, k in enumerate(rej):
+                _set128(st, k, GE128[(gi + j) % len(GE128)])
+            if not rej:
+                _set128(st, 0, P128 - 1)  # the largest element: taken, no flag
+                _set128(st, 1, ((HI128 - 1) << 64) | M64)
+            chunks = [st[2 * k] | (st[2 * k + 1] << 64) for k in range(10)]
+            # fast: the first cnt chunks as they are, FLAG_SLOW exactly when one of them is >= p
+            buf, out, flags = _u64s(st), ctypes.create_string_buffer(32), ctypes.c_uint32(other)
+            ht.ht_sample2_f128(buf, cnt, 0, out, ctypes.byref(flags))
+            got = [int.from_bytes(out.raw[16 * i:16 * i + 16], "little") for i in range(2)]
+            assert got[:cnt] == chunks[:cnt]
+            assert flags.value == other | (FLAG_SLOW if any(c >= P128 for c in chunks[:cnt]) else 0), (rej, cnt)
+            assert list(buf) == st
+            # slow: the first cnt accepted chunks
+            want, st_after, _ = _model_take(st, 16, cnt, P128, whole_chunks=10)
+            buf, out, flags = _u64s(st), ctypes.create_string_buffer(32), ctypes.c_uint32(other)
+            ht.ht_sample2_f128(buf, cnt, 1, out, ctypes.byref(flags))
+            got = [int.from_bytes(out.raw[16 * i:16 * i + 16], "little") for i in range(2)]
+            assert got[:cnt] == want, (rej, cnt)
+            assert flags.value == other and list(buf) == st_after
+
+
+def test_bx_sample128_rejection_before_a_block_boundary(ht):
+    """The slow path's byte stream: a rejected element (or two in a row) whose successor straddles the
+    168-byte block boundary, at several alignments of the stream. Rejections are placed in the first block
+    only: what the permutation leaves in the next block cannot be chosen, so the straddling element itself
+    and those after it are always below p."""
+    rnd = random.Random(70)
+    # (first byte, elements to take, indices of the rejected elements); the successor of the last rejected
+    # element covers bytes 160..175, 152..167 + 0..7 of the next block, ... according to the alignment
+    for pos0, nelem, rej_at in [(0, 12, [9]), (0, 12, [8, 9]), (8, 12, [0, 9]), (144, 3, [0]), (4, 12, [3]),
+                                (4, 12, [9]), (12, 12, [8])]:
+        for g in GE128:
+            # elements are 16 bytes from byte pos0; the element at index e covers bytes pos0 + 16 e ..
+            st = _state(rnd, 8)
+            blk = bytearray(b"".join(x.to_bytes(8, "little") for x in st[:21]))
+            for e in range((168 - pos0) // 16):  # keep the unplaced first-block elements below p
+                blk[pos0 + 16 * e + 15] &= 0x7F
+            for e in rej_at:
+                assert pos0 + 16 * e + 16 <= 168
+                blk[pos0 + 16 * e:pos0 + 16 * e + 16] = g.to_bytes(16, "little")
+            st[:21] = [int.from_bytes(blk[8 * i:8 * i + 8], "little") for i in range(21)]
+            want, st_after, pos_after = _model_take(st, 16, nelem, P128, pos=pos0)
+            buf, out = _u64s(st), ctypes.create_string_buffer(16 * nelem)
+            pos = ht.ht_bx_sample128(buf, pos0, nelem, out)
+            got = [int.from_bytes(out.raw[16 * i:16 * i + 16], "little") for i in range(nelem)]
+            assert got == want, (pos0, rej_at)
+            assert pos == pos_after and list(buf) == st_after
+    # no rejection at all: the eleventh element is the straddling one (bytes 160..167 and 0..7 of the next block)
+    st = _state(rnd, 8)
+    st[20] = M64
+    want, st_after, pos_after = _model_take(st, 16, 12, P128)
+    buf, out = _u64s(st), ctypes.create_string_buffer(16 * 12)
+    assert ht.ht_bx_sample128(buf, 0, 12, out) == pos_after
+    assert [int.from_bytes(out.raw[16 * i:16 * i + 16], "little") for i in range(12)] == want
