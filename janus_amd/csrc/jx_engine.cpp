@@ -21,6 +21,7 @@
 
 #include "jx_engine_internal.h"
 #include "jx_field.h"
+#include "jx_fused_plan.h"
 #include "jx_sha_aes.h"
 
 using namespace jx;
@@ -825,14 +826,19 @@ static int32_t flush_acc(jx_engine* e) {
     if (_fr) return _fr;             \
   } while (0)
 
-// Upload the device pointer table (aggs, counts, checksums) of `targets` into per-call scratch `tbl` (e->d_ptrs
-// points at it while it is held). The pinned host copy is double-buffered and reused only once the upload
-// that last read it has completed, so the host never waits for the call's own kernels.
-static int32_t upload_targets(jx_engine* e, const std::vector<Segment>& targets, Scratch& tbl) {
+// The device pointer table of a call's targets, [3][S]: aggs, counts, checksums. It owns the per-call scratch it
+// lies in, which goes back to the arena (stream-ordered) with it.
+struct PtrTable {
+  Scratch mem;
+  void** d() const { return (void**)mem.p(); }
+};
+
+// Upload the pointer table of `targets` into `tbl`. The pinned host copy is double-buffered and reused only once
+// the upload that last read it has completed, so the host never waits for the call's own kernels.
+static int32_t upload_targets(jx_engine* e, const std::vector<Segment>& targets, PtrTable& tbl) {
   const uint64_t S = targets.size();
-  int32_t rc = scratch_get(e, 3 * S * sizeof(void*), tbl);
+  int32_t rc = scratch_get(e, 3 * S * sizeof(void*), tbl.mem);
   if (rc) return rc;
-  e->d_ptrs = (void**)tbl.p();
   const int k = e->ptrs_k;
   e->ptrs_k ^= 1;
   if (!e->ev_ptrs[k]) HIPCHK(e, hipEventCreateWithFlags(&e->ev_ptrs[k], hipEventDisableTiming));
@@ -849,7 +855,7 @@ static int32_t upload_targets(jx_engine* e, const std::vector<Segment>& targets,
     h[S + t] = targets[t].count;
     h[2 * S + t] = targets[t].checksum;
   }
-  HIPCHK(e, hipMemcpyAsync(e->d_ptrs, h, 3 * S * sizeof(void*), hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, hipMemcpyAsync(tbl.d(), h, 3 * S * sizeof(void*), hipMemcpyHostToDevice, e->stream));
   HIPCHK(e, hipEventRecord(e->ev_ptrs[k], e->stream));
   return JX_OK;
 }
@@ -863,13 +869,21 @@ static uint32_t seg_items_len(const jx_engine* e, uint64_t n) {
 }
 
 // Accumulate the finished, accepted reports of src into the aggregations named by a dense per-report
-// index d_dense[r] in [0, S) (S = segments of the table uploaded by upload_targets; indices >= S are
-// skipped); one pass per SEG_MAX segments.
+// index d_dense[r] in [0, S) (S = targets.size(); indices >= S are skipped); one pass per SEG_MAX segments.
+// tbl: the targets' pointer table when the caller has uploaded it (one upload for every launch of a call);
+// null: uploaded here.
 static int32_t accumulate_many(jx_engine* e, const AccSrc& src, const uint8_t* d_mask, const uint32_t* d_dense,
-                               uint64_t S) {
+                               const std::vector<Segment>& targets, const PtrTable* tbl) {
   const Cfg& c = e->cfg;
-  const uint64_t n = src.n;
+  const uint64_t n = src.n, S = targets.size();
   if (S == 0 || n == 0) return JX_OK;
+  PtrTable own;
+  if (!tbl) {
+    int32_t rc = upload_targets(e, targets, own);
+    if (rc) return rc;
+    tbl = &own;
+  }
+  void** const d_ptrs = tbl->d();
   // per-pass segments: SEG_MAX, or fewer when the per-item partials would exceed ~512 MiB
   const uint32_t L = seg_items_len(e, n);
   const uint64_t items_n = (n + L - 1) / L;
@@ -886,10 +900,11 @@ static int32_t accumulate_many(jx_engine* e, const AccSrc& src, const uint8_t* d
   Scratch work;
   int32_t rc = scratch_get(e, wbytes, work);
   if (rc) return rc;
-  e->d_segx = (uint32_t*)(work.p() + o_segx);
-  e->d_perm = (uint32_t*)(work.p() + o_perm);
-  e->d_items = (uint4*)(work.p() + o_items);
-  e->d_spart = (uint64_t*)(work.p() + o_spart);
+  // d_segx: cnt, off, cursor [SEG_MAX each], ioff [SEG_MAX + 1], nitems [2]
+  uint32_t* const d_segx = (uint32_t*)(work.p() + o_segx);
+  uint32_t* const d_perm = (uint32_t*)(work.p() + o_perm);
+  uint4* const d_items = (uint4*)(work.p() + o_items);
+  uint64_t* const d_spart = (uint64_t*)(work.p() + o_spart);
   uint64_t grid = (n + 255) / 256;
   if (grid > SELECT_WGS) grid = SELECT_WGS;
   for (uint64_t s0 = 0; s0 < S; s0 += ns_max) {
@@ -905,19 +920,19 @@ static int32_t accumulate_many(jx_engine* e, const AccSrc& src, const uint8_t* d
     a.s0 = (uint32_t)s0;
     a.ns = ns;
     a.nonces = src.nonces;
-    a.cnt = e->d_segx;
-    a.off = e->d_segx + SEG_MAX;
-    a.cursor = e->d_segx + 2 * SEG_MAX;
-    a.ioff = e->d_segx + 3 * SEG_MAX;
-    a.nitems = e->d_segx + 4 * SEG_MAX + 1;
-    a.perm = e->d_perm;
+    a.cnt = d_segx;
+    a.off = d_segx + SEG_MAX;
+    a.cursor = d_segx + 2 * SEG_MAX;
+    a.ioff = d_segx + 3 * SEG_MAX;
+    a.nitems = d_segx + 4 * SEG_MAX + 1;
+    a.perm = d_perm;
     a.L = L;
-    a.items = e->d_items;
+    a.items = d_items;
     a.wmax = (uint32_t)(items_n + ns);
-    a.partials = e->d_spart;
-    a.aggs = reinterpret_cast<uint4* const*>(e->d_ptrs + s0);
-    a.counts = reinterpret_cast<unsigned long long* const*>(e->d_ptrs + S + s0);
-    a.checksums = reinterpret_cast<uint32_t* const*>(e->d_ptrs + 2 * S + s0);
+    a.partials = d_spart;
+    a.aggs = reinterpret_cast<uint4* const*>(d_ptrs + s0);
+    a.counts = reinterpret_cast<unsigned long long* const*>(d_ptrs + S + s0);
+    a.checksums = reinterpret_cast<uint32_t* const*>(d_ptrs + 2 * S + s0);
     HIPCHK(e, hipMemsetAsync(a.cnt, 0, ns * sizeof(uint32_t), e->stream));
     hipEvent_t ev = nullptr;
     HIPCHK(e, stage_begin(e, &ev));
@@ -959,17 +974,12 @@ static int32_t segment_targets(jx_engine* e, const uint32_t* ids, uint64_t nids,
 }
 
 // Accumulate src into targets[d_dense[r]] (d_dense nullable: all into targets[0]). One target takes the
-// coalesced select/accumulate path; several upload their pointer table (unless `uploaded`).
+// coalesced select/accumulate path; several go through their pointer table (tbl, or null: accumulate_many).
 static int32_t accumulate_into(jx_engine* e, const AccSrc& src, const uint8_t* d_mask, const uint32_t* d_dense,
-                               const std::vector<Segment>& targets, bool uploaded = false) {
+                               const std::vector<Segment>& targets, const PtrTable* tbl = nullptr) {
   if (src.n == 0 || targets.empty()) return JX_OK;
   if (targets.size() == 1 || !d_dense) return accumulate_one(e, src, d_mask, d_dense, targets[0]);
-  Scratch tbl;
-  if (!uploaded) {
-    int32_t rc = upload_targets(e, targets, tbl);
-    if (rc) return rc;
-  }
-  return accumulate_many(e, src, d_mask, d_dense, targets.size());
+  return accumulate_many(e, src, d_mask, d_dense, targets, tbl);
 }
 
 // Per-call delta aggregations (zeroed): ns contiguous segment states in per-call scratch `d`.
@@ -990,40 +1000,8 @@ static int32_t delta_targets(jx_engine* e, uint32_t ns, std::vector<Segment>& ou
 
 static uint32_t record_bytes(const Cfg& c) { return c.out_len * c.fb + 40u; }
 
-// Reports per launch for an n-report fused call: the fewest launches that fit the staging
-// budget (default_chunk), split evenly (multiple of 64) so every launch has the same shape.
-// When the chunk is a whole number of K1 rounds (round_reports), launches are full chunks and
-// only the last one carries a partial round (1.25M SumVec reports: 4 x 262,144 + 201,424
-// instead of 4 x 312,500). Measured on MI355X: K1 time per report is unchanged (its waves do
-// not finish in lockstep rounds), the step went 188.4 -> 184.6 ms, within run-to-run noise.
-static uint64_t launch_chunk(const jx_engine* e, uint64_t n) {
-  if (n <= e->default_chunk) return n;
-  if (e->round_reports && e->default_chunk % e->round_reports == 0) return e->default_chunk;
-  const uint64_t launches = (n + e->default_chunk - 1) / e->default_chunk;
-  const uint64_t per = (n + launches - 1) / launches;
-  return (per + 63) / 64 * 64;
-}
-
 // ---------------------------------------------------------------------------- pipelines
-// A helper launch of the fused path runs K1 (two sponges per lane, two waves per SIMD, VALU), then K3
-// (LDS-DMA ring: HBM + limb products) and K4 (HBM): one after the other, every launch's waves are in the
-// same phase at the same time (the K1 waves of a round reach their FLP-coefficient tails together, K3 runs
-// at a throttled clock beside an idle Keccak pipe). With P pipelines the launches of one call alternate
-// over P child engines, each with its own stream and per-call staging from the arena, so different
-// launches' phases overlap; only the K4s are ordered (they add into the same aggregation). Measured on
-// MI355X with P independent engines (tools/multi_engine_probe.py): SumVec 8x1000/88, 1.25M reports,
-// 7.28M (one) -> 7.67M (two) -> 7.79M reports/s (three). Used when a call spans >= 2 launches of one
-// segment; not for Count (one tiny kernel) or the multiproof path.
-// host: the host-buffer path, whose pageable copies also take turns (3 by default there: SumVec 1.25M
-// reports 5.02M -> 6.44M (two) -> 7.12M (three) reports/s including the copies, tools/bench_host_path.py).
-static uint32_t pipes_for(const jx_engine* e, uint64_t n, uint64_t chunk, bool many, bool host = false) {
-  const Cfg& c = e->cfg;
-  if (many || c.algo == ALGO_COUNT || c.algo == ALGO_SUMVEC_F64_MULTIPROOF) return 1;
-  const uint64_t launches = (n + chunk - 1) / chunk;
-  const uint64_t want = e->npipes ? e->npipes : (host ? 3 : 2);
-  return (uint32_t)(launches < want ? launches : want);
-}
-
+// The launches of a fused call alternate over child engines (jx_fused_plan.h says how many and why).
 jx_engine* jxi::new_child(jx_engine* parent) {
   jx_engine* q = new jx_engine();
   q->cfg = parent->cfg;
@@ -1042,8 +1020,6 @@ jx_engine* jxi::new_child(jx_engine* parent) {
   }
   return q;
 }
-
-constexpr uint32_t MAX_PIPES = 4;
 
 // Staging for up to P pipelines: the first one may wait for the arena, the others take what is free
 // now (so two calls never wait on each other holding half their pipelines). *got = pipelines staged.
@@ -1091,6 +1067,109 @@ static int32_t collect_pipe_timing(jx_engine* e) {
 // measurement staging for a helper prepare whose outputs go to a batch (Histogram writes its
 // measurement share, which is its output share, straight into the batch)
 static uint32_t helper_meas_flag(const Cfg& c) { return outs_alias_meas(c) ? 0u : SG_MEAS; }
+
+// ---------------------------------------------------------------------------- fused prepare + aggregate
+// jx_helper_prep_aggregate (host buffers) and jx_helper_prep_aggregate_device describe their call with a FusedCall;
+// run_fused runs every launch of it, on the engine stream or over the pipelines, as fused_plan says.
+
+// One launch's inputs on the device.
+struct FusedIn {
+  const uint8_t *nonces, *ps, *his, *lps;
+};
+
+struct FusedCall {
+  bool host;  // the host-buffer form: its launches stage their inputs, `download` brings the results back
+  // The inputs of launch [off, off + m) on lane q. The host form queues its four copies into q's staging (pageable:
+  // the host thread stages them, so with pipelines they go out while another pipeline's kernels run); the device
+  // form names the caller's arrays at off.
+  std::function<int32_t(jx_engine* q, uint64_t off, uint64_t m, FusedIn& in)> inputs;
+  // Device arrays for the whole call's verdicts and prep messages (row off is launch [off, ...)'s first). Null:
+  // each launch's go to its lane's staging (SG_RES), or, for the pipelined host form, to per-call scratch.
+  uint8_t *verdicts, *msgs;
+  const uint32_t* dense;  // the reports' dense segment index (nullable)
+  // Host form: copy rows [off, off + m) of the results, which start at dv / dm, to the caller's buffers and wait
+  // for them. After every launch on the engine stream; once for the whole call after the pipelines' join.
+  std::function<int32_t(const uint8_t* dv, const uint8_t* dm, uint64_t off, uint64_t m)> download;
+};
+
+// The staging of one lane of a fused call. The pipelined host form keeps its results in per-call scratch.
+static uint32_t fused_stage_flags(bool host, bool pipelined) {
+  if (!host) return SG_MEAS | SG_PREP | SG_RES | SG_ACC;
+  return SG_IN | SG_HIN | SG_MEAS | SG_PREP | SG_ACC | (pipelined ? 0u : SG_RES);
+}
+
+static int32_t run_fused(jx_engine* e, uint64_t n, const FusedPlan& plan, const std::vector<Segment>& targets,
+                         const FusedCall& call) {
+  const Cfg& c = e->cfg;
+  const uint64_t chunk = plan.chunk;
+  Stage pst[MAX_PIPES];
+  uint32_t P = 0;
+  int32_t rc = JX_OK;
+  if (plan.pipes > 1) {
+    rc = pipes_acquire(e, plan.pipes, chunk, fused_stage_flags(call.host, true), pst, &P);
+    if (rc) return rc;
+  }
+  const bool piped = P > 1;  // the lanes: e->pipes[0..P), else the engine itself
+  e->last_pipes = piped ? P : 1;
+  Stage st;
+  Scratch hout;  // per call, from the arena (handed back after download's copies are queued)
+  PtrTable tbl;
+  uint8_t *dv = call.verdicts, *dm = call.msgs;
+  if (piped) {
+    if (call.host) {
+      rc = scratch_get(e, n + (c.jr_len ? n * c.seed : 0), hout);
+      if (rc) return rc;
+      dv = hout.p();
+      dm = hout.p() + n;
+    }
+    // every pipeline orders after the caller's producers (jx_engine_wait_stream / _event act on the
+    // engine stream) and the engine stream after every pipeline (the join), so the call keeps the
+    // single-stream ordering contract
+    HIPCHK(e, hipEventRecord(e->ev_pipe, e->stream));
+    for (uint32_t k = 0; k < P; k++) HIPCHK(e, hipStreamWaitEvent(e->pipes[k]->stream, e->ev_pipe, 0));
+  } else {
+    if (P == 1) pst[0].release();  // one pipeline's staging only: run on the engine stream
+    rc = stage_acquire(e, chunk, fused_stage_flags(call.host, false), st);
+    if (rc) return rc;
+    // several aggregations (one pipeline, says the plan): the pointer table is uploaded once for every launch
+    // of the call (no per-launch host sync)
+    if (call.dense && targets.size() > 1) {
+      rc = upload_targets(e, targets, tbl);
+      if (rc) return rc;
+    }
+  }
+  auto run = [&]() -> int32_t {
+    uint64_t off = 0;
+    for (uint64_t i = 0; i < plan.launches; i++, off += chunk) {
+      jx_engine* q = piped ? e->pipes[i % P] : e;
+      const uint64_t m = (n - off) < chunk ? (n - off) : chunk;
+      FusedIn in{};
+      int32_t r = call.inputs(q, off, m, in);
+      if (r) return r;
+      uint8_t* vout = dv ? dv + off : q->d_verdicts;
+      uint8_t* mout = dm ? dm + off * c.seed : q->d_msgs;
+      r = prep_core(q, m, in.nonces, in.ps, in.his, in.lps, vout, mout, staging_outs(q));
+      if (r) return r;
+      if (piped && i > 0) HIPCHK(e, hipStreamWaitEvent(q->stream, e->ev_pipe, 0));  // the previous launch's K4
+      r = accumulate_into(q, AccSrc{m, staging_outs(q), vout, in.nonces}, nullptr,
+                          call.dense ? call.dense + off : nullptr, targets, tbl.d() ? &tbl : nullptr);
+      if (r) return r;
+      if (piped) HIPCHK(e, hipEventRecord(e->ev_pipe, q->stream));
+      else if (call.host && (r = call.download(vout, mout, off, m))) return r;
+    }
+    return JX_OK;
+  };
+  rc = run();
+  // the join, also after a failed launch: whatever was queued on a pipeline stays ordered before the
+  // engine stream's later work (and jx_engine_sync)
+  for (uint32_t k = 0; piped && k < P; k++) {
+    HIPCHK(e, hipEventRecord(e->pipes[k]->ev_join, e->pipes[k]->stream));
+    HIPCHK(e, hipStreamWaitEvent(e->stream, e->pipes[k]->ev_join, 0));
+  }
+  if (rc || !call.host) return rc;
+  if (piped) return call.download(dv, dm, 0, n);  // the pipelines' kernel timings: jx_engine_timing_read drains them
+  return drain_timing(e);
+}
 
 // ---------------------------------------------------------------------------- C ABI
 
@@ -1839,6 +1918,9 @@ int32_t jx_batch_aggregate_records_device(jx_engine* e, uint64_t batch_id, uint6
                        (uint8_t*)d_out_records);
 }
 
+// Whether the engine's algorithm pipelines its fused calls at all (jx_fused_plan.h).
+static bool fused_pipelines(const Cfg& c) { return c.algo != ALGO_COUNT && c.algo != ALGO_SUMVEC_F64_MULTIPROOF; }
+
 int32_t jx_helper_prep_aggregate(jx_engine* e, uint64_t n, const uint8_t* nonces, const uint8_t* public_shares,
                                  const uint8_t* helper_input_shares, const uint8_t* leader_prep_shares,
                                  uint32_t segment, uint8_t* out_prep_msgs, uint8_t* out_verdicts) {
@@ -1847,91 +1929,34 @@ int32_t jx_helper_prep_aggregate(jx_engine* e, uint64_t n, const uint8_t* nonces
   const Cfg& c = e->cfg;
   if (c.ps_bytes && !public_shares) return JX_E_INVALID;
   HIPCHK(e, hipSetDevice(e->device));
-  const uint64_t chunk = launch_chunk(e, n);
   Segment* seg = nullptr;
   int32_t rc = get_segment(e, segment, &seg);
   if (rc) return rc;
   const std::vector<Segment> targets{*seg};
-  const uint32_t want = pipes_for(e, n, chunk, false, true);
-  Stage pst[MAX_PIPES];
-  uint32_t P = 0;
-  if (want > 1) {
-    rc = pipes_acquire(e, want, chunk, SG_IN | SG_HIN | SG_MEAS | SG_PREP | SG_ACC, pst, &P);
-    if (rc) return rc;
-  }
-  e->last_pipes = P > 1 ? P : 1;
-  if (P > 1) {
-    // the pipelines (see jx_helper_prep_aggregate_device): launch i's host-to-device copies (pageable: the
-    // host thread stages them) go out while the other pipeline's kernels run; the verdicts and prep
-    // messages collect in an engine buffer and come back once, after the join
-    const uint64_t ob = n + (c.jr_len ? n * c.seed : 0);
-    Scratch hout;  // per call, from the arena (handed back after the copies below are queued)
-    rc = scratch_get(e, ob, hout);
-    if (rc) return rc;
-    uint8_t* dv = hout.p();
-    uint8_t* dm = hout.p() + n;
-    HIPCHK(e, hipEventRecord(e->ev_pipe, e->stream));
-    for (uint32_t k = 0; k < P; k++) HIPCHK(e, hipStreamWaitEvent(e->pipes[k]->stream, e->ev_pipe, 0));
-    auto run = [&]() -> int32_t {
-      uint64_t i = 0;
-      for (uint64_t off = 0; off < n; off += chunk, i++) {
-        jx_engine* q = e->pipes[i % P];
-        const uint64_t m = (n - off) < chunk ? (n - off) : chunk;
-        HIPCHK(e, hipMemcpyAsync(q->d_nonces, nonces + off * 16, m * 16, hipMemcpyHostToDevice, q->stream));
-        if (c.ps_bytes)
-          HIPCHK(e, hipMemcpyAsync(q->d_ps, public_shares + off * c.ps_bytes, m * c.ps_bytes, hipMemcpyHostToDevice,
-                                   q->stream));
-        HIPCHK(e, hipMemcpyAsync(q->d_his, helper_input_shares + off * c.his_bytes, m * c.his_bytes,
-                                 hipMemcpyHostToDevice, q->stream));
-        HIPCHK(e, hipMemcpyAsync(q->d_lps, leader_prep_shares + off * c.lps_bytes, m * c.lps_bytes,
-                                 hipMemcpyHostToDevice, q->stream));
-        int32_t r = prep_core(q, m, q->d_nonces, q->d_ps, q->d_his, q->d_lps, dv + off, dm + off * c.seed,
-                              staging_outs(q));
-        if (r) return r;
-        if (i > 0) HIPCHK(e, hipStreamWaitEvent(q->stream, e->ev_pipe, 0));  // the previous launch's K4
-        r = accumulate_into(q, AccSrc{m, staging_outs(q), dv + off, q->d_nonces}, nullptr, nullptr, targets);
-        if (r) return r;
-        HIPCHK(e, hipEventRecord(e->ev_pipe, q->stream));
-      }
-      return JX_OK;
-    };
-    rc = run();
-    for (uint32_t k = 0; k < P; k++) {
-      HIPCHK(e, hipEventRecord(e->pipes[k]->ev_join, e->pipes[k]->stream));
-      HIPCHK(e, hipStreamWaitEvent(e->stream, e->pipes[k]->ev_join, 0));
-    }
-    if (rc) return rc;
-    if (out_verdicts) HIPCHK(e, hipMemcpyAsync(out_verdicts, dv, n, hipMemcpyDeviceToHost, e->stream));
+  const FusedPlan plan =
+      fused_plan(n, e->default_chunk, e->round_reports, e->npipes, fused_pipelines(c), false, true);
+  FusedCall call{};
+  call.host = true;
+  call.inputs = [&](jx_engine* q, uint64_t off, uint64_t m, FusedIn& in) -> int32_t {
+    HIPCHK(e, hipMemcpyAsync(q->d_nonces, nonces + off * 16, m * 16, hipMemcpyHostToDevice, q->stream));
+    if (c.ps_bytes)
+      HIPCHK(e, hipMemcpyAsync(q->d_ps, public_shares + off * c.ps_bytes, m * c.ps_bytes, hipMemcpyHostToDevice,
+                               q->stream));
+    HIPCHK(e, hipMemcpyAsync(q->d_his, helper_input_shares + off * c.his_bytes, m * c.his_bytes,
+                             hipMemcpyHostToDevice, q->stream));
+    HIPCHK(e, hipMemcpyAsync(q->d_lps, leader_prep_shares + off * c.lps_bytes, m * c.lps_bytes,
+                             hipMemcpyHostToDevice, q->stream));
+    in = FusedIn{q->d_nonces, q->d_ps, q->d_his, q->d_lps};
+    return JX_OK;
+  };
+  call.download = [&](const uint8_t* dv, const uint8_t* dm, uint64_t off, uint64_t m) -> int32_t {
+    if (out_verdicts) HIPCHK(e, hipMemcpyAsync(out_verdicts + off, dv, m, hipMemcpyDeviceToHost, e->stream));
     if (out_prep_msgs && c.jr_len)
-      HIPCHK(e, hipMemcpyAsync(out_prep_msgs, dm, n * c.seed, hipMemcpyDeviceToHost, e->stream));
+      HIPCHK(e, hipMemcpyAsync(out_prep_msgs + off * c.seed, dm, m * c.seed, hipMemcpyDeviceToHost, e->stream));
     HIPCHK(e, hipStreamSynchronize(e->stream));
     return JX_OK;
-  }
-  if (P == 1) pst[0].release();  // one pipeline's staging only: run on the engine stream
-  Stage st;
-  rc = stage_acquire(e, chunk, SG_IN | SG_HIN | SG_MEAS | SG_PREP | SG_RES | SG_ACC, st);
-  if (rc) return rc;
-  for (uint64_t off = 0; off < n; off += chunk) {
-    const uint64_t m = (n - off) < chunk ? (n - off) : chunk;
-    HIPCHK(e, hipMemcpyAsync(e->d_nonces, nonces + off * 16, m * 16, hipMemcpyHostToDevice, e->stream));
-    if (c.ps_bytes)
-      HIPCHK(e, hipMemcpyAsync(e->d_ps, public_shares + off * c.ps_bytes, m * c.ps_bytes, hipMemcpyHostToDevice,
-                               e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->d_his, helper_input_shares + off * c.his_bytes, m * c.his_bytes,
-                             hipMemcpyHostToDevice, e->stream));
-    HIPCHK(e, hipMemcpyAsync(e->d_lps, leader_prep_shares + off * c.lps_bytes, m * c.lps_bytes,
-                             hipMemcpyHostToDevice, e->stream));
-    rc = prep_core(e, m, e->d_nonces, e->d_ps, e->d_his, e->d_lps, e->d_verdicts, e->d_msgs, staging_outs(e));
-    if (rc) return rc;
-    rc = accumulate_into(e, AccSrc{m, staging_outs(e), e->d_verdicts, e->d_nonces}, nullptr, nullptr, targets);
-    if (rc) return rc;
-    if (out_verdicts)
-      HIPCHK(e, hipMemcpyAsync(out_verdicts + off, e->d_verdicts, m, hipMemcpyDeviceToHost, e->stream));
-    if (out_prep_msgs && c.jr_len)
-      HIPCHK(e, hipMemcpyAsync(out_prep_msgs + off * c.seed, e->d_msgs, m * c.seed, hipMemcpyDeviceToHost, e->stream));
-    HIPCHK(e, hipStreamSynchronize(e->stream));
-  }
-  return drain_timing(e);
+  };
+  return run_fused(e, n, plan, targets, call);
 }
 
 int32_t jx_helper_prep_aggregate_device(jx_engine* e, uint64_t n, const void* d_nonces, const void* d_ps,
@@ -1943,77 +1968,23 @@ int32_t jx_helper_prep_aggregate_device(jx_engine* e, uint64_t n, const void* d_
   const Cfg& c = e->cfg;
   if (c.ps_bytes && !d_ps) return JX_E_INVALID;
   HIPCHK(e, hipSetDevice(e->device));
-  const uint64_t chunk = launch_chunk(e, n);
   std::vector<Segment> targets;
   int32_t rc = segment_targets(e, segment_ids, nsegments, targets);
   if (rc) return rc;
   const uint8_t *N = (const uint8_t*)d_nonces, *PS = (const uint8_t*)d_ps, *H = (const uint8_t*)d_his,
                 *L = (const uint8_t*)d_lps;
-  const uint32_t* SG = (const uint32_t*)d_segment;
-  const bool many = SG && targets.size() > 1;
-  const uint32_t want = pipes_for(e, n, chunk, many);
-  Stage pst[MAX_PIPES];
-  uint32_t P = 0;
-  if (want > 1) {
-    rc = pipes_acquire(e, want, chunk, SG_MEAS | SG_PREP | SG_RES | SG_ACC, pst, &P);
-    if (rc) return rc;
-  }
-  e->last_pipes = P > 1 ? P : 1;
-  if (P > 1) {
-    // every pipeline orders after the caller's producers (jx_engine_wait_stream / _event act on the
-    // engine stream) and the engine stream after every pipeline (the join), so the call keeps the
-    // single-stream ordering contract
-    HIPCHK(e, hipEventRecord(e->ev_pipe, e->stream));
-    for (uint32_t k = 0; k < P; k++) HIPCHK(e, hipStreamWaitEvent(e->pipes[k]->stream, e->ev_pipe, 0));
-    auto run = [&]() -> int32_t {
-      uint64_t i = 0;
-      for (uint64_t off = 0; off < n; off += chunk, i++) {
-        jx_engine* q = e->pipes[i % P];
-        const uint64_t m = (n - off) < chunk ? (n - off) : chunk;
-        uint8_t* vout = d_out_verdicts ? (uint8_t*)d_out_verdicts + off : q->d_verdicts;
-        uint8_t* mout = (d_out_prep_msgs && c.jr_len) ? (uint8_t*)d_out_prep_msgs + off * c.seed : q->d_msgs;
-        int32_t r = prep_core(q, m, N + off * 16, PS ? PS + off * c.ps_bytes : nullptr, H + off * c.his_bytes,
-                              L + off * c.lps_bytes, vout, mout, staging_outs(q));
-        if (r) return r;
-        if (i > 0) HIPCHK(e, hipStreamWaitEvent(q->stream, e->ev_pipe, 0));  // the previous launch's K4
-        r = accumulate_into(q, AccSrc{m, staging_outs(q), vout, N + off * 16}, nullptr, SG ? SG + off : nullptr,
-                            targets);
-        if (r) return r;
-        HIPCHK(e, hipEventRecord(e->ev_pipe, q->stream));
-      }
-      return JX_OK;
-    };
-    rc = run();
-    // the join, also after a failed launch: whatever was queued on a pipeline stays ordered before the
-    // engine stream's later work (and jx_engine_sync)
-    for (uint32_t k = 0; k < P; k++) {
-      HIPCHK(e, hipEventRecord(e->pipes[k]->ev_join, e->pipes[k]->stream));
-      HIPCHK(e, hipStreamWaitEvent(e->stream, e->pipes[k]->ev_join, 0));
-    }
-    return rc;
-  }
-  if (P == 1) pst[0].release();
-  Stage st;
-  rc = stage_acquire(e, chunk, SG_MEAS | SG_PREP | SG_RES | SG_ACC, st);
-  if (rc) return rc;
-  // the pointer table is uploaded once for every launch of the call (no per-launch host sync)
-  Scratch tbl;
-  if (many) {
-    rc = upload_targets(e, targets, tbl);
-    if (rc) return rc;
-  }
-  for (uint64_t off = 0; off < n; off += chunk) {
-    const uint64_t m = (n - off) < chunk ? (n - off) : chunk;
-    uint8_t* vout = d_out_verdicts ? (uint8_t*)d_out_verdicts + off : e->d_verdicts;
-    uint8_t* mout = (d_out_prep_msgs && c.jr_len) ? (uint8_t*)d_out_prep_msgs + off * c.seed : e->d_msgs;
-    rc = prep_core(e, m, N + off * 16, PS ? PS + off * c.ps_bytes : nullptr, H + off * c.his_bytes,
-                   L + off * c.lps_bytes, vout, mout, staging_outs(e));
-    if (rc) return rc;
-    rc = accumulate_into(e, AccSrc{m, staging_outs(e), vout, N + off * 16}, nullptr, SG ? SG + off : nullptr, targets,
-                         many);
-    if (rc) return rc;
-  }
-  return JX_OK;
+  const bool many = d_segment && targets.size() > 1;
+  const FusedPlan plan =
+      fused_plan(n, e->default_chunk, e->round_reports, e->npipes, fused_pipelines(c), many, false);
+  FusedCall call{};
+  call.inputs = [&](jx_engine*, uint64_t off, uint64_t, FusedIn& in) -> int32_t {
+    in = FusedIn{N + off * 16, PS ? PS + off * c.ps_bytes : nullptr, H + off * c.his_bytes, L + off * c.lps_bytes};
+    return JX_OK;
+  };
+  call.verdicts = (uint8_t*)d_out_verdicts;
+  call.msgs = c.jr_len ? (uint8_t*)d_out_prep_msgs : nullptr;
+  call.dense = (const uint32_t*)d_segment;
+  return run_fused(e, n, plan, targets, call);
 }
 
 int32_t jx_aggregate_read(jx_engine* e, uint32_t segment, uint8_t* out_agg, uint64_t* count) {
@@ -2245,8 +2216,8 @@ int32_t jx_engine_debug(jx_engine* e, int32_t option, int64_t value) {
     e->k1_forced = (K1Kernel)value;
     return JX_OK;
   }
-  if (option == 4) {  // pipelines of the fused device path: 0 automatic, 1 single stream, 2..4
-    if (value < 0 || value > 4) return JX_E_INVALID;
+  if (option == 4) {  // pipelines of the fused device path: 0 automatic, 1 single stream, 2..MAX_PIPES (4)
+    if (value < 0 || value > (int64_t)MAX_PIPES) return JX_E_INVALID;
     e->npipes = (uint32_t)value;
     return JX_OK;
   }

@@ -248,14 +248,8 @@ struct jx_engine {
   std::map<uint64_t, jxi::Batch> batches;
   uint64_t batch_gen = 0;
   std::atomic<uint64_t> last_batch{0};  // a coalesced prepare sets it without the engine mutex
-  // segmented accumulation: pointers into the call's arena scratch while it runs (accumulate_many)
-  uint32_t* d_segx = nullptr;  // cnt, off, cursor [SEG_MAX each], ioff [SEG_MAX + 1], nitems [2]
-  uint32_t* d_perm = nullptr;
-  uint4* d_items = nullptr;
-  uint64_t* d_spart = nullptr;
-  void** d_ptrs = nullptr;  // [3][nptrs]: aggs, counts, checksums of the call's segments (upload_targets)
-  // pinned host copies of the pointer table, double-buffered: buffer k is rewritten only after the
-  // upload that last read it has completed (ev_ptrs[k]), so no call waits for its own work
+  // pinned host copies of the segments' pointer table (upload_targets), double-buffered: buffer k is rewritten
+  // only after the upload that last read it has completed (ev_ptrs[k]), so no call waits for its own work
   void** h_ptrs[2] = {nullptr, nullptr};
   uint64_t h_ptrs_cap[2] = {0, 0};
   hipEvent_t ev_ptrs[2] = {nullptr, nullptr};
@@ -288,7 +282,7 @@ struct jx_engine {
   uint32_t lanes_wg_cap = 2;  // lane-split K1 workgroups per CU (debug option 6; 0: no cap)
   // producer / consumer ordering (jx_engine_wait_stream / jx_engine_join_stream): reused events
   hipEvent_t ev_wait = nullptr, ev_join = nullptr;
-  // Concurrent pipelines of the fused paths (pipes_for): child engines with their own stream run
+  // Concurrent pipelines of the fused paths (fused_plan, run_fused): child engines with their own stream run
   // K1 -> K3 -> K4 of alternate launches, so launches of different phases share the device; the K4s stay
   // in launch order through ev_pipe. Their staging comes from the arena per call.
   std::vector<jx_engine*> pipes;

@@ -1,4 +1,4 @@
-"""GPU: the fused device path with concurrent pipelines (jx_engine.cpp `pipes_for`, debug option 4):
+"""GPU: the fused device path with concurrent pipelines (jx_engine.cpp `run_fused`, jx_fused_plan.h, debug option 4):
 the launches of one jx_helper_prep_aggregate_device call alternate over P child engines (own stream and
 staging) and only their accumulations are ordered. Verdicts, prep messages, aggregate, count and checksum
 must equal the oracle's for P = 1..4, with a ragged last launch, with the inputs produced on torch's stream
@@ -78,6 +78,96 @@ def test_pipes_match_oracle(name, vdaf):
     finally:
         for eng in engs:
             eng.close()
+
+
+VK_SMALL = bytes(range(11, 27))
+N_SMALL = 193  # at 64 reports per launch: three launches of 64 and one of 1
+
+
+@pytest.fixture(scope="module")
+def small():
+    """193 SumVec reports and the oracle's results for them, shared (and left unchanged) by the tests below."""
+    vdaf = Prio3.sum_vec(8, 100, 10)
+    orc, nonces, ps, his, lps = _batch(vdaf, VK_SMALL, N_SMALL, seed=193)
+    want = orc.helper_prep_batch(VK_SMALL, nonces, ps, his, lps, nthreads=16, want_out_shares=True)
+    return vdaf, orc, (nonces, ps, his, lps), want
+
+
+def _expected(orc, want, nonces, sel):
+    """The oracle's (aggregate share, count, checksum) of the finished reports that sel picks."""
+    idx = np.nonzero(sel & (want["verdicts"] == 0))[0]
+    agg = orc.aggregate([want["out_shares"][i].tobytes() for i in idx])
+    cs = bytes(32)
+    for i in idx:
+        cs = bytes(a ^ b for a, b in zip(cs, O.sha256(nonces[i].tobytes())))
+    return agg, len(idx), cs
+
+
+def _to_device(arrays):
+    import torch
+
+    return [torch.from_numpy(np.array(a, copy=True)).to(torch.device("cuda", 0)) for a in arrays]
+
+
+@pytest.mark.parametrize("P", [1, 2, 3, 4])
+def test_staged_results_over_pipes(small, P):
+    """The device form without output arrays: every lane writes its launches' verdicts and prep messages into its
+    own staging. Two calls on one engine (the staging is reused) give the oracle's aggregate, count and checksum,
+    doubled."""
+    vdaf, orc, inputs, want = small
+    d_in = _to_device(inputs)
+    eng = HelperEngine(vdaf, VK_SMALL)
+    eng.debug(5, 64)  # 64 reports per launch
+    with eng:
+        eng.debug(4, P)
+        for _ in range(2):
+            eng.prep_and_aggregate_device(*[d.data_ptr() for d in d_in], N_SMALL)
+        agg, cnt, cs = eng.aggregate_share(0)
+        assert cnt == 2 * want["count"]
+        exp = b"".join(((2 * int.from_bytes(want["agg"][i:i + 16], "little")) % P128).to_bytes(16, "little")
+                       for i in range(0, len(want["agg"]), 16))
+        assert agg == exp
+        assert cs == bytes(32)  # every report id twice: the XOR checksum cancels
+        assert eng.memory()["last_pipelines"] == P
+
+
+def test_segments_force_one_stream(small):
+    """Reports that go to two aggregations by a per-report index run on the engine stream alone, whatever debug
+    option 4 asks for; both aggregations equal the oracle's merge of their reports."""
+    vdaf, orc, inputs, want = small
+    dense = (np.arange(N_SMALL) % 3 == 1).astype(np.uint32)
+    ids = [40, 4]
+    d_in = _to_device(inputs)
+    d_seg = _to_device([dense.astype(np.int32)])[0]
+    eng = HelperEngine(vdaf, VK_SMALL)
+    eng.debug(5, 64)
+    with eng:
+        eng.debug(4, 3)
+        eng.prep_and_aggregate_device(*[d.data_ptr() for d in d_in], N_SMALL, d_segments=d_seg.data_ptr(),
+                                      segment_ids=ids)
+        assert eng.memory()["last_pipelines"] == 1
+        for k, s in enumerate(ids):
+            assert eng.aggregate_share(s) == _expected(orc, want, inputs[0], dense == k), s
+
+
+def test_empty_call(small):
+    """A fused call of no reports, device form and host form, on an engine that holds 64 reports' aggregate:
+    no error, no launch, the aggregate as it was."""
+    vdaf, orc, inputs, want = small
+    d_in = _to_device([a[:64] for a in inputs])
+    eng = HelperEngine(vdaf, VK_SMALL)
+    eng.debug(5, 64)
+    with eng:
+        eng.prep_and_aggregate_device(*[d.data_ptr() for d in d_in], 64)
+        before = eng.aggregate_share(0)
+        assert before == _expected(orc, want, inputs[0], np.arange(N_SMALL) < 64)
+        eng.prep_and_aggregate_device(*[d.data_ptr() for d in d_in], 0)
+        assert eng.memory()["last_pipelines"] == 1
+        assert eng.aggregate_share(0) == before
+        v, m = eng.prep_and_aggregate(*[a[:0] for a in inputs])
+        assert v.shape == (0,) and m.shape[0] == 0
+        assert eng.memory()["last_pipelines"] == 1
+        assert eng.aggregate_share(0) == before
 
 
 @pytest.mark.parametrize("P", [1, 2, 3])
