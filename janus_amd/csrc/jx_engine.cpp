@@ -109,6 +109,9 @@ static void host_hmac_pads(const uint8_t key[32], uint32_t ist[8], uint32_t ost[
   hmac_pads(kbe, ist, ost);
 }
 
+// most gadget calls of a Field128 ParallelSum instance (see make_cfg)
+constexpr uint32_t MAX_PSUM128_CALLS = 1u << 16;
+
 static int32_t make_cfg(const jx_prio3_params* p, const uint8_t* vk, uint32_t vk_len, Cfg& c, std::string& why) {
   memset(&c, 0, sizeof c);
   const bool mp = p->algo_id == ALGO_SUMVEC_F64_MULTIPROOF;
@@ -210,6 +213,13 @@ static int32_t make_cfg(const jx_prio3_params* p, const uint8_t* vk, uint32_t vk
   c.ngt = c.ngroups + c.ngroups1;
   c.qr_len = fp ? 2 : 1;
   c.trunc_len = fp ? p->bits * p->length : c.out_len * c.bits;
+  // Field128 ParallelSum: a lazy wire sum holds one product < 2^256 per call and wacc_reduce (jx_field.h)
+  // takes values < 2^272. FixedPoint stays far below (calls < 2^15, calls1 <= 2^12); the Field64 kernels
+  // fold into add64 and have no such limit.
+  if ((c.algo == ALGO_SUMVEC || c.algo == ALGO_HISTOGRAM) && c.calls > MAX_PSUM128_CALLS) {
+    why = "more than 65536 gadget calls (ceil(measurement length / chunk_length)) in a Field128 ParallelSum";
+    return JX_E_UNSUPPORTED;
+  }
   c.P = next_pow2(1 + c.calls);
   if (mp && c.P > (1u << 30)) {
     why = "too many gadget calls for Field64";
@@ -285,11 +295,25 @@ static void root_tables(f128 gen, uint32_t P, uint32_t logP, uint32_t calls, uin
     omega[k] = h_u4(wk);
     wk = mont128(wk, w);
   }
-  for (uint32_t m = 0; m < glen; m++) {
-    f128 s = make128(0, 0);
-    for (uint32_t k = 1; k <= calls; k++) s = add128(s, pw[(uint64_t)(k * m) % P]);
-    S[m] = h_u4(s);
+  // S_m = sum_{k=1..calls} z^k with z = w^m depends on m mod P only: calls where z = 1 (m = 0 mod P), else
+  // z (z^calls - 1) / (z - 1), the P - 1 inverses out of one h_minv (Montgomery's trick). The plain double
+  // sum is glen * calls additions: most of a minute at 65536 calls.
+  const f128 R1 = make128(R1_128_LO, R1_128_HI);
+  std::vector<f128> d(P), pre(P), Sp(P);  // d[m] = (w^m - 1) R, pre[m] = (d[1] ... d[m]) R
+  pre[0] = R1;
+  for (uint32_t m = 1; m < P; m++) {
+    d[m] = sub128(pw[m], R1);
+    pre[m] = mont128(pre[m - 1], d[m]);
   }
+  f128 inv = h_minv(pre[P - 1]);  // (d[1] ... d[m])^-1 R, m going down
+  Sp[0] = to_mont128(h_from_u64(calls));
+  for (uint32_t m = P - 1; m >= 1; m--) {
+    const f128 dinv = mont128(inv, pre[m - 1]);
+    inv = mont128(inv, d[m]);
+    const f128 zc = pw[((uint64_t)m * calls) % P];
+    Sp[m] = mont128(mont128(pw[m], sub128(zc, R1)), dinv);
+  }
+  for (uint32_t m = 0; m < glen; m++) S[m] = h_u4(Sp[m % P]);
 }
 
 static std::vector<uint4> make_consts(const Cfg& c) {
@@ -1184,6 +1208,7 @@ int32_t jx_engine_create_ex(const jx_prio3_params* params, const uint8_t* verify
                             int32_t device, jx_engine** out) {
   if (!params || !verify_key || !out) return JX_E_INVALID;
   *out = nullptr;
+  t_err.clear();  // a refused parameter set leaves its reason here (jx_last_error takes a null engine)
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return JX_E_NODEVICE;
   if (device < 0 || device >= ndev) return JX_E_INVALID;

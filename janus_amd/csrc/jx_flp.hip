@@ -771,19 +771,12 @@ static void launch_fp_r(const Cfg& c, const Bufs& b, hipStream_t s) {
 
 hipError_t launch_flp(const Cfg& c, const Bufs& b, hipStream_t s) {
   if (c.algo == ALGO_FIXEDPOINT_L2) {
-    if (c.ppw == 2) {
-      if (b.leader)
-        launch_fp_r<2, true>(c, b, s);
-      else
-        launch_fp_r<2, false>(c, b, s);
-    } else if (c.ppw == 1) {
-      if (b.leader)
-        launch_fp_r<1, true>(c, b, s);
-      else
-        launch_fp_r<1, false>(c, b, s);
-    } else {
-      return hipErrorInvalidValue;
-    }
+    // chunk = isqrt(meas_len) >= 6 here, so psum_ppw never picks the one-slot kernel for this instance
+    if (c.ppw != 2) return hipErrorInvalidValue;
+    if (b.leader)
+      launch_fp_r<2, true>(c, b, s);
+    else
+      launch_fp_r<2, false>(c, b, s);
     return hipGetLastError();
   }
   if (c.algo == ALGO_SUM) {

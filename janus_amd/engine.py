@@ -148,7 +148,9 @@ class HelperEngine:
         vk = (ctypes.c_uint8 * len(verify_key)).from_buffer_copy(verify_key)
         st = L.jx_engine_create_ex(ctypes.byref(p), ctypes.cast(vk, ctypes.c_void_p), len(verify_key), device,
                                    ctypes.byref(h))
-        check(st, None, f"jx_engine_create({vdaf.name()})")
+        if st != 0:  # no engine to ask: the reason a parameter set was refused is this thread's last error
+            why = L.jx_last_error(None).decode()
+            raise EngineError(f"jx_engine_create({vdaf.name()}): {L.jx_status_str(st).decode()} ({st}) {why}".strip())
         self._h = h
         sizes = [ctypes.c_uint32() for _ in range(6)]
         check(L.jx_engine_sizes(h, *[ctypes.byref(s) for s in sizes]), h, "jx_engine_sizes")

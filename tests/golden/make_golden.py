@@ -19,6 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from oracle import oracle as O  # noqa: E402
 
+HERE = os.path.dirname(os.path.abspath(__file__))  # where make() writes
 VK = bytes(range(16))
 VK32 = bytes(range(32))  # VERIFY_KEY_LENGTH_HMACSHA256_AES128, core/src/vdaf.rs:24
 
@@ -46,6 +47,36 @@ CONFIGS = {
     "fixedpoint32_100": dict(algo=O.FIXEDPOINT_L2, bits=32, length=100, chunk=0, n=12),
     "fixedpoint16_10000": dict(algo=O.FIXEDPOINT_L2, bits=16, length=10000, chunk=0, n=6),
 }
+LONG_GADGETS = {
+    # Long and degenerate gadgets (tests/test_oracle_long_gadgets.py pins the oracle on these). The FLP
+    # kernels normalise their lazy Field128 wire sums every 512 gadget calls and fold the Field64 ones
+    # every 1024: chunk_length 1 (the one-slot-per-wave kernels) up to and one call past that point,
+    "sumvec_1x512_1": dict(algo=O.SUMVEC, bits=1, length=512, chunk=1, n=12),
+    "sumvec_1x513_1": dict(algo=O.SUMVEC, bits=1, length=513, chunk=1, n=12),
+    "histogram_600_1": dict(algo=O.HISTOGRAM, bits=0, length=600, chunk=1, n=12),
+    "sumvec_f64mp_2_1x1024_1": dict(algo=O.SUMVEC_F64_MULTIPROOF, bits=1, length=1024, chunk=1, proofs=2, n=12),
+    "sumvec_f64mp_2_1x1025_1": dict(algo=O.SUMVEC_F64_MULTIPROOF, bits=1, length=1025, chunk=1, proofs=2, n=12),
+    # the two-slot kernels past it: 1540 = 513 * 3 + 1 (a ragged last call, a half-real last group),
+    # Histogram's sum of x, and an odd proof count (the last proof pair is half empty)
+    "sumvec_2x770_3": dict(algo=O.SUMVEC, bits=2, length=770, chunk=3, n=12),
+    "histogram_1030_2": dict(algo=O.HISTOGRAM, bits=0, length=1030, chunk=2, n=12),
+    "sumvec_f64mp_3_2x1030_2": dict(algo=O.SUMVEC_F64_MULTIPROOF, bits=2, length=1030, chunk=2, proofs=3, n=12),
+    # Long enough that a helper sum which is never normalised wraps 64 bits on honest reports: a 26-bit
+    # limb product of pseudo-random share and coefficient averages 2^50 and the widest Field128 column
+    # takes 5 per call (mean 2^64.4 at 4400 calls); a Field64 column takes one of 2^52 (2^64.45 at 5600)
+    "sumvec_1x4400_1": dict(algo=O.SUMVEC, bits=1, length=4400, chunk=1, n=4),
+    "sumvec_1x8800_2": dict(algo=O.SUMVEC, bits=1, length=8800, chunk=2, n=4),
+    "sumvec_f64mp_2_1x5600_1": dict(algo=O.SUMVEC_F64_MULTIPROOF, bits=1, length=5600, chunk=1, proofs=2, n=4),
+    # one gadget call with chunk_length > the measurement (later slots lie past the share), and three
+    # calls (one fewer than the depth of the kernels' load ring)
+    "sumvec_1x3_5": dict(algo=O.SUMVEC, bits=1, length=3, chunk=5, n=12),
+    "histogram_3_8": dict(algo=O.HISTOGRAM, bits=0, length=3, chunk=8, n=12),
+    "sumvec_f64mp_2_1x3_5": dict(algo=O.SUMVEC_F64_MULTIPROOF, bits=1, length=3, chunk=5, proofs=2, n=12),
+    "sumvec_1x9_3": dict(algo=O.SUMVEC, bits=1, length=9, chunk=3, n=12),
+}
+for _c in LONG_GADGETS.values():  # small files: hashes in place of longer measurements and aggregates, a report per line
+    _c["compact"] = True
+CONFIGS.update(LONG_GADGETS)
 
 
 def measurements(cfg, rng, n):
@@ -100,7 +131,7 @@ def make(name, cfg):
     orc = O.Prio3Oracle(cfg["algo"], cfg["bits"], cfg["length"], cfg["chunk"], proofs)
     s = orc.sizes
     VK = VK32 if s.verify_key == 32 else bytes(range(16))
-    n = cfg["n"]
+    n, compact = cfg["n"], cfg.get("compact", False)
     meas = measurements(cfg, rng, n)
     nonces = rng.integers(0, 256, size=(n, 16), dtype=np.uint8)
     rands = rng.integers(0, 256, size=(n, s.client_rand), dtype=np.uint8)
@@ -113,7 +144,7 @@ def make(name, cfg):
         out = res["out_shares"][i].tobytes() if v == 0 else b""
         m = [int(x) for x in meas[i]]
         rep = {
-            "measurement": m if len(m) <= 1000 else
+            "measurement": m if len(m) <= (16 if compact else 1000) else
             {"sha256_u64le": hashlib.sha256(meas[i].astype("<u8").tobytes()).hexdigest()},
             "nonce": nonces[i].tobytes().hex(),
             "public_share": ps[i].tobytes().hex(),
@@ -137,14 +168,20 @@ def make(name, cfg):
         "verify_key": VK.hex(),
         "sizes": s.__dict__,
         "reports": reports,
-        **({"aggregate_share": res["agg"].hex()} if len(res["agg"]) <= 16000 else
+        **({"aggregate_share": res["agg"].hex()} if len(res["agg"]) <= (256 if compact else 16000) else
            {"aggregate_share_sha256": hashlib.sha256(res["agg"]).hexdigest()}),
         "report_count": res["count"],
         "checksum": res["checksum"].hex(),
     }
-    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), f"{name}.json")
+    path = os.path.join(HERE, f"{name}.json")
     with open(path, "w") as f:
-        json.dump(doc, f, indent=1)
+        if compact:  # the sizes and each report on one line
+            rows = ",\n".join("  " + json.dumps(r) for r in reports)
+            head = json.dumps({**doc, "sizes": 0, "reports": []}, indent=1)
+            f.write(head.replace('"sizes": 0', '"sizes": ' + json.dumps(doc["sizes"]))
+                    .replace('"reports": []', '"reports": [\n' + rows + "\n ]") + "\n")
+        else:
+            json.dump(doc, f, indent=1)
     print(f"{name}: {n} reports, verdicts={[r['verdict'] for r in reports]} -> {path}")
 
 
