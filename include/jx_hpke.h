@@ -96,6 +96,21 @@ int32_t jx_hpke_open_batch(jx_hpke* h, uint64_t n, const uint8_t* encs, const ui
 int32_t jx_hpke_open_batch_device(jx_hpke* h, uint64_t n, const void* d_encs, const void* d_cts,
                                   const uint64_t* d_ct_offsets, const void* d_aads, const uint64_t* d_aad_offsets,
                                   void* d_out_plaintexts, void* d_out_ok);
+/* The same two calls for LONG payloads, such as a leader input share (the whole measurement and proof share: 135 KB
+ * for Prio3SumVec 8x1000/88): the arguments and the contract of jx_hpke_open_batch[_device], and the same bytes in
+ * out_plaintexts (for every report that opens) and out_ok. The calls above open one report per lane, which suits
+ * the helper's 48-byte shares; these run the decapsulation and key schedule one report per lane, then the AEAD one
+ * wave per report (AES-GCM: GHASH and CTR split over the 64 lanes; ChaCha20Poly1305: the same
+ * serial code in one lane of the wave, so no faster than above). The recipient key is read from the device's key
+ * registry; a launch uploads no key material. Scratch (64 bytes per report) comes from the device's arena. A
+ * ciphertext of 2^32 bytes or more is refused with JX_HPKE_E_INVALID before any launch by the host-buffer call,
+ * which sees the offsets; the device-buffer call cannot read them, and its kernel fails that report (ok = 0). */
+int32_t jx_hpke_open_long_batch(jx_hpke* h, uint64_t n, const uint8_t* encs, const uint8_t* cts,
+                                const uint64_t* ct_offsets, const uint8_t* aads, const uint64_t* aad_offsets,
+                                uint8_t* out_plaintexts, uint8_t* out_ok);
+int32_t jx_hpke_open_long_batch_device(jx_hpke* h, uint64_t n, const void* d_encs, const void* d_cts,
+                                       const uint64_t* d_ct_offsets, const void* d_aads, const uint64_t* d_aad_offsets,
+                                       void* d_out_plaintexts, void* d_out_ok);
 /* The context's stream (a hipStream_t), on which jx_hpke_open_batch_device enqueues: for events around an open,
  * or to order other work after it. Created by the first call that needs it (this one included). */
 int32_t jx_hpke_stream(const jx_hpke* h, void** out_stream);

@@ -323,6 +323,47 @@ int32_t jx_leader_prep_init_device_ex(jx_engine* e, uint64_t n, const void* d_no
                                       const void* d_leader_input_shares, uint64_t lis_stride, void* d_out_prep_shares,
                                       void* d_out_verdicts, uint64_t* out_batch_id);
 
+/* ---- The leader's upload path: handle_upload_generic's per-report loop (aggregator/src/aggregator.rs:1513-1694) on
+ * the device, producing the rows jx_leader_prep_init_device_ex reads. Per report: hpke::open of
+ * leader_encrypted_input_share under (InputShare, Client -> Leader) with keypairs[key_index[2i]] and, if that fails to
+ * decrypt, keypairs[key_index[2i + 1]] (the task's keypair, then the global one of the same config id, :1602-1637);
+ * PlaintextInputShare::get_decoded (:1653); A::InputShare::get_decoded_with_param(&(&vdaf, 0), payload) (:1659-1662):
+ * the payload's length must equal jx_engine_leader_sizes' LIS exactly and every element of its measurement-share and
+ * proofs-share parts must be < p (the blind is opaque), for every algo id 0-5. The three time checks of the handler
+ * are the caller's (they need no report bytes). Arguments as in jx_helper_prep_encrypted_batch2:
+ *   report_ids[n x 16], times[n], public_shares[n x PS] (fixed-length rows: a report with another length is the
+ *   caller's to reject), task_id, keypairs (contexts created with the (InputShare, Client -> Leader) application
+ *   info; their keys are read from the device's key registry, the call uploads no key material), key_index[n x 2]
+ *   (JX_KEY_NONE / JX_KEY_MALFORMED as there), encs with enc_offsets[n + 1] (NULL: n x 32 bytes), payloads with
+ *   payload_offsets[n + 1] (each ciphertext < 2^32 bytes). The associated data, the encoded InputShareAad, is built
+ *   on the device.
+ * out_status[i] reuses the JX_OPEN_* codes: JX_OPEN_UNKNOWN_CONFIG is Janus's ReportRejectionReason::
+ * OutdatedHpkeConfig, JX_OPEN_HPKE_DECRYPT_ERROR is DecryptFailure, JX_OPEN_PLAINTEXT_DECODE_FAILURE (the framing: a
+ * truncated list, an unknown extension type, bytes after the payload) and JX_OPEN_INPUT_SHARE_DECODE_FAILURE (the
+ * payload: its length, an element >= p) are both DecodeFailure and stay distinct for the logs; JX_OPEN_OK the rest.
+ * The upload handler makes no duplicate-extension and no taskprov checks (:1653-1678), so codes 3-5
+ * (JX_OPEN_DUPLICATE_EXTENSION, JX_OPEN_UNEXPECTED_TASKPROV, JX_OPEN_MISSING_TASKPROV) never occur here.
+ * An accepted report's payload goes to row i of the output (host call: rows of LIS bytes; device call: rows of
+ * lis_stride bytes, 0 = LIS, else >= LIS and a multiple of 16, zero padded; d_out_rows 16-byte aligned); a rejected
+ * report's row is zeros. Report i's extension list, without its u16 length prefix, goes to out_extensions +
+ * payload_offsets[i] (the buffer is as long as payloads) with its length in out_ext_len[i] (0 for a rejected report).
+ * The call runs on the engine's stream with scratch from the device's arena and is not coalesced (upload batches
+ * come from the report writer's own batcher). The device call takes device pointers for the bulk data (report ids,
+ * public shares, encapsulated keys, payloads, the four outputs) and HOST arrays for times, key_index and the two
+ * offset arrays; it returns once its launches are queued. */
+int32_t jx_leader_upload_open_batch(jx_engine* e, uint64_t n, const uint8_t* report_ids, const uint64_t* times,
+                                    const uint8_t* public_shares, const uint8_t task_id[32], jx_hpke* const* keypairs,
+                                    uint32_t nkeypairs, const uint8_t* key_index, const uint8_t* encs,
+                                    const uint64_t* enc_offsets, const uint8_t* payloads, const uint64_t* payload_offsets,
+                                    uint8_t* out_leader_input_shares, uint8_t* out_extensions, uint32_t* out_ext_len,
+                                    uint8_t* out_status);
+int32_t jx_leader_upload_open_device(jx_engine* e, uint64_t n, const void* d_report_ids, const uint64_t* times,
+                                     const void* d_public_shares, const uint8_t task_id[32], jx_hpke* const* keypairs,
+                                     uint32_t nkeypairs, const uint8_t* key_index, const void* d_encs,
+                                     const uint64_t* enc_offsets, const void* d_payloads, const uint64_t* payload_offsets,
+                                     void* d_out_rows, uint64_t lis_stride, void* d_out_extensions, void* d_out_ext_len,
+                                     void* d_out_status);
+
 /* Accumulate the output shares of the resident batch `batch_id` (helper, or leader after finish) into
  * the engine's running batch aggregations (the engine as one shard, §8e): report i is added iff
  * verdict == FINISHED and accept_mask[i] != 0 (accept_mask nullable = all), into aggregation

@@ -24,7 +24,7 @@ EXPORTED_SYMBOLS = (
     "jx_engine_timing_read", "jx_engine_debug", "jx_status_str", "jx_last_error",
     "jx_engine_wait_stream", "jx_engine_join_stream", "jx_engine_wait_event", "jx_engine_record_event",
     "jx_engine_memory", "jx_engine_coalesce", "jx_leader_prep_init_device_ex", "jx_helper_prep_encrypted_batch",
-    "jx_helper_prep_encrypted_batch2",
+    "jx_helper_prep_encrypted_batch2", "jx_leader_upload_open_batch", "jx_leader_upload_open_device",
 )
 
 _lib = None
@@ -79,6 +79,10 @@ def load():
                                                   u32, u8p, u8p, u8p, u8p, P(u64)]),
         "jx_helper_prep_encrypted_batch2": (i32, [vp, u64, u8p, P(u64), u8p, u8p, P(vp), u32, u8p, u8p, P(u64), u8p,
                                                    P(u64), u32, u8p, u8p, u8p, u8p, P(u64)]),
+        "jx_leader_upload_open_batch": (i32, [vp, u64, u8p, P(u64), u8p, u8p, P(vp), u32, u8p, u8p, P(u64), u8p,
+                                               P(u64), u8p, u8p, P(u32), u8p]),
+        "jx_leader_upload_open_device": (i32, [vp, u64, vp, P(u64), vp, u8p, P(vp), u32, u8p, vp, P(u64), vp, P(u64),
+                                                vp, u64, vp, vp, vp]),
         "jx_engine_batch_id": (i32, [vp, P(u64)]),
         "jx_engine_batches": (i32, [vp, P(u64), P(u64)]),
         "jx_batch_release": (i32, [vp, u64]),

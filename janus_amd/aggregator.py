@@ -19,6 +19,7 @@ engine's running aggregations.
 """
 from __future__ import annotations
 
+import enum
 from collections import Counter
 from dataclasses import dataclass, field
 
@@ -480,3 +481,148 @@ def _open_alone(pi: PrepareInit, opener, hpke_config_id: int, globals_: dict, ta
     else:
         failures["public_share_decode_failure"] += 1
     return PrepareError.InvalidMessage
+
+
+# ----------------------------------------------------------------------------- upload (leader)
+
+
+class ReportRejectionReason(enum.Enum):  # aggregator/src/aggregator/error.rs:220-228
+    IntervalCollected = "interval_collected"
+    DecryptFailure = "decrypt_failure"
+    DecodeFailure = "decode_failure"
+    TaskExpired = "task_expired"
+    Expired = "expired"
+    TooEarly = "too_early"
+    OutdatedHpkeConfig = "outdated_hpke_config"
+
+
+@dataclass(frozen=True)
+class ReportRejection:
+    """ReportRejection::new(task_id, report_id, time, reason) (:1538); config_id: OutdatedHpkeConfig's."""
+
+    task_id: bytes
+    report_id: bytes
+    time: int
+    reason: ReportRejectionReason
+    config_id: int | None = None
+
+
+@dataclass(frozen=True)
+class StoredReport:
+    """LeaderStoredReport::new (:1680-1687) with the leader input share left on the device: `row` is its row of
+    UploadOutcome.rows, which leader_init_device reads in place."""
+
+    task_id: bytes
+    metadata: ReportMetadata
+    public_share: bytes
+    extensions: tuple
+    row: int
+    helper_encrypted_input_share: HpkeCiphertext
+
+
+@dataclass
+class UploadTask:
+    """What handle_upload_generic reads of an AggregatorTask: hpke_keys are the task's keypairs by config id,
+    janus_amd.hpke.HpkeOpener contexts created with application_info(recipient=ROLE_LEADER)."""
+
+    task_id: bytes
+    hpke_keys: dict
+    tolerable_clock_skew: int = 0
+    task_expiration: int | None = None
+    report_expiry_age: int | None = None
+
+
+@dataclass
+class UploadOutcome:
+    results: list                        # per report: StoredReport or ReportRejection
+    rows: object = None                  # torch uint8[m, lis_stride] on the device (None: no report reached it)
+    lis_stride: int = 0
+    status: dict = field(default_factory=dict)      # report index -> open status (OPEN_STATUS key) where not OK
+    counters: Counter = field(default_factory=Counter)  # upload_decrypt_failure / upload_decode_failure
+
+
+def handle_upload(engine: HelperEngine, task: UploadTask, reports: list, now: int, global_keypairs=None,
+                  lis_stride: int = 0) -> UploadOutcome:
+    """VdafOps::handle_upload_generic (aggregator/src/aggregator.rs:1513-1694) for a batch of Reports (encoded
+    bytes or messages.Report), in the reference's order per report: the three time checks on the host (TooEarly:
+    time after now + tolerable_clock_skew, :1544-1553; TaskExpired, :1557-1561; Expired: now after time +
+    report_expiry_age, :1564-1573), the public share's length (DecodeFailure, :1580-1593), then for all that are
+    left one engine.leader_upload_open: HPKE open with the task's keypair and then the global one of the same
+    config id (OutdatedHpkeConfig when neither exists, DecryptFailure, :1602-1651), PlaintextInputShare and leader
+    input share decode (DecodeFailure, :1653-1678). Each report maps to a StoredReport (what goes to the report
+    writer; its input share stays on the device) or to a ReportRejection."""
+    from .engine import KEY_NONE, OPEN_OK
+    from .messages import Report
+
+    v = engine.vdaf
+    reports = [Report.decode(r) if isinstance(r, (bytes, bytearray)) else r for r in reports]
+    out = UploadOutcome([None] * len(reports))
+
+    def reject(i: int, reason: ReportRejectionReason, config_id: int | None = None):
+        md = reports[i].metadata
+        out.results[i] = ReportRejection(task.task_id, md.report_id, md.time, reason, config_id)
+
+    globals_ = dict(global_keypairs or {})
+    keypairs: list = []
+    slot: dict[int, int] = {}
+
+    def key_slot(k) -> int:
+        if id(k) not in slot:
+            slot[id(k)] = len(keypairs)
+            keypairs.append(k)
+        return slot[id(k)]
+
+    deadline = now + task.tolerable_clock_skew
+    rows: list[int] = []
+    key_index = []
+    for i, r in enumerate(reports):
+        t = r.metadata.time
+        if t > deadline:
+            reject(i, ReportRejectionReason.TooEarly)
+        elif task.task_expiration is not None and t > task.task_expiration:
+            reject(i, ReportRejectionReason.TaskExpired)
+        elif task.report_expiry_age is not None and now > t + task.report_expiry_age:
+            reject(i, ReportRejectionReason.Expired)
+        elif len(r.public_share) != v.public_share_len:
+            out.counters["upload_decode_failure"] += 1
+            reject(i, ReportRejectionReason.DecodeFailure)
+        else:
+            cfg = r.leader_encrypted_input_share.config_id
+            task_k, glob_k = task.hpke_keys.get(cfg), globals_.get(cfg)
+            first, second = (task_k, glob_k) if task_k is not None else (glob_k, None)
+            if first is None:
+                key_index.append((KEY_NONE, KEY_NONE))
+            else:
+                key_index.append((key_slot(first), key_slot(second) if second is not None else KEY_NONE))
+            if len(keypairs) > 8:
+                raise ValueError("more than JX_ENC_MAX_KEYPAIRS distinct keypairs in one upload batch")
+            rows.append(i)
+    if not rows:
+        return out
+    md = [reports[i].metadata for i in rows]
+    res = engine.leader_upload_open(
+        np.frombuffer(b"".join(x.report_id for x in md), np.uint8).reshape(len(rows), 16),
+        np.array([x.time for x in md], np.uint64),
+        np.frombuffer(b"".join(reports[i].public_share for i in rows), np.uint8), task.task_id, keypairs,
+        np.array(key_index, np.uint8), [reports[i].leader_encrypted_input_share.encapsulated_key for i in rows],
+        [reports[i].leader_encrypted_input_share.payload for i in rows], lis_stride=lis_stride)
+    out.rows, out.lis_stride = res.rows, res.lis_stride
+    for j, i in enumerate(rows):
+        st = int(res.status[j])
+        r = reports[i]
+        if st == OPEN_OK:
+            exts = PlaintextInputShare.decode(len(res.extensions[j]).to_bytes(2, "big") + res.extensions[j] +
+                                              bytes(4)).extensions
+            out.results[i] = StoredReport(task.task_id, r.metadata, r.public_share, exts, j,
+                                          r.helper_encrypted_input_share)
+            continue
+        out.status[i] = st
+        if st == 7:  # JX_OPEN_UNKNOWN_CONFIG
+            reject(i, ReportRejectionReason.OutdatedHpkeConfig, r.leader_encrypted_input_share.config_id)
+        elif st == 1:  # JX_OPEN_HPKE_DECRYPT_ERROR
+            out.counters["upload_decrypt_failure"] += 1
+            reject(i, ReportRejectionReason.DecryptFailure)
+        else:  # the plaintext's framing (2) or the input share (6)
+            out.counters["upload_decode_failure"] += 1
+            reject(i, ReportRejectionReason.DecodeFailure)
+    return out

@@ -36,6 +36,7 @@
 
 #include "../../include/jx_hpke.h"
 #include "jx_engine_internal.h"
+#include "jx_hpke_long.h"
 #include "jx_hpke_open.h"
 #include "jx_hpke_suites.h"
 #include "jx_keyreg.h"
@@ -359,6 +360,102 @@ int32_t jx_hpke_open_batch(jx_hpke* h, uint64_t n, const uint8_t* encs, const ui
       rc = hfail(JX_HPKE_E_HIP, "kernel launch failed");
       break;
     }
+    if ((pt_bytes && hipMemcpyAsync(out_plaintexts, base + o_pt, pt_bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess) ||
+        hipMemcpyAsync(out_ok, base + o_ok, n, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess) {
+      rc = hfail(JX_HPKE_E_HIP, "device-to-host copy failed");
+      break;
+    }
+  } while (0);
+  jxi::arena_put(h->arena, slab, h->stream);  // reused after this stream's work
+  return rc;
+}
+
+// ---- the wave-per-report open of long payloads (jx_hpke_long.hip)
+
+// with h->mu held and the device set: both stages on the context's stream, the context rows in a slab of the
+// arena that goes back stream-ordered
+static int32_t launch_open_long(jx_hpke* h, const HpkeBufs& b) {
+  const HpkeKeyRow* rows = nullptr;
+  uint32_t cap = 0;
+  jxi::hpke_registry(h->device, &rows, &cap);
+  jxi::Slab slab;
+  const hipError_t ga = jxi::arena_get(h->arena, jxi::align256(b.n * sizeof(LongCtxRow)), h->stream, true, true, slab);
+  if (ga == hipErrorOutOfMemory) return hfail(JX_HPKE_E_NOMEM, "device allocation failed (arena)");
+  HCHK(ga);
+  LongCtxArgs ca{};
+  ca.n = b.n;
+  ca.keys = rows;
+  ca.slot = h->slot;
+  ca.encs = b.encs;
+  ca.out = (LongCtxRow*)slab.p;
+  memcpy(ca.zero_ist, h->cfg.zero_ist, 32);
+  memcpy(ca.zero_ost, h->cfg.zero_ost, 32);
+  const hipError_t st = launch_hpke_long_open(ca, h->kem == HPKE_KEM_P256_SHA256, b, h->stream);
+  jxi::arena_put(h->arena, slab, h->stream);
+  if (st != hipSuccess) return hfail(JX_HPKE_E_HIP, std::string("long open launch: ") + hipGetErrorString(st));
+  return JX_HPKE_OK;
+}
+
+int32_t jx_hpke_open_long_batch_device(jx_hpke* h, uint64_t n, const void* d_encs, const void* d_cts,
+                                       const uint64_t* d_ct_offsets, const void* d_aads, const uint64_t* d_aad_offsets,
+                                       void* d_out_plaintexts, void* d_out_ok) {
+  if (!h || (n && (!d_encs || !d_cts || !d_ct_offsets || !d_aad_offsets || !d_out_plaintexts || !d_out_ok))) {
+    return JX_HPKE_E_INVALID;
+  }
+  if (n == 0) return JX_HPKE_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HCHK(hipSetDevice(h->device));
+  if (const int32_t rc = ensure_stream(h)) return rc;
+  HpkeBufs b{n,
+             (const uint8_t*)d_encs,
+             (const uint8_t*)d_cts,
+             d_ct_offsets,
+             (const uint8_t*)d_aads,
+             d_aad_offsets,
+             (uint8_t*)d_out_plaintexts,
+             (uint8_t*)d_out_ok};
+  return launch_open_long(h, b);
+}
+
+int32_t jx_hpke_open_long_batch(jx_hpke* h, uint64_t n, const uint8_t* encs, const uint8_t* cts,
+                                const uint64_t* ct_offsets, const uint8_t* aads, const uint64_t* aad_offsets,
+                                uint8_t* out_plaintexts, uint8_t* out_ok) {
+  if (!h || (n && (!encs || !cts || !ct_offsets || !aad_offsets || !out_plaintexts || !out_ok)))
+    return JX_HPKE_E_INVALID;
+  if (n == 0) return JX_HPKE_OK;
+  for (uint64_t i = 0; i < n; i++) {
+    if (ct_offsets[i + 1] < ct_offsets[i] + 16 || aad_offsets[i + 1] < aad_offsets[i])
+      return hfail(JX_HPKE_E_INVALID, "offsets must be non-decreasing and every ciphertext >= 16 bytes");
+    if (ct_offsets[i + 1] - ct_offsets[i] >= (1ull << 32))
+      return hfail(JX_HPKE_E_INVALID, "a ciphertext of 2^32 bytes or more is no report share");
+  }
+  std::lock_guard<std::mutex> lk(h->mu);
+  HCHK(hipSetDevice(h->device));
+  if (const int32_t rc = ensure_stream(h)) return rc;
+  const uint64_t ct_bytes = ct_offsets[n], aad_bytes = aad_offsets[n], pt_bytes = ct_bytes - 16 * n;
+  const uint64_t enc_bytes = n * hpke_enc_len(h->kem);
+  const size_t o_enc = 0, o_ct = o_enc + jxi::align256(enc_bytes), o_aad = o_ct + jxi::align256(ct_bytes),
+               o_pt = o_aad + jxi::align256(aad_bytes ? aad_bytes : 1), o_ok = o_pt + jxi::align256(pt_bytes ? pt_bytes : 1),
+               o_co = o_ok + jxi::align256(n), o_ao = o_co + jxi::align256((n + 1) * 8), bytes = o_ao + jxi::align256((n + 1) * 8);
+  jxi::Slab slab;
+  const hipError_t ga = jxi::arena_get(h->arena, bytes, h->stream, true, true, slab);
+  if (ga == hipErrorOutOfMemory) return hfail(JX_HPKE_E_NOMEM, "device allocation failed (arena)");
+  HCHK(ga);
+  uint8_t* base = (uint8_t*)slab.p;
+  int32_t rc = JX_HPKE_OK;
+  do {
+    if (hipMemcpyAsync(base + o_enc, encs, enc_bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipMemcpyAsync(base + o_ct, cts, ct_bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        (aad_bytes && hipMemcpyAsync(base + o_aad, aads, aad_bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) ||
+        hipMemcpyAsync(base + o_co, ct_offsets, (n + 1) * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipMemcpyAsync(base + o_ao, aad_offsets, (n + 1) * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+      rc = hfail(JX_HPKE_E_HIP, "host-to-device copy failed");
+      break;
+    }
+    HpkeBufs b{n, base + o_enc, base + o_ct, (const uint64_t*)(base + o_co), base + o_aad, (const uint64_t*)(base + o_ao),
+               base + o_pt, base + o_ok};
+    if ((rc = launch_open_long(h, b)) != JX_HPKE_OK) break;
     if ((pt_bytes && hipMemcpyAsync(out_plaintexts, base + o_pt, pt_bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess) ||
         hipMemcpyAsync(out_ok, base + o_ok, n, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
         hipStreamSynchronize(h->stream) != hipSuccess) {

@@ -125,6 +125,14 @@ class EncryptedResult:
     batch_id: int = 0
 
 
+@dataclass
+class UploadOpen:
+    status: np.ndarray         # uint8[n]: OPEN_OK or an OPEN_STATUS key (never 3-5: the upload path has no such checks)
+    extensions: list           # per report: its extension list's bytes, without the u16 prefix (b"" when rejected)
+    rows: object               # torch uint8[n, lis_stride] on the device: the leader input shares, zeros when rejected
+    lis_stride: int
+
+
 class HelperEngine:
     """One engine per (Prio3 instance, verify key, GPU). Serves the helper role (the north-star
     path) and the leader role of the same ping-pong exchange."""
@@ -433,6 +441,67 @@ class HelperEngine:
                                                        lis_stride, d_out_prep_shares, d_out_verdicts, ctypes.byref(bid))
             check(st, self._h, "jx_leader_prep_init_device_ex")
         return bid.value
+
+    def leader_upload_open(self, report_ids, times, public_shares, task_id: bytes, keypairs, key_index, encs,
+                           payloads: list[bytes], lis_stride: int = 0, stream=None) -> "UploadOpen":
+        """The leader's upload loop for n reports (handle_upload_generic, aggregator.rs:1513-1694) on the GPU
+        (jx_leader_upload_open_device): report i's leader_encrypted_input_share is opened with
+        keypairs[key_index[i][0]] (then keypairs[key_index[i][1]] if that fails to decrypt; KEY_NONE: none), its
+        PlaintextInputShare decoded, its payload checked as the leader input share (exact length, every element
+        < p) and laid out as row i of a device tensor. keypairs: janus_amd.hpke.HpkeOpener contexts created with
+        the (InputShare, Client -> Leader) application info on this engine's device; encs: an (n, 32) array or a
+        list of encapsulated keys of any lengths. lis_stride: 0 (rows of leader_input_share_len) or a multiple of
+        16 that is at least that. Returns the status per report (OPEN_OK or an OPEN_STATUS key), each report's
+        extension bytes and the rows, which `leader_init_device(n, ..., rows.data_ptr(), ..., lis_stride=...)`
+        reads in place (rejected reports: zeros). The inputs go through torch tensors on the engine's device;
+        the call is ordered against `stream` like the other device-pointer methods and waits for its results."""
+        import torch
+
+        n = int(np.asarray(report_ids).reshape(-1, 16).shape[0])
+        ids = _u8(report_ids, n, 16, "report_ids")
+        ps = _u8(public_shares, n, self.public_share_len, "public_shares")
+        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
+        ki = np.ascontiguousarray(np.asarray(key_index, dtype=np.uint8).reshape(n, 2)) if n else np.zeros((1, 2), np.uint8)
+        if isinstance(encs, (list, tuple)):
+            if len(encs) != n:
+                raise ValueError("one encapsulated key per report")
+            en = np.frombuffer(b"".join(bytes(x) for x in encs) or b"\0", np.uint8).copy()
+            eoff = np.zeros(n + 1, np.uint64)
+            if n:
+                eoff[1:] = np.cumsum([len(x) for x in encs])
+        else:
+            en = _u8(encs, n, 32, "encs").reshape(-1) if n else np.zeros(32, np.uint8)
+            eoff = np.arange(n + 1, dtype=np.uint64) * 32
+        if len(task_id) != 32 or len(payloads) != n:
+            raise ValueError("task id is 32 bytes; one payload per report")
+        off = np.zeros(n + 1, np.uint64)
+        if n:
+            off[1:] = np.cumsum([len(p) for p in payloads])
+        ct = np.frombuffer(b"".join(payloads) or b"\0", np.uint8).copy()
+        task = np.frombuffer(task_id, np.uint8).copy()
+        hs = (ctypes.c_void_p * max(1, len(keypairs)))(*[k.handle for k in keypairs])
+        stride = lis_stride or self.leader_input_share_len
+        dev = torch.device("cuda", self.device)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        with torch.cuda.device(dev):
+            d_ids, d_ps, d_en, d_ct = (torch.from_numpy(a.reshape(-1).copy()).to(dev) for a in (ids, ps, en, ct))
+            # 16 spare bytes: the rows start at the tensor's next 16-byte boundary whatever the allocator gives
+            d_rows = torch.zeros(max(n, 1) * stride + 16, dtype=torch.uint8, device=dev)
+            skew = (-d_rows.data_ptr()) % 16
+            rows = d_rows[skew:skew + max(n, 1) * stride].view(max(n, 1), stride)
+            d_ext = torch.zeros(ct.size, dtype=torch.uint8, device=dev)
+            d_len = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+            d_st = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
+            with self._ordered(stream):
+                st = self._L.jx_leader_upload_open_device(
+                    self._h, n, d_ids.data_ptr(), tm.ctypes.data_as(u64p),
+                    d_ps.data_ptr() if self.public_share_len else None, _ptr(task), hs, len(keypairs), _ptr(ki),
+                    d_en.data_ptr(), eoff.ctypes.data_as(u64p), d_ct.data_ptr(), off.ctypes.data_as(u64p),
+                    rows.data_ptr(), lis_stride, d_ext.data_ptr(), d_len.data_ptr(), d_st.data_ptr())
+                check(st, self._h, "jx_leader_upload_open_device")
+            status, ext_len, ext = d_st.cpu().numpy()[:n], d_len.cpu().numpy()[:n], d_ext.cpu().numpy()
+        exts = [ext[int(off[i]):int(off[i]) + int(ext_len[i])].tobytes() for i in range(n)]
+        return UploadOpen(status, exts, rows[:n], stride)
 
     def leader_finish_device(self, batch_id: int, n: int, d_prep_msgs: int | None, d_peer_verdicts: int | None = None,
                              d_out_verdicts: int | None = None, stream=None):

@@ -35,7 +35,8 @@ E_INVALID = -1  # JX_HPKE_E_INVALID
 
 EXPORTED_SYMBOLS = ("jx_hpke_create", "jx_hpke_create_suite", "jx_hpke_create_key", "jx_hpke_suite", "jx_hpke_enc_len",
                     "jx_hpke_stream", "jx_hpke_destroy",
-                    "jx_hpke_open_batch", "jx_hpke_open_batch_device", "jx_hpke_last_error")
+                    "jx_hpke_open_batch", "jx_hpke_open_batch_device", "jx_hpke_open_long_batch",
+                    "jx_hpke_open_long_batch_device", "jx_hpke_last_error")
 
 
 class UnsupportedSuite(EngineError):
@@ -77,6 +78,10 @@ def _declare(L):
     L.jx_hpke_open_batch.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
     L.jx_hpke_open_batch_device.restype = i32
     L.jx_hpke_open_batch_device.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
+    for name in ("jx_hpke_open_long_batch", "jx_hpke_open_long_batch_device"):
+        f = getattr(L, name)  # a library without them is an error here, not a fall-back to the per-lane open
+        f.restype = i32
+        f.argtypes = [vp, u64, vp, vp, vp, vp, vp, vp, vp]
     L.jx_hpke_last_error.restype = ctypes.c_char_p
     L.jx_hpke_last_error.argtypes = [vp]
     L._jx_hpke_declared = True
@@ -160,7 +165,13 @@ class HpkeOpener:
     def __exit__(self, *a):
         self.close()
 
-    def open_batch(self, encs: list[bytes], ciphertexts: list[bytes], aads: list[bytes]) -> list[bytes | None]:
+    def open_long_batch(self, encs: list[bytes], ciphertexts: list[bytes], aads: list[bytes]) -> list[bytes | None]:
+        """open_batch for long payloads such as leader input shares (jx_hpke_open_long_batch): the same results,
+        with the AEAD of each report spread over a wave instead of chained in one lane."""
+        return self.open_batch(encs, ciphertexts, aads, _call="jx_hpke_open_long_batch")
+
+    def open_batch(self, encs: list[bytes], ciphertexts: list[bytes], aads: list[bytes],
+                   _call: str = "jx_hpke_open_batch") -> list[bytes | None]:
         """Open n HPKE ciphertexts; None where opening fails (PrepareError::HpkeDecryptError)."""
         n = len(encs)
         if not (len(ciphertexts) == len(aads) == n):
@@ -182,9 +193,9 @@ class HpkeOpener:
         ao[1:] = np.cumsum([len(aads[i]) for i in idx])
         pts = np.zeros(max(1, int(co[-1]) - 16 * len(idx)), np.uint8)
         ok = np.zeros(len(idx), np.uint8)
-        st = self._L.jx_hpke_open_batch(self._h, len(idx), _p(enc), _p(cts), _p(co), _p(aad), _p(ao), _p(pts), _p(ok))
+        st = getattr(self._L, _call)(self._h, len(idx), _p(enc), _p(cts), _p(co), _p(aad), _p(ao), _p(pts), _p(ok))
         if st != 0:
-            raise EngineError(f"jx_hpke_open_batch: status {st} {self._L.jx_hpke_last_error(self._h).decode()}")
+            raise EngineError(f"{_call}: status {st} {self._L.jx_hpke_last_error(self._h).decode()}")
         for j, i in enumerate(idx):
             if ok[j]:
                 a = int(co[j]) - 16 * j

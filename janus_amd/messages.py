@@ -137,6 +137,37 @@ class HpkeCiphertext:
     def encode(self) -> bytes:
         return bytes([self.config_id]) + _o16(self.encapsulated_key) + _o32(self.payload)
 
+    @classmethod
+    def decode_from(cls, r: _Reader) -> "HpkeCiphertext":
+        return cls(r.u8(), r.opaque16(), r.opaque32())
+
+
+@dataclass(frozen=True)
+class Report:
+    """A client report as uploaded to the leader (messages/src/lib.rs:1353-1432): metadata || u32-prefixed public
+    share || leader_encrypted_input_share || helper_encrypted_input_share."""
+
+    metadata: ReportMetadata
+    public_share: bytes
+    leader_encrypted_input_share: HpkeCiphertext
+    helper_encrypted_input_share: HpkeCiphertext
+
+    MEDIA_TYPE = "application/dap-report"
+
+    def encode(self) -> bytes:
+        return (self.metadata.encode() + _o32(self.public_share) + self.leader_encrypted_input_share.encode() +
+                self.helper_encrypted_input_share.encode())
+
+    @classmethod
+    def decode(cls, b: bytes) -> "Report":
+        r = _Reader(b)
+        md = ReportMetadata(r.take(16), r.u64())
+        ps = r.opaque32()
+        leader = HpkeCiphertext.decode_from(r)
+        helper = HpkeCiphertext.decode_from(r)
+        r.done()
+        return cls(md, ps, leader, helper)
+
 
 @dataclass(frozen=True)
 class ReportShare:
