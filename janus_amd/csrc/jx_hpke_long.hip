@@ -17,10 +17,14 @@
 //     compares with E(J0) ^ tag. Only then CTR: lane j decrypts counter blocks 2 + j, 2 + j + 64, .... A block is
 //     read as one or two aligned 16-byte loads and shifted into place, so a payload at any byte offset costs the
 //     same loads; it is stored as 16 bytes, four words or bytes, as the output's alignment allows.
-//     ChaCha20Poly1305 runs the serial code of jx_chapoly.h in lane 0 of the wave: the same entry points and
-//     results, no speed-up (its speed is not what this unit is for).
+//     ChaCha20Poly1305 has the same shape (jx_chapoly_lanes.h): every lane derives the one-time key from keystream
+//     block 0; lane j owns Poly1305 blocks j, j + 64, ... of AAD blocks || ciphertext blocks || the length block,
+//     Horner in r^64 with a plain five-limb product (no table), then one product by r^(d_j); the wave adds the
+//     partials limb-wise by __shfl_xor, finishes the tag and compares. Only then ChaCha20: lane j decrypts the
+//     64-byte blocks j, j + 64, ... under counters 1 + j, 1 + j + 64, ..., each as four 16-byte pieces.
 #include <hip/hip_runtime.h>
 
+#include "jx_chapoly_lanes.h"
 #include "jx_ghash_lanes.h"
 #include "jx_hpke_long.h"
 #include "jx_hpke_suites.h"
@@ -205,20 +209,91 @@ __device__ bool gcm_wave_open(const uint32_t* tt, uint32_t* m4, uint32_t lane, c
   return true;
 }
 
-// The AEAD of the context row by the whole wave; every lane returns the same verdict.
-template <class AadLd, class AadByte>
+__device__ __forceinline__ void shfl5(uint32_t out[5], const uint32_t in[5], uint32_t src) {
+#pragma unroll
+  for (int k = 0; k < 5; k++) out[k] = __shfl(in[k], (int)src);
+}
+
+// ChaCha20-Poly1305 open by the whole wave; every lane returns the same verdict. aad_ld as for gcm_wave_open: its
+// zero-padded little-endian words are Poly1305's byte order. Every shuffle sits outside the per-lane block loops.
+template <class AadLd>
+__device__ bool chapoly_wave_open(uint32_t lane, const LongCtxRow& c, AadLd aad_ld, uint64_t alen, const uint8_t* ct,
+                                  uint64_t clen, uint8_t* pt) {
+  uint32_t ks[16];
+  chacha20_block(c.kw, 0, c.nw, ks);  // every lane: the one-time key r || s is the first 32 bytes of block 0
+  Poly1305 st;
+  poly1305_init(st, ks);
+  // lane l: r^(l+1), by doubling
+  uint32_t pw[5] = {st.r[0], st.r[1], st.r[2], st.r[3], st.r[4]};
+#pragma unroll 1
+  for (int s = 0; s < 6; s++) {
+    uint32_t base[5], other[5];
+    shfl5(base, pw, gl_pow_src_base(s));
+    shfl5(other, pw, gl_pow_src_other(s, lane));
+    pl_mul(other, base);
+    if (gl_pow_active(s, lane))
+      for (int k = 0; k < 5; k++) pw[k] = other[k];
+  }
+  uint32_t r64[5];
+  shfl5(r64, pw, 63);
+  const uint64_t na = (alen + 15) / 16, nc = (clen + 15) / 16, N = pl_mac_blocks(alen, clen);
+  uint32_t p[5];
+  pl_lane_partial(
+      N, lane,
+      [&](uint64_t k, uint32_t m[4]) {
+        if (k < na) {
+          const uint64_t o = 16 * k;
+          aad_ld(o, alen - o < 16 ? (uint32_t)(alen - o) : 16u, m);
+        } else if (k < na + nc) {
+          const uint64_t o = 16 * (k - na);
+          ld16(ct + o, clen - o < 16 ? (uint32_t)(clen - o) : 16u, m);
+        } else {
+          pl_len_block(alen, clen, m);
+        }
+      },
+      r64, p);
+  {
+    const uint32_t d = gl_lane_exponent(N, lane);
+    uint32_t rd[5];
+    shfl5(rd, pw, d ? d - 1 : 0);  // (a lane without blocks holds p = 0)
+    pl_lane_term(p, rd);
+  }
+  // every limb < 2^26, so 64 of them fit a 32-bit word (pl_lane_term)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    for (int k = 0; k < 5; k++) p[k] += __shfl_xor(p[k], off);
+  uint32_t tag[4], want[4];
+  pl_finish(st, p, tag);
+  ld16(ct + clen, 16, want);
+  uint32_t diff = 0;
+  for (int k = 0; k < 4; k++) diff |= tag[k] ^ want[k];
+  if (diff != 0) return false;
+  const uint64_t nb = cl_blocks(clen);
+  for (uint64_t b = lane; b < nb; b += GL_LANES) {
+    chacha20_block(c.kw, cl_counter(b), c.nw, ks);
+#pragma unroll
+    for (uint32_t q = 0; q < 4; q++) {
+      const uint32_t len = cl_piece_len(clen, b, q);
+      if (len == 0) break;
+      const uint64_t o = cl_piece_offset(b, q);
+      uint32_t x[4];
+      ld16(ct + o, len, x);
+      for (int w = 0; w < 4; w++) x[w] ^= ks[4 * q + w];
+      st16(pt + o, len, x);
+    }
+  }
+  return true;
+}
+
+// The AEAD of the context row by the whole wave; every lane returns the same verdict. (The row, and so the branch,
+// is the same in every lane.)
+template <class AadLd>
 __device__ __forceinline__ bool aead_wave_open(const uint32_t* tt, uint32_t* m4, uint32_t lane, const LongCtxRow& c,
-                                               AadLd aad_ld, AadByte aad_byte, uint64_t alen, const uint8_t* ct,
-                                               uint64_t clen, uint8_t* pt) {
+                                               AadLd aad_ld, uint64_t alen, const uint8_t* ct, uint64_t clen,
+                                               uint8_t* pt) {
   if (c.aead == HPKE_AEAD_AES128GCM) return gcm_wave_open<4>(tt, m4, lane, c, aad_ld, alen, ct, clen, pt);
   if (c.aead == HPKE_AEAD_AES256GCM) return gcm_wave_open<8>(tt, m4, lane, c, aad_ld, alen, ct, clen, pt);
-  // ChaCha20Poly1305: the serial code, in lane 0
-  uint32_t ok = 0;
-  if (lane == 0) {
-    ok = chapoly_tag_ok(c.kw, c.nw, alen, aad_byte, ct, clen);
-    if (ok) chapoly_decrypt(c.kw, c.nw, ct, clen, pt);
-  }
-  return __shfl(ok, 0) != 0;
+  return chapoly_wave_open(lane, c, aad_ld, alen, ct, clen, pt);
 }
 
 __device__ __forceinline__ void fill_ttable(uint32_t* tt) {
@@ -244,8 +319,8 @@ __global__ __launch_bounds__(64 * WAVES) void hpke_long_open_kernel(const LongCt
   const uint64_t clen = ok ? c1 - c0 - 16 : 0;
   if (ok)
     ok = aead_wave_open(
-        tt, m4[wave], lane, c, [&](uint64_t o, uint32_t len, uint32_t x[4]) { ld16(aad + o, len, x); },
-        [&](uint64_t i) { return aad[i]; }, alen, ct, clen, pt);
+        tt, m4[wave], lane, c, [&](uint64_t o, uint32_t len, uint32_t x[4]) { ld16(aad + o, len, x); }, alen, ct,
+        clen, pt);
   if (lane == 0) b.ok[r] = (uint8_t)ok;
 }
 
@@ -338,7 +413,7 @@ __global__ __launch_bounds__(64 * WAVES) void upload_open_kernel(UploadArgs a) {
     for (int t = 0; t < 2 && !ok; t++) {
       const LongCtxRow c = ctx[t];
       if (!c.ok) continue;
-      ok = aead_wave_open(tt, m4[wave], lane, c, aad_ld, aad_byte, alen, ct, clen, pt);
+      ok = aead_wave_open(tt, m4[wave], lane, c, aad_ld, alen, ct, clen, pt);
     }
     if (!ok) st = JX_OPEN_HPKE_DECRYPT_ERROR;
   }

@@ -8,7 +8,7 @@ PlaintextInputShare framing and the tag) under DHKEM(X25519, HKDF-SHA256) / HKDF
 back. The shares are random bytes (every 16 bytes an element < p with probability 1 - 2^-59): what is timed does not
 depend on their values. They are sealed on the host by the kernels' own AES / GHASH code (tools/upload_seal.cpp);
 the key schedules come from the Python references. Five alternating pairs after two warm-ups; AES-256-GCM and
-ChaCha20Poly1305 (which the wave-per-report kernel runs serially in one lane) are timed for the record.
+ChaCha20Poly1305 are timed for the record (one warm-up, three runs each).
 
   python tools/bench_upload.py --probe-old      # one old call alone: run it first, under its own time limit
   python tools/bench_upload.py --out profiles/upload_open.json
