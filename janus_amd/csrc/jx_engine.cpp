@@ -254,7 +254,7 @@ static int32_t make_cfg(const jx_prio3_params* p, const uint8_t* vk, uint32_t vk
   else if (c.algo == ALGO_SUM)
     c.ncoef = COEF_K + c.calls;
   else
-    c.ncoef = COEF_K + 2 * c.calls;
+    c.ncoef = COEF_K + coef_call_slots(c.calls);  // (c_k, d_k) as 26-bit limbs: 40 bytes per call
   if (c.algo == ALGO_SUMVEC || c.algo == ALGO_HISTOGRAM || fp) {  // gadget 0's power tables (jx_kernels.h)
     c.c_rpow = c.ncoef;
     c.ncoef += c.chunk;

@@ -391,6 +391,30 @@ JX_HD limbs26 to_limbs26(f128 a) {
   return r;
 }
 
+// A ParallelSum call's coefficient pair (c_k, d_k) as K1 stages it for the FLP kernels: the ten limbs
+// to_limbs26 returns, so that no kernel splits a coefficient again. Words 0-3 = c's limbs 0-3 (row A of the
+// staging, jx_kernels.h), 4-7 = d's limbs 0-3 (row B), 8, 9 = the two top limbs (half-row C).
+constexpr int CD26_WORDS = 10;
+JX_HD void pack_cd26(f128 c, f128 d, uint32_t w[CD26_WORDS]) {
+  const limbs26 cl = to_limbs26(c), dl = to_limbs26(d);
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    w[i] = cl.l[i];
+    w[4 + i] = dl.l[i];
+  }
+  w[8] = cl.l[4];
+  w[9] = dl.l[4];
+}
+JX_HD void unpack_cd26(const uint32_t w[CD26_WORDS], limbs26& c, limbs26& d) {
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    c.l[i] = w[i];
+    d.l[i] = w[4 + i];
+  }
+  c.l[4] = w[8];
+  d.l[4] = w[9];
+}
+
 struct wacc26 {
   uint64_t col[9];  // value = sum_s col[s] * 2^(26 s)
 };

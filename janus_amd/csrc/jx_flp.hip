@@ -1,5 +1,7 @@
 // jx_flp.hip — K3, the FLP query + decide kernels of the Prio3 engine, and the leader's prepare_next (the stages
 // are described at the top of jx_kernels.hip, which keeps K0 and K1; the staging layout is in jx_kernels.h).
+#include <type_traits>
+
 #include "jx_field.h"
 #include "jx_kernels.h"
 
@@ -126,12 +128,12 @@ __device__ __forceinline__ void psum_part_finish(const Cfg& c, const Bufs& b, ui
   const uint64_t r = r0 < b.n ? r0 : b.n - 1;
   const uint32_t NC = c.ncoef, C = c.calls, chunk = c.chunk, M = c.meas_len, A = 2 * chunk;
   const uint32_t j0 = g * PPW;
-  const uint4* coefb = b.coef + il_idx(blk, NC, 0, lane);
+  const uint4* cblk = b.coef + il_idx(blk, NC, 0, 0);
   const MeasView measb = meas_view(c, b, blk, lane);
 #pragma unroll 1
   for (uint32_t k = kf + 1; k <= C; k++) {  // the ragged last call(s), or every call of a padded group
-    const limbs26 ck = to_limbs26(u4_to_f(coefb[(COEF_K + 2 * (k - 1)) * IL]));
-    const limbs26 dk = to_limbs26(u4_to_f(coefb[(COEF_K + 2 * (k - 1) + 1) * IL]));
+    limbs26 ck, dk;
+    coef_call_limbs(ld_coef_call(cblk, lane, k), ck, dk);
     const uint32_t nb = (k - 1) * chunk + j0;
 #pragma unroll
     for (int i = 0; i < PPW; i++) {
@@ -264,7 +266,7 @@ __global__ __launch_bounds__(64, 4) void flp_psum_part_kernel(Cfg c, Bufs b) {
     wacc_zero(ao[i]);
   }
   acc_zero(sx);
-  const uint4* coefb = b.coef + il_idx(blk, NC, 0, lane);
+  const uint4* cblk = b.coef + il_idx(blk, NC, 0, 0);
   const MeasView measb = meas_view(c, b, blk, lane);
   // calls whose PPW slots of this group are all real measurement elements run branch-free;
   // the rest (the ragged last chunk, slots beyond chunk) take the guarded tail loop
@@ -273,13 +275,13 @@ __global__ __launch_bounds__(64, 4) void flp_psum_part_kernel(Cfg c, Bufs b) {
   for (uint32_t k0 = 1; k0 <= kf; k0 += 512) {  // <= 5 * 512 limb products (< 2^52) per column
     const uint32_t k1 = min(kf, k0 + 511);
     // software pipeline: the loads of calls k+1 .. k+PF are in flight while call k multiplies
-    uint4 cr[PF], dr[PF], xr[PF][PPW];
+    CoefCall cr[PF];
+    uint4 xr[PF][PPW];
 #pragma unroll
     for (int u = 0; u < PF; u++) {
       const uint32_t k = k0 + u;
       if (k <= k1) {
-        cr[u] = coefb[(COEF_K + 2 * (k - 1)) * IL];
-        dr[u] = coefb[(COEF_K + 2 * (k - 1) + 1) * IL];
+        cr[u] = ld_coef_call(cblk, lane, k);
 #pragma unroll
         for (int i = 0; i < PPW; i++) xr[u][i] = measb[(uint64_t)((k - 1) * chunk + j0 + i)];
       }
@@ -290,15 +292,14 @@ __global__ __launch_bounds__(64, 4) void flp_psum_part_kernel(Cfg c, Bufs b) {
       for (int u = 0; u < PF; u++) {
         const uint32_t k = kb + u;
         if (k <= k1) {
-          const limbs26 ck = to_limbs26(u4_to_f(cr[u]));
-          const limbs26 dk = to_limbs26(u4_to_f(dr[u]));
+          limbs26 ck, dk;
+          coef_call_limbs(cr[u], ck, dk);
           f128 x[PPW];
 #pragma unroll
           for (int i = 0; i < PPW; i++) x[i] = u4_to_f(xr[u][i]);
           const uint32_t kn = k + PF;
           if (kn <= k1) {
-            cr[u] = coefb[(COEF_K + 2 * (kn - 1)) * IL];
-            dr[u] = coefb[(COEF_K + 2 * (kn - 1) + 1) * IL];
+            cr[u] = ld_coef_call(cblk, lane, kn);
 #pragma unroll
             for (int i = 0; i < PPW; i++) xr[u][i] = measb[(uint64_t)((kn - 1) * chunk + j0 + i)];
           }
@@ -331,33 +332,56 @@ __device__ __forceinline__ void glds16(const uint4* src, uint4* lds_row) {
   __builtin_amdgcn_global_load_lds((const void*)src, (void*)lds_row, 16, 0, 0);
 }
 
-// K3 with an LDS-DMA ring of depth D (4). A workgroup is K3W waves = K3W consecutive slot
-// groups of one 64-report block. Per call k, wave 0 streams c_k and wave 1 d_k (one
-// global_load_lds_dwordx4 each: 1 KiB, the block's 64 reports) into ring slot (k-1) % D, and every
-// wave its own PPW measurement elements; the coefficients are fetched once per K3W groups instead of
-// once per group, and D-1 calls stay in flight without holding VGPRs. One s_barrier per call: after it,
-// every wave's loads of call k have landed (each waited for its own with vmcnt) and every wave has
-// finished reading call k-1's slot, which the next issue overwrites. Every call runs in the ring: an
-// element past the share (the ragged last call) or of a padded slot is loaded from a zero constant, so
-// it adds nothing, and a padding group's wave only keeps the barriers.
+__device__ __forceinline__ void glds4(const uint32_t* src, uint32_t* lds_row) {
+  __builtin_amdgcn_global_load_lds((const void*)src, (void*)lds_row, 4, 0, 0);
+}
+
+// K3 with two LDS-DMA rings. A workgroup is K3W waves = K3W consecutive slot groups of one 64-report
+// block. Per call k every wave streams its own PPW measurement elements into slot (k-1) % D of the
+// measurement ring (depth D = 4) and a quarter of the call's coefficient limbs (K1 staged them as the ten
+// 26-bit limbs of (c_k, d_k), jx_kernels.h: 2.5 KiB per call and block) into slot (k-1) % (D-1) of the
+// coefficient ring: wave 0 row A and wave 1 row B (one global_load_lds_dwordx4 each), waves 2 and 3 one
+// half of half-row C (a global_load_lds_dword each). So the coefficients are fetched once per K3W groups
+// and never split into limbs here, every wave issues 1 + PPW loads per call, and D-1 (D-2) calls stay in
+// flight without holding VGPRs; 4 x 8 + 3 x 2.5 = 39.5 KiB keeps four workgroups per CU. One s_barrier
+// per call: after it, every wave's loads of call k have landed (each waited for its own with vmcnt) and
+// every wave has finished reading call k-1's slots, which the next issues overwrite. Every call runs in
+// the rings: an element past the share (the ragged last call) or of a padded slot is loaded from a zero
+// constant, so it adds nothing, and a padding group's wave only keeps the barriers and its share of the
+// coefficient loads.
+//
+// The loads of one wave complete in issue order, and iteration k issues c(k+2), then x(k+3): when
+// iteration k starts, the loads issued after c(k) are x(k+1), c(k+1), x(k+2) = 2 PPW + 1, so
+// vmcnt(2 PPW + 1) proves that c(k) and x(k) (issued before it) have landed, as long as those three were
+// issued at all (k + 2 <= calls; later iterations wait for everything).
+//
+// The call loop is unrolled by D, so a block's measurement slots are the constants 0..3, and three such
+// blocks (one per phase of the depth-3 coefficient ring) make every LDS address an immediate offset and
+// every wait a constant; calls near the end (the last call's range check, fewer loads in flight) take the
+// generic loop after it. The 512-call normalisation falls on a block's last call.
 constexpr uint32_t K3W = 4;
 // LDS address of a __shared__ object
 __device__ __forceinline__ uint32_t lds_addr(const void* p) {
   return (uint32_t)(size_t)(const __attribute__((address_space(3))) uint8_t*)p;
 }
-// Four 16-byte LDS reads and one wait, in asm: the compiler's LDS-DMA wait tracking cannot tell which
-// ring slot a read touches and would otherwise drain every outstanding global_load_lds (vmcnt(0))
-// before each read, serialising the ring; the explicit wait_vmcnt + s_barrier order the reads here.
-__device__ __forceinline__ void lds_read4(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3, uint4& v0, uint4& v1,
-                                          uint4& v2, uint4& v3) {
+// One call's LDS reads (coefficient rows A, B and half-row C, two measurement rows) and one wait, in asm:
+// the compiler's LDS-DMA wait tracking cannot tell which ring slot a read touches and would otherwise
+// drain every outstanding global_load_lds (vmcnt(0)) before each read, serialising the rings; the explicit
+// wait_vmcnt + s_barrier order the reads here. ca / ce: the lane's address in rows A / C of coefficient
+// slot 0, x0 / x1: of its measurement rows in slot 0; OC / OX: the slots' byte offsets (immediates).
+template <uint32_t OC, uint32_t OX>
+__device__ __forceinline__ void lds_read_call(uint32_t ca, uint32_t ce, uint32_t x0, uint32_t x1, CoefCall& cv,
+                                              uint4& xv0, uint4& xv1) {
+  static_assert(OC + COEF_ROWB_U4 * 16 < 65536 && OX < 65536, "ds offsets are 16 bits");
   asm volatile(
-      "ds_read_b128 %0, %4\n\t"
-      "ds_read_b128 %1, %5\n\t"
-      "ds_read_b128 %2, %6\n\t"
-      "ds_read_b128 %3, %7\n\t"
+      "ds_read_b128 %0, %5 offset:%9\n\t"
+      "ds_read_b128 %1, %5 offset:%10\n\t"
+      "ds_read_b64 %2, %6 offset:%9\n\t"
+      "ds_read_b128 %3, %7 offset:%11\n\t"
+      "ds_read_b128 %4, %8 offset:%11\n\t"
       "s_waitcnt lgkmcnt(0)"
-      : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3)
-      : "v"(a0), "v"(a1), "v"(a2), "v"(a3)
+      : "=&v"(cv.a), "=&v"(cv.b), "=&v"(cv.e), "=&v"(xv0), "=&v"(xv1)
+      : "v"(ca), "v"(ce), "v"(x0), "v"(x1), "n"(OC), "n"(OC + COEF_ROWB_U4 * 16), "n"(OX)
       : "memory");
 }
 // W: waves (slot groups) per workgroup
@@ -365,24 +389,30 @@ __device__ __forceinline__ void lds_read4(uint32_t a0, uint32_t a1, uint32_t a2,
 // the column sums instead of the group finish (results wrong by design), to time the finish by difference.
 template <int PPW, bool HIST, bool LEADER, int D, int W = K3W, bool RING_ONLY = false>
 __global__ __launch_bounds__(64 * W, 4) void flp_psum_part_glds_kernel(Cfg c, Bufs b) {
-  static_assert(PPW == 2, "lds_read4 reads c, d and two measurement rows");
-  constexpr int ROWS = 2 + W * PPW;  // c_k, d_k, then x[wave][i]
-  __shared__ uint4 ring[D][ROWS][64];
+  static_assert(PPW == 2, "lds_read_call reads two measurement rows");
+  static_assert(W == 4, "one quarter of a call's coefficient limbs per wave");
+  static_assert(D == 4, "the unrolled blocks assume measurement depth 4, coefficient depth 3");
+  constexpr int XROWS = W * PPW;  // x[wave][i]
+  constexpr int DC = D - 1;       // depth of the coefficient ring
+  constexpr uint32_t ROW_BYTES = 64 * 16, XSLOT = XROWS * ROW_BYTES, XBYTES = D * XSLOT;
+  constexpr uint32_t CSLOT = COEF_CALL_BYTES;
+  // the measurement ring [D][XROWS][64] uint4, then the coefficient ring [DC][COEF_CALL_U4] uint4
+  __shared__ uint4 ring[D * XROWS * 64 + DC * COEF_CALL_U4];
+  static_assert(sizeof(ring) <= 40 * 1024, "four workgroups per CU");
   const uint32_t NG = c.ngroups, NW = (NG + W - 1) / W;
   const uint32_t bid = blockIdx.x, xcd = bid & 7u, q = bid >> 3;
   const uint32_t wg = q % NW;
   const uint64_t blk = (uint64_t)(q / NW) * 8 + xcd;
   const uint64_t nblk = (b.n + 63) / 64;
   if (blk >= nblk) return;  // uniform over the workgroup
-  const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  // (the wave index is uniform: in an SGPR, the ring slots' LDS addresses are scalar arithmetic)
+  const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
   const uint32_t g = wg * W + wave;
   const uint32_t C = c.calls, chunk = c.chunk, M = c.meas_len;
   const uint32_t j0 = g * PPW;
-  const uint4* coefb = b.coef + il_idx(blk, c.ncoef, 0, lane);
   const MeasView measb = meas_view(c, b, blk, lane);
   const uint4* zero = b.consts + c.c_misc + MISC_ZERO;
-  const uint32_t kfw = C;  // every call (see above)
-  bool real[PPW];          // slot j0 + i exists (a padding group's wave has none)
+  bool real[PPW];  // slot j0 + i exists (a padding group's wave has none)
 #pragma unroll
   for (int i = 0; i < PPW; i++) real[i] = g < NG && j0 + i < chunk;
 
@@ -404,75 +434,169 @@ __global__ __launch_bounds__(64 * W, 4) void flp_psum_part_glds_kernel(Cfg c, Bu
   // The part swap on odd q puts rows r and r + 8 in opposite halves of a 256-byte LDS bank window, so the
   // consumers' ds_read_b128 (16 lanes per pass, lane = row) stay conflict-free.
   const bool inpl = LEADER && !HIST && b.meas_rs != 0;
-  // loads of call k into ring slot (k - 1) % D
-  auto issue = [&](uint32_t k) {
-    const uint32_t sl = (k - 1) % D;
-    if (wave < 2) glds16(coefb + (uint64_t)(COEF_K + 2 * (k - 1) + wave) * IL, &ring[sl][wave][0]);
+  static_assert(W * PPW == 8, "one 128-byte row segment per report per call");
+  // ---- sources. Measurement load u of this lane: the element's first-call address and whether its slot
+  // exists (in place: slot wg * 8 + p of row 8 q + a; staged: slot j0 + u of the lane's report)
+  const uint8_t* xbase[PPW];
+  bool xreal[PPW], xlast[PPW];  // the slot exists; its element of the last call does (is below meas_len)
+#pragma unroll
+  for (int u = 0; u < PPW; u++) {
+    uint32_t xslot;
     if (inpl) {
-      static_assert(W * PPW == 8, "one 128-byte row segment per report per call");
-#pragma unroll
-      for (int u = 0; u < PPW; u++) {
-        const uint32_t q = wave * PPW + u, a = lane & 7u, p = (lane >> 3) ^ (q & 1u);
-        const uint32_t slot = wg * (W * PPW) + p, e = (k - 1) * chunk + slot;
-        const uint64_t r0 = blk * 64 + 8 * q + a, r = r0 < b.n ? r0 : b.n - 1;
-        const uint4* src = slot < chunk && e < M ? reinterpret_cast<const uint4*>(b.meas_src + r * b.meas_rs) + e : zero;
-        glds16(src, &ring[sl][2 + q][0]);
-      }
+      const uint32_t q = wave * PPW + u, a = lane & 7u, p = (lane >> 3) ^ (q & 1u);
+      const uint64_t r0 = blk * 64 + 8 * q + a, r = r0 < b.n ? r0 : b.n - 1;
+      xslot = wg * (W * PPW) + p;
+      xreal[u] = xslot < chunk;
+      xbase[u] = b.meas_src + r * b.meas_rs + 16ull * xslot;
     } else {
+      xslot = j0 + u;
+      xreal[u] = real[u];
+      xbase[u] = reinterpret_cast<const uint8_t*>(&measb[xslot]);
+    }
+    xlast[u] = xreal[u] && (C - 1) * chunk + xslot < M;
+  }
+  const uint64_t xstep = (uint64_t)chunk * measb.es * 16u;  // bytes from a call's element to the next call's
+  // this wave's quarter of a call's coefficient limbs: its byte offset in the call's region (global and
+  // LDS alike) and this lane's part of it
+  const uint32_t cq = wave < 2 ? wave * ROW_BYTES : COEF_ROWC_U4 * 16 + (wave - 2) * 256;
+  const uint8_t* cbase = reinterpret_cast<const uint8_t*>(b.coef + il_idx(blk, c.ncoef, COEF_K, 0)) + cq +
+                         (wave < 2 ? lane * 16 : lane * 4);
+  uint8_t* const ringb = reinterpret_cast<uint8_t*>(ring);
+  // loads of call k: the coefficient quarter into slot sc of its ring, the measurement elements into slot sx
+  auto issue_c = [&](const uint8_t* src, uint32_t sc) {
+    uint8_t* dst = ringb + XBYTES + sc * CSLOT + cq;
+    if (wave < 2)
+      glds16(reinterpret_cast<const uint4*>(src), reinterpret_cast<uint4*>(dst));
+    else
+      glds4(reinterpret_cast<const uint32_t*>(src), reinterpret_cast<uint32_t*>(dst));
+  };
+  auto issue_x = [&](const uint8_t* const* src, uint32_t sx_) {
 #pragma unroll
-      for (int i = 0; i < PPW; i++) {
-        const uint32_t e = (k - 1) * chunk + j0 + i;
-        glds16(real[i] && e < M ? &measb[e] : zero, &ring[sl][2 + wave * PPW + i][0]);
-      }
+    for (int u = 0; u < PPW; u++)
+      glds16(reinterpret_cast<const uint4*>(src[u]),
+             reinterpret_cast<uint4*>(ringb + sx_ * XSLOT + (wave * PPW + u) * ROW_BYTES));
+  };
+  // Calls are issued in order, so a source is a running pointer: xp[u], stepping xst[u] per call (a missing
+  // slot: the zero constant, step 0), and cp. Only the last call can reach past the share (xlast).
+  const uint8_t* xp[PPW];
+  uint64_t xst[PPW];
+#pragma unroll
+  for (int u = 0; u < PPW; u++) {
+    xp[u] = xreal[u] ? xbase[u] : reinterpret_cast<const uint8_t*>(zero);
+    xst[u] = xreal[u] ? xstep : 0u;
+  }
+  const uint8_t* cp = cbase;
+  // (the empty asm keeps each pointer one register pair stepped in place: left alone, the compiler holds
+  // multiples of the steps in further pairs for the unrolled calls, and the kernel spills)
+  auto step_x = [&]() {
+#pragma unroll
+    for (int u = 0; u < PPW; u++) {
+      xp[u] += xst[u];
+      asm volatile("" : "+v"(xp[u]));
     }
   };
-  // loads a wave issues per call: 1 (coefficient, waves 0/1) + PPW (measurement)
-  auto wait_call = [&](bool tail) {
-    if (tail) {
-      wait_vmcnt<0>();
-    } else if (wave < 2) {
-      wait_vmcnt<(D - 2) * (PPW + 1)>();
-    } else {
-      wait_vmcnt<(D - 2) * PPW>();
-    }
+  // any call, every check made (the prologue and the generic loop)
+  auto issue_c_k = [&](uint32_t k) {
+    issue_c(cp, (k - 1) % DC);
+    cp += CSLOT;
   };
-  for (uint32_t k = 1; k < D && k <= kfw; k++) issue(k);
-  const uint32_t ring_base = lds_addr(&ring[0][0][lane]);
-  constexpr uint32_t SLOT_BYTES = ROWS * 64 * 16, ROW_BYTES = 64 * 16;
-  // this lane's measurement elements in a ring slot (relative to ring_base)
-  uint32_t xoff[PPW];
+  auto issue_x_k = [&](uint32_t k) {
+    const uint8_t* src[PPW];
+#pragma unroll
+    for (int u = 0; u < PPW; u++)
+      src[u] = k < C || xlast[u] ? xp[u] : reinterpret_cast<const uint8_t*>(zero);
+    issue_x(src, (k - 1) % D);
+    step_x();
+  };
+  // in the order the steady state issues them: x(1) c(1) x(2) c(2) x(3)
+  for (uint32_t k = 1; k < D && k <= C; k++) {
+    issue_x_k(k);
+    if (k < DC) issue_c_k(k);
+  }
+  // ---- this lane's LDS read addresses in slot 0 of each ring
+  const uint32_t ring_base = lds_addr(ring) + lane * 16;
+  uint32_t xa[PPW];
 #pragma unroll
   for (int i = 0; i < PPW; i++) {
     const uint32_t q = lane >> 3, p = wave * PPW + i;
-    xoff[i] = inpl ? (2 + q) * ROW_BYTES + ((8 * (p ^ (q & 1u)) + (lane & 7u)) * 16) - lane * 16
-                   : (2 + wave * PPW + i) * ROW_BYTES;
+    xa[i] = ring_base + (inpl ? q * ROW_BYTES + ((8 * (p ^ (q & 1u)) + (lane & 7u)) * 16) - lane * 16
+                              : (wave * PPW + i) * ROW_BYTES);
   }
+  const uint32_t ca = ring_base, ce = lds_addr(ring) + COEF_ROWC_U4 * 16 + lane * 8;  // (+ XBYTES: an immediate)
+  auto mac_call = [&](const CoefCall& cv, const uint4* xv) {
+    limbs26 ck, dk;
+    coef_call_limbs(cv, ck, dk);
+#pragma unroll
+    for (int i = 0; i < PPW; i++) {
+      const f128 x = u4_to_f(xv[i]);
+      const limbs26 xl = to_limbs26(x);
+      wacc_mac(ae[i], xl, dk);
+      wacc_mac(ao[i], xl, ck);
+      if (HIST) acc_add128(sx, x);
+    }
+  };
+  auto normalize = [&]() {  // <= 5 * 512 limb products (< 2^52) per column
+#pragma unroll
+    for (int i = 0; i < PPW; i++) {
+      wacc_normalize(ae[i]);
+      wacc_normalize(ao[i]);
+    }
+  };
+  uint32_t k = 1;
+  // ---- whole blocks of D calls k..k+3 (k = 1 mod D) that issue only calls before the last one
+  // (k + 2 D - 2 < C): no range check, and every slot and wait is a constant. PH: (k - 1) / D mod DC, the
+  // coefficient ring's phase.
+  {
+    auto step = [&](auto uc, auto phc) {
+      constexpr uint32_t U = decltype(uc)::value, PH = decltype(phc)::value;
+      wait_vmcnt<2 * PPW + 1>();
+      __builtin_amdgcn_s_barrier();
+      issue_c(cp, (PH + U + DC - 1) % DC);
+      issue_x(xp, (U + D - 1) % D);
+      cp += CSLOT;
+      step_x();
+      if (g < NG) {
+        CoefCall cv;
+        uint4 xv[PPW];
+        lds_read_call<XBYTES + ((PH + U) % DC) * CSLOT, U * XSLOT>(ca, ce, xa[0], xa[1], cv, xv[0], xv[1]);
+        mac_call(cv, xv);
+      }
+    };
+    auto block = [&](auto phc) {
+      step(std::integral_constant<uint32_t, 0>{}, phc);
+      step(std::integral_constant<uint32_t, 1>{}, phc);
+      step(std::integral_constant<uint32_t, 2>{}, phc);
+      step(std::integral_constant<uint32_t, 3>{}, phc);
+      k += D;
+      if (((k - 1) & 511u) == 0 && g < NG) normalize();  // after call 512, 1024, ...
+    };
+    // such blocks: 1 + D j + 2 D - 2 < C; they run three at a time (one loop exit: with one per block the
+    // register allocation spilled at every exit edge)
+    const uint32_t nblocks = C > 2 * D - 1 ? (C - (2 * D - 1) + D - 1) / D : 0;
 #pragma unroll 1
-  for (uint32_t k = 1; k <= kfw; k++) {
-    wait_call(k + D - 2 > kfw);  // near the end fewer calls are in flight: wait for all
+    for (uint32_t t = nblocks / DC; t > 0; t--) {
+      block(std::integral_constant<uint32_t, 0>{});
+      block(std::integral_constant<uint32_t, 1>{});
+      block(std::integral_constant<uint32_t, 2>{});
+    }
+  }
+  // ---- the remaining calls
+#pragma unroll 1
+  for (; k <= C; k++) {
+    if (k + 2 > C)  // near the end fewer calls are in flight: wait for all
+      wait_vmcnt<0>();
+    else
+      wait_vmcnt<2 * PPW + 1>();
     __builtin_amdgcn_s_barrier();
-    if (k + D - 1 <= kfw) issue(k + D - 1);
+    if (k + DC - 1 <= C) issue_c_k(k + DC - 1);
+    if (k + D - 1 <= C) issue_x_k(k + D - 1);
     if (g < NG) {
-      const uint32_t a = ring_base + ((k - 1) % D) * SLOT_BYTES;
-      uint4 cv, dv, xv[PPW];
-      lds_read4(a, a + ROW_BYTES, a + xoff[0], a + xoff[1], cv, dv, xv[0], xv[1]);
-      const limbs26 ck = to_limbs26(u4_to_f(cv));
-      const limbs26 dk = to_limbs26(u4_to_f(dv));
-#pragma unroll
-      for (int i = 0; i < PPW; i++) {
-        const f128 x = u4_to_f(xv[i]);
-        const limbs26 xl = to_limbs26(x);
-        wacc_mac(ae[i], xl, dk);
-        wacc_mac(ao[i], xl, ck);
-        if (HIST) acc_add128(sx, x);
-      }
-      if ((k & 511u) == 0) {  // <= 5 * 512 limb products (< 2^52) per column
-#pragma unroll
-        for (int i = 0; i < PPW; i++) {
-          wacc_normalize(ae[i]);
-          wacc_normalize(ao[i]);
-        }
-      }
+      const uint32_t co = ((k - 1) % DC) * CSLOT, xo = ((k - 1) % D) * XSLOT;
+      CoefCall cv;
+      uint4 xv[PPW];
+      lds_read_call<XBYTES, 0>(ca + co, ce + co, xa[0] + xo, xa[1] + xo, cv, xv[0], xv[1]);
+      mac_call(cv, xv);
+      if ((k & 511u) == 0) normalize();
     }
   }
   if (g >= NG) return;
@@ -727,9 +851,10 @@ int psum_ppw(uint32_t chunk) {
   return best;
 }
 
-// K3 phase 1: the depth-4 LDS-DMA ring (K3W slot groups per workgroup) for PPW = 2; the per-wave
-// register-prefetch kernel for PPW = 1 (chunk_length 1). Measured and removed:
-// 2 / 3 calls of register prefetch, 3-waves/SIMD builds, a depth-3 ring, 8 groups per workgroup.
+// K3 phase 1: the LDS-DMA rings (measurement rows four calls deep, coefficient limb rows three; K3W slot
+// groups per workgroup) for PPW = 2; the per-wave register-prefetch kernel for PPW = 1 (chunk_length 1).
+// Measured and removed: 2 / 3 calls of register prefetch, 3-waves/SIMD builds, a ring
+// with the measurement rows three deep as well, 8 groups per workgroup.
 template <int PPW, bool HIST, bool LEADER>
 static void launch_psum_part(const Cfg& c, const Bufs& b, hipStream_t s, uint32_t grid) {
   if constexpr (PPW == 2) {

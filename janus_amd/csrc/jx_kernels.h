@@ -76,6 +76,18 @@ enum : uint32_t {
   COEF_R2 = 5,       // joint_rand[1] (Histogram)
   COEF_K = 6,        // first per-call slot
 };
+// The per-call region from COEF_K on. Prio3Sum: one 16-byte slot c_k per call. ParallelSum gadget 0: call
+// k's pair (c_k, d_k) as its ten 26-bit limbs (pack_cd26, jx_field.h), COEF_CALL_U4 uint4 (2.5 KiB) per
+// call and 64-report block, at uint4 offset COEF_K * IL + (k - 1) * COEF_CALL_U4 of the block's staging:
+//   row A       [lane] uint4  c_k limbs 0-3
+//   row B       [lane] uint4  d_k limbs 0-3      (+ COEF_ROWB_U4)
+//   half-row C  [lane] uint2  (c_k, d_k) limb 4  (+ COEF_ROWC_U4)
+// i.e. exactly the bytes one slot of the K3 ring's coefficient stream holds. coef_call_slots rounds the
+// region up to whole 16-byte slots per report.
+constexpr uint32_t COEF_CALL_U4 = 2 * IL + IL / 2;
+constexpr uint32_t COEF_ROWB_U4 = IL, COEF_ROWC_U4 = 2 * IL;
+constexpr uint32_t COEF_CALL_BYTES = COEF_CALL_U4 * 16;
+inline uint32_t coef_call_slots(uint32_t calls) { return (5 * calls + 1) / 2; }
 // FixedPoint gadget-1 coefficient slots, relative to Cfg::coef1 (Montgomery form)
 enum : uint32_t {
   G1_L = 0,   // (t1^P1 - 1)/P1
@@ -289,14 +301,42 @@ __device__ __forceinline__ uint64_t il_idx(uint64_t blk, uint32_t len, uint32_t 
 // vmcnt and lgkmcnt and force full waits; the host pass of hipcc keeps plain pointers
 #ifdef __HIP_DEVICE_COMPILE__
 typedef __attribute__((address_space(1))) uint4 g_uint4;
+typedef __attribute__((address_space(1))) uint2 g_uint2;
 #else
 typedef uint4 g_uint4;
+typedef uint2 g_uint2;
 #endif
 __device__ __forceinline__ f128 ld_il(const uint4* base, uint64_t blk, uint32_t len, uint32_t e, uint32_t lane) {
   return u4_to_f(((const g_uint4*)base)[il_idx(blk, len, e, lane)]);
 }
 __device__ __forceinline__ void st_il(uint4* base, uint64_t blk, uint32_t len, uint32_t e, uint32_t lane, f128 v) {
   ((g_uint4*)base)[il_idx(blk, len, e, lane)] = f_to_u4(v);
+}
+// ParallelSum call k's staged coefficient limbs (the layout at COEF_K above) of one report: cblk = the
+// block's coefficient staging (b.coef + il_idx(blk, ncoef, 0, 0)).
+struct CoefCall {
+  uint4 a, b;  // rows A, B
+  uint2 e;     // half-row C
+};
+__device__ __forceinline__ CoefCall ld_coef_call(const uint4* cblk, uint32_t lane, uint32_t k) {
+  const g_uint4* p = (const g_uint4*)cblk + (uint64_t)COEF_K * IL + (uint64_t)(k - 1) * COEF_CALL_U4;
+  CoefCall v;
+  v.a = p[lane];
+  v.b = p[COEF_ROWB_U4 + lane];
+  v.e = ((const g_uint2*)(p + COEF_ROWC_U4))[lane];
+  return v;
+}
+__device__ __forceinline__ void coef_call_limbs(const CoefCall& v, limbs26& c, limbs26& d) {
+  const uint32_t w[CD26_WORDS] = {v.a.x, v.a.y, v.a.z, v.a.w, v.b.x, v.b.y, v.b.z, v.b.w, v.e.x, v.e.y};
+  unpack_cd26(w, c, d);
+}
+__device__ __forceinline__ void st_coef_call(uint4* cblk, uint32_t lane, uint32_t k, f128 c, f128 d) {
+  uint32_t w[CD26_WORDS];
+  pack_cd26(c, d, w);
+  g_uint4* p = (g_uint4*)cblk + (uint64_t)COEF_K * IL + (uint64_t)(k - 1) * COEF_CALL_U4;
+  p[lane] = make_uint4(w[0], w[1], w[2], w[3]);
+  p[COEF_ROWB_U4 + lane] = make_uint4(w[4], w[5], w[6], w[7]);
+  ((g_uint2*)(p + COEF_ROWC_U4))[lane] = make_uint2(w[8], w[9]);
 }
 // The measurement share as the FLP kernels read it: the interleaved staging (element e of the lane's
 // report at p[e * IL]) or, for the leader, its explicit input share in place (p[e], report-major).

@@ -237,22 +237,28 @@ __device__ __forceinline__ void emit_proof(const Cfg& c, uint4* pp, uint32_t e, 
 }
 
 // Barycentric weights of one gadget on the P-th roots of unity w^k (Montgomery form):
-//   c_k = w^k / (t - w^k) for k = 1..C at slot sk + stride*(k-1), c_0 = 1/(t - 1) at slot s0,
+//   c_k = w^k / (t - w^k) for k = 1..C at slot sk + (k-1), c_0 = 1/(t - 1) at slot s0,
 // by one batch inversion (prefix products parked in the c_k slots, then one inversion chain).
-// With with_d (ParallelSum gadget 0, stride 2; rcR = r^chunk R): also d_k = c_k rc^(k-1) at slot sk + 2(k-1) + 1, rc = r^chunk,
+// With with_d (ParallelSum gadget 0, sk = COEF_K; rcR = r^chunk R): also d_k = c_k rc^(k-1), rc = r^chunk,
 // in the same backward pass: rc joins the inverted product, so 1/rc costs two products, and the powers
-// descend from rc^(C-1). The backward pass keeps four prefix-product loads in flight (a prefix in slot k-1
-// is overwritten only at step k-1, after its read). Returns sum_{k>=1} c_k.
+// descend from rc^(C-1). The pair (c_k, d_k) is stored as its 26-bit limbs in call k's 40-byte region
+// (jx_kernels.h, st_coef_call), whose row A parks the prefix product until then. The backward pass keeps
+// four prefix-product loads in flight (a prefix in slot k-1 is overwritten only at step k-1, after its
+// read). Returns sum_{k>=1} c_k.
 __device__ f128 bary_coeffs(uint4* coef, uint64_t blk, uint32_t NC, uint32_t lane, f128 tR, const uint4* omega,
-                            uint32_t C, uint32_t s0, uint32_t sk, uint32_t stride, bool with_d = false,
-                            f128 rcR = f128{0, 0}) {
-  auto slot = [&](uint32_t k) { return k == 0 ? s0 : sk + stride * (k - 1); };
+                            uint32_t C, uint32_t s0, uint32_t sk, bool with_d = false, f128 rcR = f128{0, 0}) {
+  // where step k parks its prefix product (uint4 index into coef)
+  auto slot = [&](uint32_t k) -> uint64_t {
+    if (k == 0) return il_idx(blk, NC, s0, lane);
+    return with_d ? il_idx(blk, NC, sk, lane) + (uint64_t)(k - 1) * COEF_CALL_U4 : il_idx(blk, NC, sk + (k - 1), lane);
+  };
+  g_uint4* gco = (g_uint4*)coef;
   const g_uint4* gom = (const g_uint4*)omega;
   f128 acc = sub128(tR, u4_to_f(gom[0]));
-  st_il(coef, blk, NC, slot(0), lane, acc);
+  gco[slot(0)] = f_to_u4(acc);
   for (uint32_t k = 1; k <= C; k++) {
     acc = mont128(acc, sub128(tR, u4_to_f(gom[k])));
-    st_il(coef, blk, NC, slot(k), lane, acc);
+    gco[slot(k)] = f_to_u4(acc);
   }
   f128 inv, rp = make128(R1_128_LO, R1_128_HI), rinv = rp;
   if (with_d) {
@@ -266,7 +272,7 @@ __device__ f128 bary_coeffs(uint4* coef, uint64_t blk, uint32_t NC, uint32_t lan
   f128 sumc = make128(0, 0);
   // step k needs the prefix of slot k-1 and w^k: both loaded four steps ahead (vmcnt counts in order, so a
   // load issued just before its use would also wait for every prefetch)
-  auto pref = [&](int k) { return k >= 1 ? ld_il(coef, blk, NC, slot((uint32_t)k - 1), lane) : make128(0, 0); };
+  auto pref = [&](int k) { return k >= 1 ? u4_to_f(gco[slot((uint32_t)k - 1)]) : make128(0, 0); };
   auto wk = [&](int k) { return k >= 1 ? u4_to_f(gom[k]) : make128(0, 0); };
   const int Ci = (int)C;
   f128 q0 = pref(Ci), q1 = pref(Ci - 1), q2 = pref(Ci - 2), q3 = pref(Ci - 3);
@@ -282,15 +288,16 @@ __device__ f128 bary_coeffs(uint4* coef, uint64_t blk, uint32_t NC, uint32_t lan
     // unconditional loads (a clamped index past the end: the value is never used) keep the loop
     // branch-free, so the wait before the first use counts only the older loads
     const uint32_t kn = k > 4 ? k - 4 : 1;
-    q3 = ld_il(coef, blk, NC, slot(kn - 1), lane);
+    q3 = u4_to_f(gco[slot(kn - 1)]);
     o3 = u4_to_f(gom[kn]);
     f128 invden = mont128(inv, pre);
     inv = mont128(inv, sub128(tR, w));
     f128 ck = mont128(w, invden);
-    st_il(coef, blk, NC, slot(k), lane, ck);
     if (with_d) {
-      st_il(coef, blk, NC, slot(k) + 1, lane, mont128(ck, rp));
+      st_coef_call(coef + il_idx(blk, NC, 0, 0), lane, k, ck, mont128(ck, rp));
       rp = mont128(rp, rinv);
+    } else {
+      gco[slot(k)] = f_to_u4(ck);
     }
     sumc = add128(sumc, ck);
   }
@@ -391,14 +398,13 @@ __device__ uint32_t xof_tail(const Cfg& c, const Bufs& b, uint64_t blk, uint32_t
   st_il(coef, blk, NC, COEF_R2, lane, to_mont128(jr[1]));
   // batch inversion of den_k = t - w^k, k = 0..calls
   const uint32_t C = c.calls;
-  const uint32_t stride = c.algo == ALGO_SUM ? 1u : 2u;
   const f128 rcR = mpow(rR, c.chunk);  // r^chunk (ParallelSum's d_k = c_k r^((k-1) chunk))
   f128 sumc;
   if constexpr (INL) {
     [[clang::always_inline]] sumc =
-        bary_coeffs(coef, blk, NC, lane, tR, omega, C, COEF_C0, COEF_K, stride, c.algo != ALGO_SUM, rcR);
+        bary_coeffs(coef, blk, NC, lane, tR, omega, C, COEF_C0, COEF_K, c.algo != ALGO_SUM, rcR);
   } else {
-    sumc = bary_coeffs(coef, blk, NC, lane, tR, omega, C, COEF_C0, COEF_K, stride, c.algo != ALGO_SUM, rcR);
+    sumc = bary_coeffs(coef, blk, NC, lane, tR, omega, C, COEF_C0, COEF_K, c.algo != ALGO_SUM, rcR);
   }
   if (c.algo == ALGO_SUM) {
     // (1/2) * sum c_k, canonical: mont(sumc*R, 1/2) = sumc/2
@@ -439,9 +445,9 @@ __device__ uint32_t xof_tail(const Cfg& c, const Bufs& b, uint64_t blk, uint32_t
     st_il(coef, blk, NC, B + G1_T, lane, t1R);
     if constexpr (INL) {
       [[clang::always_inline]] (void)bary_coeffs(coef, blk, NC, lane, t1R, b.consts + c.c_omega1, c.calls1, B + G1_C0,
-                                                  B + G1_K, 1);
+                                                  B + G1_K);
     } else {
-      (void)bary_coeffs(coef, blk, NC, lane, t1R, b.consts + c.c_omega1, c.calls1, B + G1_C0, B + G1_K, 1);
+      (void)bary_coeffs(coef, blk, NC, lane, t1R, b.consts + c.c_omega1, c.calls1, B + G1_C0, B + G1_K);
     }
   }
   return flags;

@@ -60,15 +60,30 @@ def main():
             loops.append((labels[m.group(1)], i))
     lo, hi = min(loops, key=lambda t: t[1] - t[0])  # the innermost loop around the barrier
     loop = body[lo:hi + 1]
-    # the normalisation block: from the first 64-bit shift by 26 to the end of the loop body
-    norm_at = next((i for i, l in enumerate(loop) if re.search(r"v_lshrrev_b64 \S+, 26,", l)), len(loop))
-    hot, norm = loop[:norm_at], loop[norm_at:]
+    # The loop is unrolled: one s_barrier per call. The normalisation blocks (one per unrolled block of
+    # calls, each behind a branch) are the basic blocks holding 64-bit shifts by 26.
+    blocks, cur = [], []
+    for l in loop:
+        if re.match(r"^\.LBB\d+_\d+:", l) and cur:
+            blocks.append(cur)
+            cur = []
+        cur.append(l)
+    blocks.append(cur)
+    is_norm = [any(re.search(r"v_lshrrev_b64 \S+, 26,", l) for l in b) for b in blocks]
+    hot = [l for b, n in zip(blocks, is_norm) if not n for l in b]
+    norm = [l for b, n in zip(blocks, is_norm) if n for l in b]
+    calls = sum("s_barrier" in l for l in loop)
+    per_iter = summary(ops(hot))
+    per_call = {k: round(v / calls, 2) for k, v in per_iter.items() if k != "top"}
     tail = body[hi + 1:]
     out = {"kernel": body[0].rstrip(":"), "source": os.path.relpath(SRC, ROOT),
-           "per_call": summary(ops(hot)), "normalize_every_512_calls": summary(ops(norm)),
+           "calls_per_iteration": calls, "per_call": per_call, "per_iteration": per_iter,
+           "normalize_every_512_calls": summary(ops(norm)), "normalize_blocks": sum(is_norm),
            "tail_static": summary(ops(tail)),
-           "note": "static counts from hipcc -S (gfx950); per_call = one iteration of the ring loop without the "
-                   "rarely-taken normalisation block; tail_static counts each inner loop of the group finish once"}
+           "note": "static counts from hipcc -S (gfx950); per_iteration = one turn of the unrolled ring loop "
+                   "(calls_per_iteration calls) without the rarely-taken normalisation blocks, per_call = that "
+                   "divided by the calls; tail_static = everything after that loop (the generic loop for the "
+                   "last calls and the group finish), each inner loop counted once"}
     print(json.dumps(out, indent=1))
 
 
