@@ -1,10 +1,13 @@
-"""Build the gfx950 engine library in-tree: janus_amd/lib/libjanus_prio3.so.
+"""Build the gfx950 engine library in-tree: janus_amd/lib/libjanus_prio3.so, and the test-only device harness
+tests/csrc/libjx_devtest.so (the arithmetic headers one case per lane, for tests/test_gpu_device_math.py).
 
 hipcc cross-compiles for gfx950 without a GPU. Run: ``python -m janus_amd.build``.
 """
 from __future__ import annotations
 
+import hashlib
 import os
+import re
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -25,6 +28,10 @@ OUT = os.path.join(_HERE, "lib", "libjanus_prio3.so")
 EXTRA_FLAGS = {"jx_mp64.hip": ["-mllvm", "-disable-promote-alloca-to-lds"]}
 ARCH = os.environ.get("JX_OFFLOAD_ARCH", "gfx950")
 
+_TESTS_CSRC = os.path.join(_HERE, "..", "tests", "csrc")
+DEVTEST_SRC = os.path.join(_TESTS_CSRC, "devtest.hip")
+DEVTEST_OUT = os.path.join(_TESTS_CSRC, "libjx_devtest.so")
+
 
 def _stale() -> bool:
     if not os.path.exists(OUT):
@@ -34,24 +41,27 @@ def _stale() -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force: bool = False, verbose: bool = False) -> str:
-    """Build the library (measurement variants live in tools/kernel_probe.hip, not here)."""
-    out = OUT
-    if not force and not _stale():
-        return OUT
+def hipcc_path() -> str:
+    return os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+
+
+def compile_and_link(sources, out: str, extra_flags=None, defines=(), verbose: bool = False) -> str:
+    """The one hipcc invocation of the project: every source to an object beside `out` (one hipcc per
+    translation unit, at most 16 at a time), then the shared library, linked aside and renamed into place."""
+    extra_flags = extra_flags or {}
     os.makedirs(os.path.dirname(out), exist_ok=True)
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objs = [os.path.join(os.path.dirname(out), os.path.basename(src) + ".o") for src in SOURCES]
+    hipcc = hipcc_path()
+    objs = [os.path.join(os.path.dirname(out), os.path.basename(src) + ".o") for src in sources]
 
     def compile_one(src, obj):
         cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-x", "hip", "-c", src, "-o", obj]
-        cmd += EXTRA_FLAGS.get(os.path.basename(src), [])
+        cmd += [f"-D{d}" for d in defines]
+        cmd += extra_flags.get(os.path.basename(src), [])
         p = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
         return p.returncode, p.stdout.decode(), cmd
 
-    # one hipcc per translation unit, at most 16 at a time
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), 16)) as pool:
-        results = list(pool.map(compile_one, SOURCES, objs))
+    with ThreadPoolExecutor(max_workers=min(len(sources), 16)) as pool:
+        results = list(pool.map(compile_one, sources, objs))
     for rc, log, cmd in results:
         if rc != 0:
             sys.stderr.write(log)
@@ -67,5 +77,60 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return out
 
 
+_INCLUDE = re.compile(r'^\s*#\s*include\s+"([^"]+)"', re.M)
+
+
+def devtest_sources() -> list:
+    """devtest.hip and every project header it includes, directly or not, in a fixed order."""
+    seen, todo = [], [os.path.normpath(DEVTEST_SRC)]
+    while todo:
+        f = todo.pop()
+        if f in seen:
+            continue
+        seen.append(f)
+        with open(f, encoding="utf-8") as fh:
+            for inc in _INCLUDE.findall(fh.read()):
+                p = os.path.normpath(os.path.join(os.path.dirname(f), inc))
+                if os.path.exists(p):
+                    todo.append(p)
+    return sorted(seen)
+
+
+def devtest_source_hash() -> str:
+    """File times do not survive a copy between machines: the harness is stale when this differs from the
+    dt_source_hash() it was built with."""
+    h = hashlib.sha256()
+    for f in devtest_sources():
+        h.update(os.path.basename(f).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(hashlib.sha256(fh.read()).digest())
+    return h.hexdigest()[:32]
+
+
+def build_devtest(verbose: bool = False) -> str:
+    """Build tests/csrc/libjx_devtest.so (test-only; needs neither torch nor the engine library)."""
+    return compile_and_link([DEVTEST_SRC], DEVTEST_OUT, defines=[f'DT_SRC_HASH="{devtest_source_hash()}"'], verbose=verbose)
+
+
+def devtest_built_hash():
+    """The hash libjx_devtest.so was built with, read from the file (no GPU, no load); None when there is none."""
+    if not os.path.exists(DEVTEST_OUT):
+        return None
+    with open(DEVTEST_OUT, "rb") as fh:
+        m = re.search(rb"DT_SRC_HASH=([0-9a-f]{32})\0", fh.read())
+    return m.group(1).decode() if m else None
+
+
+def build(force: bool = False, verbose: bool = False) -> str:
+    """Build the library (measurement variants live in tools/kernel_probe.hip, not here), then the device harness
+    of the tests when its sources changed."""
+    if force or _stale():
+        compile_and_link(SOURCES, OUT, extra_flags=EXTRA_FLAGS, verbose=verbose)
+    if force or devtest_built_hash() != devtest_source_hash():
+        build_devtest(verbose=verbose)
+    return OUT
+
+
 if __name__ == "__main__":
     print(build(force="--force" in sys.argv, verbose=True))
+    print(DEVTEST_OUT)

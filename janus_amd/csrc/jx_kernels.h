@@ -381,5 +381,46 @@ __device__ __forceinline__ void trunc_add(acc192& a, f128 x, uint32_t sh) {
   a.w2 = a.w2 + w2 + cc;
 }
 
+// A value the optimizer cannot see through (no instruction is emitted): keeps x * 2^j a single
+// v_mad_u64_u32 (x * 2^j + T) instead of the zero-extend + 64-bit shift + 64-bit add it would
+// strength-reduce the multiply to.
+__device__ __forceinline__ uint32_t opaque_u32(uint32_t v) {
+  asm volatile("" : "+v"(v));
+  return v;
+}
+
+// Output-share truncation in the fast XOF kernel (SumVec / Sum):
+//   out_i = sum_{j<bits} 2^j x_{bits*i+j} mod p.
+// Word columns T_w = sum_j x_{j,w} 2^j (< 2^(32+bits) <= 2^64) cost one v_mad_u64_u32 per 32-bit
+// word of each element; the <= 160-bit total is reduced once per output element.
+struct TruncW {
+  uint64_t T[4];
+  uint32_t j, i;
+};
+__device__ __forceinline__ void truncw_zero(TruncW& t) {
+#pragma unroll
+  for (int w = 0; w < 4; w++) t.T[w] = 0;
+}
+// T_w += v_w * sh for the element v, sh = 2^j (or 0 for an element that does not count)
+__device__ __forceinline__ void truncw_mac(TruncW& t, uint4 v, uint32_t sh) {
+  t.T[0] += (uint64_t)v.x * sh;
+  t.T[1] += (uint64_t)v.y * sh;
+  t.T[2] += (uint64_t)v.z * sh;
+  t.T[3] += (uint64_t)v.w * sh;
+}
+__device__ __forceinline__ f128 truncw_value(const TruncW& t) {
+  // V = T0 + T1 2^32 + T2 2^64 + T3 2^96
+  uint32_t c = 0;
+  const uint64_t w0 = addc64(t.T[0], t.T[1] << 32, c);
+  const uint64_t w1 = addc64(t.T[2], (t.T[1] >> 32) | (t.T[3] << 32), c);
+  const uint64_t w2 = (t.T[3] >> 32) + c;
+  return reduce192_small(w0, w1, w2);  // V < 2^(128 + bits), bits <= 32
+}
+
+// h * 2^32 mod p (the high half of a > 32-bit truncation)
+__device__ __forceinline__ f128 shl32_mod(f128 h) {
+  return reduce192(h.lo << 32, (h.hi << 32) | (h.lo >> 32), h.hi >> 32);
+}
+
 }  // namespace jx
 #endif  // __HIPCC__

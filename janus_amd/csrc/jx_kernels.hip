@@ -164,39 +164,8 @@ struct Trunc {
   uint32_t j, i;
 };
 
-// A value the optimizer cannot see through (no instruction is emitted): keeps x * 2^j a single
-// v_mad_u64_u32 (x * 2^j + T) instead of the zero-extend + 64-bit shift + 64-bit add it would
-// strength-reduce the multiply to.
-__device__ __forceinline__ uint32_t opaque_u32(uint32_t v) {
-  asm volatile("" : "+v"(v));
-  return v;
-}
-
-// Output-share truncation in the fast XOF kernel (SumVec / Sum):
-//   out_i = sum_{j<bits} 2^j x_{bits*i+j} mod p.
-// Word columns T_w = sum_j x_{j,w} 2^j (< 2^(32+bits) <= 2^64) cost one v_mad_u64_u32 per 32-bit
-// word of each element; the <= 160-bit total is reduced once per output element.
-struct TruncW {
-  uint64_t T[4];
-  uint32_t j, i;
-};
-__device__ __forceinline__ void truncw_zero(TruncW& t) {
-#pragma unroll
-  for (int w = 0; w < 4; w++) t.T[w] = 0;
-}
-__device__ __forceinline__ f128 truncw_value(const TruncW& t) {
-  // V = T0 + T1 2^32 + T2 2^64 + T3 2^96
-  uint32_t c = 0;
-  const uint64_t w0 = addc64(t.T[0], t.T[1] << 32, c);
-  const uint64_t w1 = addc64(t.T[2], (t.T[1] >> 32) | (t.T[3] << 32), c);
-  const uint64_t w2 = (t.T[3] >> 32) + c;
-  return reduce192_small(w0, w1, w2);  // V < 2^(128 + bits), bits <= 32
-}
-
-// h * 2^32 mod p (the high half of a > 32-bit truncation)
-__device__ __forceinline__ f128 shl32_mod(f128 h) {
-  return reduce192(h.lo << 32, (h.hi << 32) | (h.lo >> 32), h.hi >> 32);
-}
+// (opaque_u32, TruncW, truncw_zero / truncw_mac / truncw_value and shl32_mod: the output-share truncation's word
+// columns, in the device section of jx_kernels.h, where the device tests reach them)
 
 // one measurement element at static stream position e (fast path: no rejections)
 // WIDE (bits in (32, 64], Sum / SumVec): the word columns of bits 0..31 are folded into `lo` at
@@ -212,10 +181,7 @@ __device__ __forceinline__ void emit_meas(const Cfg& c, uint4* mp, uint4* op, ui
   gmax = max(gmax, in ? ge_screen(v) : 0u);
   const bool tin = !c.out_is_meas && e < c.trunc_len;
   const uint32_t sh = opaque_u32(tin ? 1u << (WIDE ? (tr.j & 31u) : tr.j) : 0u);
-  tr.T[0] += (uint64_t)v.x * sh;
-  tr.T[1] += (uint64_t)v.y * sh;
-  tr.T[2] += (uint64_t)v.z * sh;
-  tr.T[3] += (uint64_t)v.w * sh;
+  truncw_mac(tr, v, sh);
   tr.j += tin ? 1u : 0u;
   if (WIDE && tin && tr.j == 32 && c.bits > 32) {
     lo = truncw_value(tr);

@@ -10,6 +10,8 @@
 #include <vector>
 
 #include "../../janus_amd/csrc/jx_chapoly_lanes.h"
+#define JX_TESTOPS_CHAPOLY
+#include "jx_testops.h"  // what each operation computes, shared with the gfx950 harness (devtest.hip)
 
 using namespace jx;
 
@@ -92,10 +94,7 @@ void wave_decrypt(const uint32_t key[8], const uint32_t nonce[3], const uint8_t*
 extern "C" {
 
 // out = h m mod 2^130 - 5 by pl_mul, limbs in and out as they are (the caller checks the ranges)
-void cl_mul(const uint32_t h[5], const uint32_t m[5], uint32_t out[5]) {
-  memcpy(out, h, 20);
-  pl_mul(out, m);
-}
+void cl_mul(const uint32_t h[5], const uint32_t m[5], uint32_t out[5]) { jxt::t_pl_mul(h, m, out); }
 
 // The AEAD tag over (aad, ct) under the Poly1305 key `key` (r || s, 32 bytes; r is clamped as poly1305_init
 // clamps it) as the wave computes it. Returns 1, or 0 when a 32-bit limb sum of the combine wrapped.

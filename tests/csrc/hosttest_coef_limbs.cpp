@@ -5,55 +5,20 @@
 #include <string.h>
 
 #include "../../janus_amd/csrc/jx_field.h"
+#include "jx_testops.h"  // what each operation computes, shared with the gfx950 harness (devtest.hip)
 
 using namespace jx;
-
-static f128 ld(const uint8_t* p) {
-  uint64_t lo, hi;
-  memcpy(&lo, p, 8);
-  memcpy(&hi, p + 8, 8);
-  return make128(lo, hi);
-}
+using namespace jxt;
 
 extern "C" {
 int cl_words(void) { return CD26_WORDS; }
-void cl_to_limbs(const uint8_t* a, uint32_t l[5]) {
-  const limbs26 r = to_limbs26(ld(a));
-  for (int i = 0; i < 5; i++) l[i] = r.l[i];
-}
-void cl_pack(const uint8_t* c, const uint8_t* d, uint32_t* w) { pack_cd26(ld(c), ld(d), w); }
-void cl_unpack(const uint32_t* w, uint32_t cl[5], uint32_t dl[5]) {
-  limbs26 c, d;
-  unpack_cd26(w, c, d);
-  for (int i = 0; i < 5; i++) {
-    cl[i] = c.l[i];
-    dl[i] = d.l[i];
-  }
-}
+void cl_to_limbs(const uint8_t* a, uint32_t l[5]) { t_cl_to_limbs(a, l); }
+void cl_pack(const uint8_t* c, const uint8_t* d, uint32_t* w) { t_cl_pack(c, d, w); }
+void cl_unpack(const uint32_t* w, uint32_t cl[5], uint32_t dl[5]) { t_cl_unpack(w, cl, dl); }
 // The ring's accumulation over n calls of one slot: ae += x_k * d_k, ao += x_k * c_k, as raw column sums.
 // packed = 0: the coefficient limbs split from the 16-byte values at every use; 1: from the staged words.
 void cl_mac(const uint8_t* xs, const uint8_t* cs, const uint8_t* ds, int n, int packed, uint64_t cole[9],
             uint64_t colo[9]) {
-  wacc26 ae, ao;
-  wacc_zero(ae);
-  wacc_zero(ao);
-  for (int k = 0; k < n; k++) {
-    const limbs26 xl = to_limbs26(ld(xs + 16 * k));
-    limbs26 ck, dk;
-    if (packed) {
-      uint32_t w[CD26_WORDS];
-      pack_cd26(ld(cs + 16 * k), ld(ds + 16 * k), w);
-      unpack_cd26(w, ck, dk);
-    } else {
-      ck = to_limbs26(ld(cs + 16 * k));
-      dk = to_limbs26(ld(ds + 16 * k));
-    }
-    wacc_mac(ae, xl, dk);
-    wacc_mac(ao, xl, ck);
-  }
-  for (int s = 0; s < 9; s++) {
-    cole[s] = ae.col[s];
-    colo[s] = ao.col[s];
-  }
+  t_cl_mac(xs, cs, ds, n, packed, cole, colo);
 }
 }

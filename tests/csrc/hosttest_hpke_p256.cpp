@@ -7,6 +7,8 @@
 #include <string.h>
 
 #include "../../janus_amd/csrc/jx_hpke_suites.h"
+#define JX_TESTOPS_P256
+#include "jx_testops.h"  // what each operation computes, shared with the gfx950 harness (devtest.hip)
 
 using namespace jx;
 
@@ -14,40 +16,13 @@ extern "C" {
 
 // a op b mod p on canonical integers (32 big-endian bytes each), through the Montgomery form the kernels use.
 // op: 0 mul, 1 square (of a), 2 inverse (of a; 0 for 0), 3 add, 4 sub. Returns 0 when an operand is >= p.
-int hp_fe_op(int op, const uint8_t a[32], const uint8_t b[32], uint8_t out[32]) {
-  p256_fe x, y, r;
-  if (!p256_from_bytes(x, a) || !p256_from_bytes(y, b)) return 0;
-  switch (op) {
-    case 0: p256_mul(r, x, y); break;
-    case 1: p256_sq(r, x); break;
-    case 2: p256_invert(r, x); break;
-    case 3: p256_add(r, x, y); break;
-    default: p256_sub(r, x, y); break;
-  }
-  p256_to_bytes(out, r);
-  return 1;
-}
+int hp_fe_op(int op, const uint8_t a[32], const uint8_t b[32], uint8_t out[32]) { return jxt::t_p256_fe_op(op, a, b, out); }
 
 // 1: pt (65 bytes) is a valid encoding of a point of the curve
-int hp_point_valid(const uint8_t pt[65]) {
-  p256_fe x, y;
-  return p256_point_from_bytes(x, y, pt) ? 1 : 0;
-}
+int hp_point_valid(const uint8_t pt[65]) { return jxt::t_p256_point_valid(pt); }
 
 // sk (32 big-endian bytes) * pt -> x || y (64 bytes). 0 for an invalid point or the point at infinity.
-int hp_scalar_mul(const uint8_t sk[32], const uint8_t pt[65], uint8_t out[64]) {
-  uint32_t k[8];
-  for (int i = 0; i < 8; i++) {
-    const uint8_t* q = sk + 4 * (7 - i);
-    k[i] = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | q[3];
-  }
-  p256_fe x, y;
-  if (!p256_point_from_bytes(x, y, pt)) return 0;
-  uint8_t x_only[32];
-  const int ok = p256_scalar_mul_xy(out, k, x, y) ? 1 : 0;
-  const int ok_x = p256_scalar_mul_x(x_only, k, x, y) ? 1 : 0;  // what a lane calls
-  return ok && ok_x && memcmp(x_only, out, 32) == 0;
-}
+int hp_scalar_mul(const uint8_t sk[32], const uint8_t pt[65], uint8_t out[64]) { return jxt::t_p256_scalar_mul(sk, pt, out); }
 
 // What jx_hpke_create_key checks of a P-256 keypair: 0 when it is accepted, else 1
 int hp_keypair(const uint8_t sk[32], const uint8_t pk[65]) {

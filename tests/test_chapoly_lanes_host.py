@@ -12,6 +12,7 @@ import subprocess
 import pytest
 
 import hpke_suites_ref as S
+import math_vectors as V
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 P = S.P1305
@@ -26,6 +27,7 @@ def cl():
     hdrs = [os.path.join(HERE, "..", "janus_amd", "csrc", h) for h in ("jx_field.h", "jx_sha256.h", "jx_sha_aes.h", "jx_hpke.h",
                                                                          "jx_ghash_lanes.h", "jx_chapoly.h",
                                                                          "jx_chapoly_lanes.h")]
+    hdrs.append(os.path.join(HERE, "csrc", "jx_testops.h"))
     if not os.path.exists(so) or any(os.path.getmtime(h) > os.path.getmtime(so) for h in hdrs + [src]):
         tmp = f"{so}.{os.getpid()}.tmp"  # atomic: pytest-xdist workers may build concurrently
         subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", tmp, src], check=True)
@@ -59,12 +61,8 @@ def _limbs(x: int):
 def test_product_ranges(cl):
     """pl_mul over the ranges it documents: accumulator limbs < 2^27, multiplier limbs < 2^26 + 2^25. The value is
     the product mod p, and what comes back is carried (limb 1 < 2^26 + 2^10, the others < 2^26)."""
-    rnd = random.Random(1305)
-    hi_h, hi_m = 2**27 - 1, 2**26 + 2**25 - 1
-    cases = [([hi_h] * 5, [hi_m] * 5), ([hi_h] * 5, [0] * 5), ([0] * 5, [hi_m] * 5), ([hi_h] * 5, [1, 0, 0, 0, 0])]
-    cases += [([rnd.randrange(hi_h + 1) for _ in range(5)], [rnd.randrange(hi_m + 1) for _ in range(5)]) for _ in range(300)]
-    cases += [([hi_h if i == k else 0 for i in range(5)], [hi_m if i == j else 0 for i in range(5)])
-              for k in range(5) for j in range(5)]
+    cases = V.pl_mul_cases()
+    assert len(cases) == 329
     out = (ctypes.c_uint32 * 5)()
     for h, m in cases:
         cl.cl_mul((ctypes.c_uint32 * 5)(*h), (ctypes.c_uint32 * 5)(*m), out)

@@ -9,8 +9,9 @@ import subprocess
 
 import pytest
 
+import math_vectors as V
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-P128 = 2**128 - 28 * 2**64 + 1
 M26 = 2**26 - 1
 
 
@@ -19,7 +20,7 @@ def cl():
     src = os.path.join(HERE, "csrc", "hosttest_coef_limbs.cpp")
     so = os.path.join(HERE, "csrc", "libjx_hosttest_coef_limbs.so")
     hdr = os.path.join(HERE, "..", "janus_amd", "csrc", "jx_field.h")
-    if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in (src, hdr)):
+    if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in (src, hdr, os.path.join(HERE, "csrc", "jx_testops.h"))):
         tmp = f"{so}.{os.getpid()}.tmp"  # atomic: pytest-xdist workers may build concurrently
         subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", tmp, src], check=True)
         os.replace(tmp, so)
@@ -42,11 +43,7 @@ def _b(x):
     return ctypes.create_string_buffer(x.to_bytes(16, "little"), 16)
 
 
-def _values():
-    rnd = random.Random(26)
-    one_limb = [M26 << (26 * i) for i in range(4)] + [(2**24 - 1) << 104]
-    return [0, 1, P128 - 1, 2**128 - 1] + one_limb + [rnd.randrange(2**128) for _ in range(1500)] + \
-        [rnd.randrange(P128) for _ in range(1500)]
+_values = V.coef_limb_values
 
 
 def test_unpack_of_pack_is_to_limbs26(cl):
@@ -71,13 +68,9 @@ def test_unpack_of_pack_is_to_limbs26(cl):
 def test_wacc_mac_from_unpacked_rows(cl, n):
     """n calls of one slot (512: the most between two normalisations), operands drawn from the edge values
     and random ones: the same nine columns from the staged words as from to_limbs26, == Python's."""
-    vals = _values()
-    rnd = random.Random(28 + n)
-    for rep in range(40):
-        pool = vals[:9] if rep < 8 else vals
-        xs, cs, ds = ([rnd.choice(pool) for _ in range(n)] for _ in range(3))
-        if rep == 0:
-            xs = cs = ds = [2**128 - 1] * n  # every limb product maximal: 5 * 512 * (2^26 - 1)^2 < 2^64
+    draws = V.coef_mac_operands(n)
+    assert len(draws) == 40
+    for xs, cs, ds in draws:
         bx, bc, bd = (ctypes.create_string_buffer(b"".join(v.to_bytes(16, "little") for v in a), 16 * n)
                       for a in (xs, cs, ds))
         got = {}

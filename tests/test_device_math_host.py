@@ -8,12 +8,11 @@ import subprocess
 
 import pytest
 
+import math_vectors as V
+from math_vectors import M64, P64, P128, P25519, R, _model_take
 from oracle import oracle as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-P128 = 2**128 - 28 * 2**64 + 1
-P64 = 2**64 - 2**32 + 1
-R = 2**128
 
 
 @pytest.fixture(scope="module")
@@ -23,6 +22,7 @@ def ht():
     hdrs = [os.path.join(HERE, "..", "janus_amd", "csrc", h) for h in ("jx_field.h", "jx_keccak.h", "jx_sha256.h",
                                                                          "jx_hpke.h", "jx_sha_aes.h", "jx_sample.h",
                                                                          "jx_flags.h")]
+    hdrs.append(os.path.join(HERE, "csrc", "jx_testops.h"))
     if not os.path.exists(so) or any(os.path.getmtime(h) > os.path.getmtime(so) for h in hdrs + [src]):
         tmp = f"{so}.{os.getpid()}.tmp"  # atomic: pytest-xdist workers may build concurrently
         subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", tmp, src], check=True)
@@ -74,15 +74,8 @@ def f128(L, op, a, b=None):
     return int.from_bytes(out.raw, "little")
 
 
-EDGE = [0, 1, 2, P128 - 1, P128 - 2, 2**127, 2**64, 2**64 - 1, 28 * 2**64 - 1, P128 // 2,
-        # all-ones 32-bit limbs: every column sum and REDC add carries (mont128's carry chains)
-        0xFFFFFFFFFFFFFFE3FFFFFFFFFFFFFFFF, 0xFFFFFFFFFFFFFFE3FFFFFFFF00000000, 2**96 - 1, 2**32 - 1,
-        0xFFFFFFFF00000000FFFFFFFF, 0xFFFFFFFFFFFFFFE300000000FFFFFFFF]
-
-
 def test_field128_add_sub(ht):
-    rnd = random.Random(1)
-    vals = EDGE + [rnd.randrange(P128) for _ in range(200)]
+    vals = V.field128_add_sub_values()
     for a in vals[:60]:
         for b in vals[:60]:
             assert f128(ht, 0, a, b) == (a + b) % P128
@@ -90,9 +83,8 @@ def test_field128_add_sub(ht):
 
 
 def test_field128_montgomery(ht):
-    rnd = random.Random(2)
     rinv = pow(R, P128 - 2, P128)
-    vals = EDGE + [rnd.randrange(P128) for _ in range(300)]
+    vals = V.field128_mont_values()
     for a in vals[:90]:
         for b in vals[:90]:
             assert f128(ht, 2, a, b) == a * b * rinv % P128
@@ -102,10 +94,8 @@ def test_field128_montgomery(ht):
 
 
 def test_field128_mont_lazy_bound(ht):
-    rnd = random.Random(3)
     rinv = pow(R, P128 - 2, P128)
-    for _ in range(500):
-        a, b = rnd.choice(EDGE + [rnd.randrange(P128)]), rnd.randrange(P128)
+    for a, b in V.mont_lazy_cases():
         out = (ctypes.c_uint64 * 3)()
         ht.ht_mont_lazy(_b(a), _b(b), out)
         v = out[0] + (out[1] << 64) + (out[2] << 128)
@@ -113,9 +103,7 @@ def test_field128_mont_lazy_bound(ht):
 
 
 def test_reduce192(ht):
-    rnd = random.Random(4)
-    cases = [0, 1, P128, 2**192 - 1, 2**128, 2**128 - 1, 64 * 2 * P128] + [rnd.randrange(2**192) for _ in range(500)]
-    for v in cases:
+    for v in V.reduce192_cases():
         w = (ctypes.c_uint64 * 3)(v & (2**64 - 1), (v >> 64) & (2**64 - 1), v >> 128)
         out = ctypes.create_string_buffer(16)
         ht.ht_reduce192(w, out)
@@ -124,14 +112,7 @@ def test_reduce192(ht):
 
 def test_reduce192_small(ht):
     """The branch-free reduction of the output-share truncation (top word < 2^32)."""
-    rnd = random.Random(14)
-    cases = [0, 1, P128 - 1, P128, 2**128 - 1, 2**128, 2**160 - 1, 2**128 + 2**64 - 1, (2**32 - 1) << 128,
-             ((2**32 - 1) << 128) + 2**128 - 1, ((2**32 - 1) << 128) | 1, P128 * 255, 2**136 - 1]
-    cases += [rnd.randrange(2**(128 + rnd.randrange(0, 33))) for _ in range(3000)]
-    # tops whose fold carries: w1 close to 2^64
-    cases += [(rnd.randrange(1, 2**32) << 128) | ((2**64 - rnd.randrange(1, 2**40)) << 64) | rnd.randrange(2**64)
-              for _ in range(500)]
-    for v in cases:
+    for v in V.reduce192_small_cases():
         w = (ctypes.c_uint64 * 3)(v & (2**64 - 1), (v >> 64) & (2**64 - 1), v >> 128)
         out = ctypes.create_string_buffer(16)
         ht.ht_reduce192_small(w, out)
@@ -139,8 +120,7 @@ def test_reduce192_small(ht):
 
 
 def test_field64(ht):
-    rnd = random.Random(5)
-    vals = [0, 1, P64 - 1, P64 - 2, 2**32, 2**32 - 1, 2**63] + [rnd.randrange(P64) for _ in range(300)]
+    vals = V.field64_values()
     for a in vals[:70]:
         for b in vals[:70]:
             assert ht.ht_f64(0, a, b) == (a + b) % P64
@@ -183,12 +163,7 @@ def test_xof_block_builder(ht, usage, binder):
 def test_wacc_reduce_columns(ht):
     """wacc_reduce's straight-line fold on raw column sums: every column up to 2^63 (the kernels' bound:
     <= 5 * 512 limb products < 2^52 per column between normalisations), zeros, and random mixes."""
-    rnd = random.Random(11)
-    cases = [[0] * 9, [2**63 - 1] * 9, [2**26 - 1] * 8 + [2**63 - 1], [0] * 8 + [2**63 - 1], [1] + [0] * 8,
-             [2**63 - 1] + [0] * 8, [0, 0, 0, 0, 0, 2**63 - 1, 0, 0, 0]]
-    cases += [[rnd.randrange(2**63) for _ in range(9)] for _ in range(300)]
-    cases += [[rnd.choice([0, 2**26 - 1, 2**63 - 1, rnd.randrange(2**63)]) for _ in range(9)] for _ in range(300)]
-    for cols in cases:
+    for cols in V.wacc_reduce_cases():
         out = ctypes.create_string_buffer(16)
         ht.ht_wacc_reduce((ctypes.c_uint64 * 9)(*cols), out)
         assert int.from_bytes(out.raw, "little") == sum(c << (26 * s) for s, c in enumerate(cols)) % P128, cols
@@ -198,14 +173,7 @@ def test_wacc_reduce_columns(ht):
 def test_wide_dot_accumulator(ht, n, norm):
     """The FLP wire sums: sum x_k c_k mod p with 26-bit limbs and deferred reduction,
     including worst-case operands (p - 1) at the term counts the kernel allows."""
-    rnd = random.Random(n)
-    for trial in range(3):
-        if trial == 0:
-            xs = [P128 - 1] * n
-            cs = [P128 - 1] * n
-        else:
-            xs = [rnd.randrange(P128) for _ in range(n)]
-            cs = [rnd.choice([rnd.randrange(P128), P128 - 1, 2**128 - 2**100]) % P128 for _ in range(n)]
+    for xs, cs in V.wide_dot_operands(n):
         xb = b"".join(x.to_bytes(16, "little") for x in xs)
         cb = b"".join(c.to_bytes(16, "little") for c in cs)
         out = ctypes.create_string_buffer(16)
@@ -214,17 +182,13 @@ def test_wide_dot_accumulator(ht, n, norm):
 
 
 # ---------------------------------------------------------------------------- HPKE primitives (jx_hpke.h)
-P25519 = 2**255 - 19
-
-
 def _buf32(x: int) -> bytes:
     return x.to_bytes(32, "little")
 
 
 def test_fe25519_ops(ht):
     from oracle import hpke_oracle as H  # noqa: F401
-    rnd = random.Random(5)
-    vals = [0, 1, 2, 19, P25519 - 1, P25519 - 19, 2**254, 2**255 - 20] + [rnd.randrange(P25519) for _ in range(40)]
+    vals = V.fe25519_values()
     out = ctypes.create_string_buffer(32)
     for a in vals:
         for b in vals[:12]:
@@ -244,12 +208,9 @@ def test_fe25519_reduction_bounds(ht):
     """The product reduction on the loosest inputs the ladder makes (every limb up to 2^28 - 1): the value is the
     product mod p, and the output limbs stay within what fe_sub's 2p needs (limb 0 <= 2^27 - 38, limbs 1..8 <=
     2^27 - 2, limb 9 <= 2^22 - 2) and small enough that a sum or difference of two stays under 2^28."""
-    rnd = random.Random(25519)
     L = ctypes.c_uint32 * 10
     ht.ht_fe_limbs.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
-    top = (1 << 28) - 1
-    cases = [[top] * 10, [0] * 10, [1] + [0] * 9] + [[rnd.randrange(1 << 28) for _ in range(10)] for _ in range(300)]
-    cases += [[rnd.choice([0, top, 1 << 26, (1 << 26) - 1, 1 << 27]) for _ in range(10)] for _ in range(100)]
+    cases = V.fe25519_loose_limb_cases()
 
     def val(v):
         return sum(x << (26 * i) for i, x in enumerate(v))
@@ -267,14 +228,8 @@ def test_fe25519_reduction_bounds(ht):
 
 def test_x25519_vs_oracle(ht):
     from oracle import hpke_oracle as H
-    rnd = random.Random(11)
     out = ctypes.create_string_buffer(32)
-    cases = [(bytes.fromhex("a546e36bf0527c9d3b16154b82465edd62144c0ac1fc5a18506a2244ba449ac4"),
-              bytes.fromhex("e6db6867583030db3594c1a424b15f7c726624ec26b3353b10a903a6d0ab1c4c"))]
-    cases += [(rnd.randbytes(32), rnd.randbytes(32)) for _ in range(6)]
-    cases += [(rnd.randbytes(32), (9).to_bytes(32, "little")), (rnd.randbytes(32), bytes(32)),
-              (rnd.randbytes(32), b"\xff" * 32)]
-    for k, u in cases:
+    for k, u in V.x25519_cases():
         ht.ht_x25519(k, u, out)
         assert out.raw == H.x25519(k, u)
 
@@ -328,23 +283,14 @@ def test_be_word_shift16(ht):
 
 @pytest.mark.parametrize("n", [1, 91, 1023, 1024, 1025, 3000])
 def test_wacc64_dot(ht, n):
-    rnd = random.Random(n)
-    edge = [0, 1, P64 - 1, P64 - 2, 2**63, 2**32, 2**32 - 1]
-    xs = [rnd.choice(edge) if rnd.random() < 0.3 else rnd.randrange(P64) for _ in range(n)]
-    cs = [rnd.choice(edge) if rnd.random() < 0.3 else rnd.randrange(P64) for _ in range(n)]
-    if n == 1024:  # worst case for the column bound
-        xs, cs = [P64 - 1] * n, [P64 - 1] * n
+    xs, cs = V.wacc64_dot_operands(n)
     ax = (ctypes.c_uint64 * n)(*xs)
     ac = (ctypes.c_uint64 * n)(*cs)
     assert ht.ht_wacc64_dot(ax, ac, n) == sum(x * c for x, c in zip(xs, cs)) % P64
 
 
 def test_reduce192_p64(ht):
-    rnd = random.Random(5)
-    for _ in range(200):
-        w = [rnd.getrandbits(64) for _ in range(3)]
-        if rnd.random() < 0.2:
-            w = [2**64 - 1] * 3
+    for w in V.reduce192_p64_cases():
         a = (ctypes.c_uint64 * 3)(*w)
         assert ht.ht_reduce192_p64(a) == (w[0] + (w[1] << 64) + (w[2] << 128)) % P64
 
@@ -353,118 +299,45 @@ def test_reduce192_p64(ht):
 # (jx_field.h ge_p128 / ge_p64, jx_sample.h): the decode bounds and the skip branches that a real stream
 # reaches once in 2^32 (Field64) or 2^59 (Field128) elements, on hand-built values and Keccak states.
 
-M64 = 2**64 - 1
-HI128 = 0xFFFFFFFFFFFFFFE4  # high half of p128 (its low half is 1)
-BOUND128 = [P128 - 1, P128, P128 + 1, (HI128 << 64) | 2**32, (HI128 + 1) << 64, ((HI128 - 1) << 64) | M64,
-            2**128 - 1, HI128 << 64, (HI128 << 64) | 2, (HI128 << 64) | 2**63, 0, 1, 2**64, 2**127,
-            ((HI128 - 1) << 64) | 1, (0xFFFFFFFF << 96) | 1, (0xFFFFFFFFFFFFFFFF << 64)]
-BOUND64 = [P64 - 1, P64, P64 + 1, 0xFFFFFFFF80000000, 0xFFFFFFFEFFFFFFFF, M64, 0xFFFFFFFF00000000, 0xFFFFFFFF00010000,
-           0xFFFFFFFE00000001, 0, 1, 2**32, 2**63]
-
-
 @pytest.mark.parametrize("fn", ["ht_ge_p128", "ht_ge_exact"])
 def test_ge_p128_exact(ht, fn):
     """ge_p128 (f128, the samplers and the verifier decode) and ge_exact (uint4, the leader's decode of its
     explicit input share) against Python integers."""
-    rnd = random.Random(41)
-    vals = BOUND128 + [rnd.randrange(2**128) for _ in range(300)]
-    vals += [(HI128 << 64) | rnd.randrange(2**64) for _ in range(50)]            # only the low half decides
-    vals += [(rnd.randrange(HI128 - 3, 2**64) << 64) | rnd.randrange(4) for _ in range(100)]
-    for v in vals:
+    for v in V.ge_p128_values():
         assert getattr(ht, fn)(_b(v)) == int(v >= P128), hex(v)
 
 
 def test_ge_p64_exact(ht):
-    rnd = random.Random(42)
-    vals = BOUND64 + [rnd.randrange(2**64) for _ in range(300)]
-    vals += [(0xFFFFFFFF << 32) | rnd.randrange(2**32) for _ in range(50)]
-    vals += [(0xFFFFFFFF << 32) | (1 << k) for k in range(32)]                   # any one low bit decides
-    vals += [(rnd.randrange(2**32 - 4, 2**32) << 32) | rnd.randrange(3) for _ in range(100)]
-    for v in vals:
+    for v in V.ge_p64_values():
         assert ht.ht_ge_p64(v & 0xFFFFFFFF, v >> 32) == int(v >= P64), hex(v)
 
 
 def test_ge_screen_is_a_superset_and_survives_the_running_max(ht):
     """ge_screen == 0xFFFFFFFF for every v >= p128 (it may also fire just below p), and the per-block running
     max still says so with any number of smaller elements before and after."""
-    rnd = random.Random(43)
-    ge = [v for v in BOUND128 if v >= P128] + [rnd.randrange(P128, 2**128) for _ in range(300)]
-    ge += [(hi << 64) | lo for hi in range(HI128, 2**64) for lo in (0, 1, 2, 2**32, M64) if (hi << 64) | lo >= P128]
+    ge, windows, quiet = V.ge_screen_cases()
+    assert len(ge) >= 400 and len(windows) == 120
     for v in ge:
         assert ht.ht_ge_screen_max(_b(v), 1) == 0xFFFFFFFF, hex(v)
-    for v in [0, 1, 2**64, 2**127, (0xFFFFFFFF << 96) - 1, (0xFFFFFFFE << 96) | (2**96 - 1)]:  # far below p: quiet
+    for v in V.GE_SCREEN_QUIET:  # far below p: quiet
         assert ht.ht_ge_screen_max(_b(v), 1) != 0xFFFFFFFF, hex(v)
-    for v in ge[:40]:
-        for k in (0, 3, 7):
-            elems = [rnd.randrange(2**126) for _ in range(8)]
-            elems[k] = v
-            buf = ctypes.create_string_buffer(b"".join(e.to_bytes(16, "little") for e in elems), 128)
-            assert ht.ht_ge_screen_max(buf, 8) == 0xFFFFFFFF
-    quiet = ctypes.create_string_buffer(b"".join(rnd.randrange(2**126).to_bytes(16, "little") for _ in range(8)), 128)
+    for elems in windows:
+        buf = ctypes.create_string_buffer(b"".join(e.to_bytes(16, "little") for e in elems), 128)
+        assert ht.ht_ge_screen_max(buf, 8) == 0xFFFFFFFF
+    quiet = ctypes.create_string_buffer(b"".join(e.to_bytes(16, "little") for e in quiet), 128)
     assert ht.ht_ge_screen_max(quiet, 8) != 0xFFFFFFFF
-
-
-def _state(rnd, field_bytes):
-    """25 random lanes whose rate part holds no encoding >= p (so every rejection is one the test placed)."""
-    st = [rnd.randrange(2**64) for _ in range(25)]
-    for i in range(21):
-        if field_bytes == 8 and st[i] >> 32 == 0xFFFFFFFF:
-            st[i] &= 2**63 - 1
-        if field_bytes == 16 and i % 2 == 1:
-            st[i] &= 2**63 - 1
-    return st
-
-
-def _model_take(st, nbytes, count, p, pos=0, whole_chunks=0):
-    """Rejection sampling over the sponge's byte stream from byte `pos` of the block in st (168-byte rate,
-    Keccak-p[1600,12] between blocks), by the oracle's permutation. whole_chunks > 0: only that many
-    aligned chunks of each block are looked at (the kernels' register-resident samplers). Returns
-    (samples, final state, final position)."""
-    out, st = [], list(st)
-    while True:
-        blk = b"".join(x.to_bytes(8, "little") for x in st[:21])
-        limit = whole_chunks * nbytes if whole_chunks else 168
-        while pos + nbytes <= limit and len(out) < count:
-            x = int.from_bytes(blk[pos:pos + nbytes], "little")
-            pos += nbytes
-            if x < p:
-                out.append(x)
-        if len(out) >= count:
-            return out, st, pos
-        assert whole_chunks or pos + nbytes > 168
-        carry = blk[pos:168] if not whole_chunks else b""
-        st = O.keccak_p1600(st, 12)
-        pos = 0
-        if carry:  # an element straddling two blocks
-            blk = b"".join(x.to_bytes(8, "little") for x in st[:21])
-            need = nbytes - len(carry)
-            x = int.from_bytes(carry + blk[:need], "little")
-            pos = need
-            if x < p:
-                out.append(x)
-                if len(out) >= count:
-                    return out, st, pos
 
 
 def _u64s(vals):
     return (ctypes.c_uint64 * len(vals))(*vals)
 
 
-GE64 = [P64, M64, 0xFFFFFFFF80000000, P64 + 1, 0xFFFFFFFF00010000]
-
-
 @pytest.mark.parametrize("n", [1, 5])
 def test_sample64_skips_rejected_chunks(ht, n):
-    rnd = random.Random(50 + n)
-    cases = [[k] for k in range(21)]                                    # one rejection at every position
-    cases += [[0, 1], [0, 1, 2, 3], [3, 4, 5, 9], [19, 20], list(range(0, 17)), list(range(1, 21)),
-              list(range(21 - n + 1)),                                  # fewer than n left: the next block is needed
-              list(range(21))]                                          # none left
+    cases = V.sample64_cases(n)
+    assert len(cases) == 30
     permuted = 0
-    for ci, rej in enumerate(cases):
-        st = _state(rnd, 8)
-        for j, k in enumerate(rej):
-            st[k] = GE64[(ci + j) % len(GE64)]
+    for rej, st in cases[:-1]:
         want, st_after, _ = _model_take(st, 8, n, P64, whole_chunks=21)
         buf, out = _u64s(st), (ctypes.c_uint64 * 5)()
         ht.ht_sample64(n, buf, out)
@@ -473,47 +346,34 @@ def test_sample64_skips_rejected_chunks(ht, n):
         permuted += st_after != st
     assert permuted >= 2
     # the largest element is taken, not skipped
-    st = _state(rnd, 8)
-    st[0] = P64 - 1
+    st = cases[-1][1]
+    assert st[0] == P64 - 1
     buf, out = _u64s(st), (ctypes.c_uint64 * 5)()
     ht.ht_sample64(n, buf, out)
     assert out[0] == P64 - 1
 
 
-GE128 = [P128, P128 + 1, 2**128 - 1, (HI128 << 64) | 2**32, (HI128 + 1) << 64]
-
-
-def _set128(st, chunk, v):
-    st[2 * chunk], st[2 * chunk + 1] = v & M64, v >> 64
-
-
 @pytest.mark.parametrize("cnt", [1, 2])
 def test_sample2_f128_fast_flags_and_slow_skips(ht, cnt):
     FLAG_SLOW, other = 4, 16
-    rnd = random.Random(60 + cnt)
-    for rej in ([], [0], [1], [0, 1], [2], [0, 2], [1, 2, 3], [0, 1, 2, 3, 4, 5, 6, 7, 8]):
-        for gi, g in enumerate(GE128):
-            st = _state(rnd, 16)
-            for j, k in enumerate(rej):
-                _set128(st, k, GE128[(gi + j) % len(GE128)])
-            if not rej:
-                _set128(st, 0, P128 - 1)  # the largest element: taken, no flag
-                _set128(st, 1, ((HI128 - 1) << 64) | M64)
-            chunks = [st[2 * k] | (st[2 * k + 1] << 64) for k in range(10)]
-            # fast: the first cnt chunks as they are, FLAG_SLOW exactly when one of them is >= p
-            buf, out, flags = _u64s(st), ctypes.create_string_buffer(32), ctypes.c_uint32(other)
-            ht.ht_sample2_f128(buf, cnt, 0, out, ctypes.byref(flags))
-            got = [int.from_bytes(out.raw[16 * i:16 * i + 16], "little") for i in range(2)]
-            assert got[:cnt] == chunks[:cnt]
-            assert flags.value == other | (FLAG_SLOW if any(c >= P128 for c in chunks[:cnt]) else 0), (rej, cnt)
-            assert list(buf) == st
-            # slow: the first cnt accepted chunks
-            want, st_after, _ = _model_take(st, 16, cnt, P128, whole_chunks=10)
-            buf, out, flags = _u64s(st), ctypes.create_string_buffer(32), ctypes.c_uint32(other)
-            ht.ht_sample2_f128(buf, cnt, 1, out, ctypes.byref(flags))
-            got = [int.from_bytes(out.raw[16 * i:16 * i + 16], "little") for i in range(2)]
-            assert got[:cnt] == want, (rej, cnt)
-            assert flags.value == other and list(buf) == st_after
+    cases = V.sample2_cases(cnt)
+    assert len(cases) == 40
+    for rej, st in cases:
+        chunks = [st[2 * k] | (st[2 * k + 1] << 64) for k in range(10)]
+        # fast: the first cnt chunks as they are, FLAG_SLOW exactly when one of them is >= p
+        buf, out, flags = _u64s(st), ctypes.create_string_buffer(32), ctypes.c_uint32(other)
+        ht.ht_sample2_f128(buf, cnt, 0, out, ctypes.byref(flags))
+        got = [int.from_bytes(out.raw[16 * i:16 * i + 16], "little") for i in range(2)]
+        assert got[:cnt] == chunks[:cnt]
+        assert flags.value == other | (FLAG_SLOW if any(c >= P128 for c in chunks[:cnt]) else 0), (rej, cnt)
+        assert list(buf) == st
+        # slow: the first cnt accepted chunks
+        want, st_after, _ = _model_take(st, 16, cnt, P128, whole_chunks=10)
+        buf, out, flags = _u64s(st), ctypes.create_string_buffer(32), ctypes.c_uint32(other)
+        ht.ht_sample2_f128(buf, cnt, 1, out, ctypes.byref(flags))
+        got = [int.from_bytes(out.raw[16 * i:16 * i + 16], "little") for i in range(2)]
+        assert got[:cnt] == want, (rej, cnt)
+        assert flags.value == other and list(buf) == st_after
 
 
 def test_bx_sample128_rejection_before_a_block_boundary(ht):
@@ -521,30 +381,20 @@ def test_bx_sample128_rejection_before_a_block_boundary(ht):
     168-byte block boundary, at several alignments of the stream. Rejections are placed in the first block
     only: what the permutation leaves in the next block cannot be chosen, so the straddling element itself
     and those after it are always below p."""
-    rnd = random.Random(70)
-    # (first byte, elements to take, indices of the rejected elements); the successor of the last rejected
-    # element covers bytes 160..175, 152..167 + 0..7 of the next block, ... according to the alignment
-    for pos0, nelem, rej_at in [(0, 12, [9]), (0, 12, [8, 9]), (8, 12, [0, 9]), (144, 3, [0]), (4, 12, [3]),
-                                (4, 12, [9]), (12, 12, [8])]:
-        for g in GE128:
-            # elements are 16 bytes from byte pos0; the element at index e covers bytes pos0 + 16 e ..
-            st = _state(rnd, 8)
-            blk = bytearray(b"".join(x.to_bytes(8, "little") for x in st[:21]))
-            for e in range((168 - pos0) // 16):  # keep the unplaced first-block elements below p
-                blk[pos0 + 16 * e + 15] &= 0x7F
-            for e in rej_at:
-                assert pos0 + 16 * e + 16 <= 168
-                blk[pos0 + 16 * e:pos0 + 16 * e + 16] = g.to_bytes(16, "little")
-            st[:21] = [int.from_bytes(blk[8 * i:8 * i + 8], "little") for i in range(21)]
-            want, st_after, pos_after = _model_take(st, 16, nelem, P128, pos=pos0)
-            buf, out = _u64s(st), ctypes.create_string_buffer(16 * nelem)
-            pos = ht.ht_bx_sample128(buf, pos0, nelem, out)
-            got = [int.from_bytes(out.raw[16 * i:16 * i + 16], "little") for i in range(nelem)]
-            assert got == want, (pos0, rej_at)
-            assert pos == pos_after and list(buf) == st_after
+    cases = V.bx_sample_cases()
+    assert len(cases) == 36
+    # (first byte, elements to take, indices of the rejected elements, the state): elements are 16 bytes from byte
+    # pos0; the element at index e covers bytes pos0 + 16 e ..
+    for pos0, nelem, rej_at, st in cases[:-1]:
+        want, st_after, pos_after = _model_take(st, 16, nelem, P128, pos=pos0)
+        buf, out = _u64s(st), ctypes.create_string_buffer(16 * nelem)
+        pos = ht.ht_bx_sample128(buf, pos0, nelem, out)
+        got = [int.from_bytes(out.raw[16 * i:16 * i + 16], "little") for i in range(nelem)]
+        assert got == want, (pos0, rej_at)
+        assert pos == pos_after and list(buf) == st_after
     # no rejection at all: the eleventh element is the straddling one (bytes 160..167 and 0..7 of the next block)
-    st = _state(rnd, 8)
-    st[20] = M64
+    st = cases[-1][3]
+    assert st[20] == M64
     want, st_after, pos_after = _model_take(st, 16, 12, P128)
     buf, out = _u64s(st), ctypes.create_string_buffer(16 * 12)
     assert ht.ht_bx_sample128(buf, 0, 12, out) == pos_after

@@ -11,6 +11,7 @@ import subprocess
 import pytest
 
 import hpke_p256_ref as R
+import math_vectors as V
 import hpke_suites_ref as S
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -24,6 +25,7 @@ def hp():
     hdrs = [os.path.join(HERE, "..", "janus_amd", "csrc", h) for h in ("jx_field.h", "jx_sha256.h", "jx_sha_aes.h", "jx_hpke.h",
                                                                          "jx_sha512.h", "jx_chapoly.h", "jx_hpke_suites.h",
                                                                          "jx_p256.h")]
+    hdrs.append(os.path.join(HERE, "csrc", "jx_testops.h"))
     if not os.path.exists(so) or any(os.path.getmtime(h) > os.path.getmtime(so) for h in hdrs + [src]):
         tmp = f"{so}.{os.getpid()}.tmp"  # atomic: pytest-xdist workers may build concurrently
         subprocess.run(["g++", "-O2", "-std=c++17", "-shared", "-fPIC", "-o", tmp, src], check=True)
@@ -49,13 +51,7 @@ def _op(hp, op: int, a: int, b: int = 0) -> int:
     return int.from_bytes(out.raw, "big")
 
 
-def _operands():
-    rnd = random.Random(256)
-    edge = [0, 1, 2, P - 1, P - 2, (P - 1) // 2, (P + 1) // 2]
-    for k in (31, 32, 33, 63, 64, 95, 96, 97, 128, 191, 192, 193, 223, 224, 225, 255):
-        edge += [2**k - 1, 2**k, 2**k + 1]
-    edge += [2**256 - 2**224, 2**224 - 1, 0xFFFFFFFF << 224, P - 2**32, P - 2**96, (1 << 255) + (1 << 32) - 1]
-    return [v % P for v in edge], [rnd.randrange(P) for _ in range(40)]
+_operands = V.p256_operands
 
 
 def test_field_mul_sq_against_python_integers(hp):
@@ -94,16 +90,14 @@ def test_field_refuses_unreduced_operands(hp):
         assert hp.hp_fe_op(0, _b(1), _b(v), out) == 0
 
 
-def _points():
-    rnd = random.Random(2561)
-    return [R.G, R.neg(R.G)] + [R.mul(rnd.randrange(1, N), R.G) for _ in range(3)]
+_points = V.p256_points
 
 
 def test_scalar_mul_exceptional_and_random_scalars(hp):
     """sk * P at the scalars where an incomplete ladder goes wrong (leading zero bits, 1, 2, n - 1, n - 2, the two
     halves of n, single bits) and at random ones, on G, -G and random points."""
-    rnd = random.Random(2562)
-    sks = [1, 2, 3, N - 1, N - 2, (N - 1) // 2, (N + 1) // 2, 2**128, 2**255] + [rnd.randrange(1, N) for _ in range(20)]
+    sks = V.p256_scalars()
+    assert len(sks) == 29
     out = ctypes.create_string_buffer(64)
     for pt in _points():
         for k in sks:
