@@ -261,6 +261,40 @@ int32_t jx_helper_prep_encrypted_batch2(jx_engine* e, uint64_t n, const uint8_t*
                                         const uint64_t* payload_offsets, uint32_t flags,
                                         const uint8_t* leader_prep_shares, uint8_t* out_prep_msgs, uint8_t* out_verdicts,
                                         uint8_t* out_open_status, uint64_t* out_batch_id);
+/* The fused prepare + aggregate (jx_helper_prep_aggregate / _device below) from report shares still under HPKE: what
+ * a helper serves, at the size the fused path is built for. The call is cut into the same launches over the same
+ * pipelines as the plaintext call, and every launch opens its own reports first, with the rows kernels of
+ * jx_helper_prep_encrypted_batch2: no resident batch, no limit of one launch's staging. Per report the semantics
+ * are exactly that call's (keypairs tried in the same order, a trial only when the encapsulated key has the
+ * length of the keypair's KEM, JX_KEY_NONE / JX_KEY_MALFORMED, JX_ENC_REQUIRE_TASKPROV); a report that fails
+ * before helper_initialized gets verdict JX_OPEN_FAILURE and its JX_OPEN_* status. Exactly the reports with verdict
+ * JX_FINISHED are accumulated: a report that did not open never reaches an aggregation. The arguments are checked
+ * as there (key indices, decreasing offsets, a payload of 2^32 bytes or more, a keypair on another device, unknown
+ * flags): JX_E_INVALID before anything is queued, the aggregations untouched. n == 0 is JX_OK.
+ * Host form: host buffers, one `segment`; out_prep_msgs, out_verdicts and out_open_status nullable; returns with
+ * the results in the caller's buffers.
+ * Device form: device pointers for the bulk data (report ids, public shares, encapsulated keys, payloads, leader
+ * prep shares, the three nullable outputs) and HOST arrays for times, key_index, enc_offsets (NULL: n x 32 bytes)
+ * and payload_offsets, as jx_leader_upload_open_device takes them; d_segment / segment_ids / nsegments as
+ * jx_helper_prep_aggregate_device. Asynchronous on the engine stream; the host arrays are consumed before it
+ * returns. The ciphertexts and encapsulated keys are read in place from the caller's arrays (which must stay
+ * unchanged until the call's work has run), and the per-report rows are laid out on the device, so nothing but
+ * 26 bytes per report crosses the host. */
+int32_t jx_helper_prep_aggregate_encrypted(jx_engine* e, uint64_t n, const uint8_t* nonces, const uint64_t* times,
+                                           const uint8_t* public_shares, const uint8_t task_id[32],
+                                           jx_hpke* const* keypairs, uint32_t nkeypairs, const uint8_t* key_index,
+                                           const uint8_t* encs, const uint64_t* enc_offsets, const uint8_t* payloads,
+                                           const uint64_t* payload_offsets, uint32_t flags,
+                                           const uint8_t* leader_prep_shares, uint32_t segment, uint8_t* out_prep_msgs,
+                                           uint8_t* out_verdicts, uint8_t* out_open_status);
+int32_t jx_helper_prep_aggregate_encrypted_device(jx_engine* e, uint64_t n, const void* d_nonces, const uint64_t* times,
+                                                  const void* d_public_shares, const uint8_t task_id[32],
+                                                  jx_hpke* const* keypairs, uint32_t nkeypairs,
+                                                  const uint8_t* key_index, const void* d_encs,
+                                                  const uint64_t* enc_offsets, const void* d_payloads,
+                                                  const uint64_t* payload_offsets, uint32_t flags, const void* d_lps,
+                                                  const void* d_segment, const uint32_t* segment_ids, uint32_t nsegments,
+                                                  void* d_out_prep_msgs, void* d_out_verdicts, void* d_out_open_status);
 /* Handle of the most recently prepared batch if it is still resident (0 otherwise). */
 int32_t jx_engine_batch_id(const jx_engine* e, uint64_t* batch_id);
 /* Resident batches and the device bytes they hold (either pointer nullable). */

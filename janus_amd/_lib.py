@@ -25,6 +25,7 @@ EXPORTED_SYMBOLS = (
     "jx_engine_wait_stream", "jx_engine_join_stream", "jx_engine_wait_event", "jx_engine_record_event",
     "jx_engine_memory", "jx_engine_coalesce", "jx_leader_prep_init_device_ex", "jx_helper_prep_encrypted_batch",
     "jx_helper_prep_encrypted_batch2", "jx_leader_upload_open_batch", "jx_leader_upload_open_device",
+    "jx_helper_prep_aggregate_encrypted", "jx_helper_prep_aggregate_encrypted_device",
 )
 
 _lib = None
@@ -100,6 +101,10 @@ def load():
         "jx_accumulate_device": (i32, [vp, u64, u64, vp, vp, P(u32), u32]),
         "jx_helper_prep_aggregate": (i32, [vp, u64, u8p, u8p, u8p, u8p, u32, u8p, u8p]),
         "jx_helper_prep_aggregate_device": (i32, [vp, u64, vp, vp, vp, vp, vp, P(u32), u32, vp, vp]),
+        "jx_helper_prep_aggregate_encrypted": (i32, [vp, u64, u8p, P(u64), u8p, u8p, P(vp), u32, u8p, u8p, P(u64), u8p,
+                                                      P(u64), u32, u8p, u32, u8p, u8p, u8p]),
+        "jx_helper_prep_aggregate_encrypted_device": (i32, [vp, u64, vp, P(u64), vp, u8p, P(vp), u32, u8p, vp, P(u64),
+                                                             vp, P(u64), u32, vp, vp, P(u32), u32, vp, vp, vp]),
         "jx_aggregate_read": (i32, [vp, u32, u8p, P(u64)]),
         "jx_aggregate_checksum": (i32, [vp, u32, u8p]),
         "jx_aggregate_reset": (i32, [vp]),

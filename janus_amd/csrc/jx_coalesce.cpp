@@ -875,44 +875,21 @@ static Lane* reserve(Coalescer* C, std::unique_lock<std::mutex>& lk, CReq* r, in
   }
 }
 
-// Lay out one job's EncRows (its ciphertexts at ct_base + their offset within the job).
-uint64_t fill_enc_rows(const EncJob& j, uint64_t n, EncRow* rows, uint64_t ct_base, uint8_t* enc65) {
-  const uint64_t c0 = j.payload_offsets[0], enc65_base = ct_base + j.payload_bytes(n);
-  uint64_t n65 = 0;
-  uint32_t klen[JX_ENC_MAX_KEYPAIRS];
-  uint16_t slot[JX_ENC_MAX_KEYPAIRS];  // the request's keypair index -> its slot of the device's key registry
+// Lay out one job's EncRows (its ciphertexts at ct_base + their offset within the job): the request's keypairs as
+// registry slots and KEM lengths, then the loop and the per-row rule of jx_enc_rows.h.
+EncRowKeys enc_row_keys(const EncJob& j) {
+  EncRowKeys K{};
+  K.nkeys = j.nkeys;
+  K.flags = j.flags;
   for (uint32_t k = 0; k < j.nkeys; k++) {
-    klen[k] = hpke_enc_len(j.keypairs[k]);
-    slot[k] = hpke_slot(j.keypairs[k]);
+    K.klen[k] = (uint8_t)hpke_enc_len(j.keypairs[k]);
+    K.slot[k] = hpke_slot(j.keypairs[k]);
   }
-  for (uint64_t i = 0; i < n; i++) {
-    EncRow& w = rows[i];
-    memset(&w, 0, sizeof w);
-    memcpy(w.task_id, j.task_id, 32);
-    const uint64_t t = j.times[i];
-    for (int b = 0; b < 8; b++) w.time_be[b] = (uint8_t)(t >> (56 - 8 * b));
-    w.ct_off = ct_base + (j.payload_offsets[i] - c0);
-    w.ct_len = (uint32_t)(j.payload_offsets[i + 1] - j.payload_offsets[i]);
-    const uint8_t k0 = j.key_index[2 * i], k1 = j.key_index[2 * i + 1];
-    w.flags = ENC_ROW_ENCRYPTED | ((j.flags & JX_ENC_REQUIRE_TASKPROV) ? ENC_ROW_REQUIRE_TASKPROV : 0);
-    // a trial can only succeed when the encapsulated key has the length of the keypair's KEM (32: X25519, 65:
-    // P-256); the others fail as the hpke crate's deserialisation does, on the device by the key row's KEM id
-    const uint64_t len = j.enc_len(i);
-    const bool fits = (k0 < j.nkeys && klen[k0] == len) || (k1 < j.nkeys && klen[k1] == len);
-    if (k0 == JX_KEY_MALFORMED || (k0 < j.nkeys && !fits)) {
-      w.flags |= ENC_ROW_MALFORMED;
-    } else if (fits && len == 65) {
-      w.flags |= ENC_ROW_ENC65;
-      w.enc65_off = enc65_base + 65 * n65;
-      memcpy(enc65 + 65 * n65, j.enc(i), 65);
-      n65++;
-    } else if (len == 32) {
-      memcpy(w.enc, j.enc(i), 32);
-    }
-    w.key0 = k0 < j.nkeys ? slot[k0] : (k0 == JX_KEY_MALFORMED ? (uint16_t)0 : KEY_SLOT_NONE);
-    w.key1 = k1 < j.nkeys ? slot[k1] : KEY_SLOT_NONE;
-  }
-  return n65;
+  return K;
+}
+uint64_t fill_enc_rows(const EncJob& j, uint64_t n, EncRow* rows, uint64_t ct_base, uint8_t* enc65) {
+  return fill_enc_rows_with(enc_row_keys(j), j.task_id, j.times, j.key_index, j.encs, j.enc_offsets, j.payload_offsets, n,
+                            rows, ct_base, ct_base + j.payload_bytes(n), enc65);
 }
 
 // The coalesced prepare of one job (both roles).

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/jx_prio3.h"
+#include "jx_enc_rows.h"
 #include "jx_kernels.h"
 
 namespace jxi {
@@ -125,6 +126,8 @@ enum : uint32_t {
   SG_VK = 128,   // coalesced launches: one verify key per report (16 B; multiproof: HMAC pads, 64 B)
   SG_JOBS = 512, // coalesced launches: the job table (MAX_JOBS_PER_LAUNCH slices)
   SG_ENC = 1024, // encrypted helper inputs: EncRows, ciphertext + plaintext bytes (enc_ct_bytes each), open status
+  SG_ENCC = 2048, // sealed fused call, device form: a launch's compact per-report arrays (times, key indices, the two
+                  // offset slices: 26 bytes per report), which enc_rows_kernel expands into the EncRows
 };
 
 // One job's encrypted input shares (jx_helper_prep_encrypted_batch), as the caller passed them.
@@ -152,6 +155,10 @@ struct EncJob {
 // at ct_base + the job's payload bytes; ENC_ROW_ENC65). A key whose length fits neither keypair's KEM marks the
 // row malformed. Returns the number of ENC_ROW_ENC65 rows.
 uint64_t fill_enc_rows(const EncJob& j, uint64_t n, jx::EncRow* rows, uint64_t ct_base, uint8_t* enc65);
+// The job's keypairs as the row rule reads them (jx_enc_rows.h): registry slots and KEM lengths by keypair index.
+jx::EncRowKeys enc_row_keys(const EncJob& j);
+// enc_rows_kernel (jx_hpke.hip): the EncRows of one launch of the sealed fused call's device form, on the device.
+hipError_t launch_enc_rows(const jx::EncRowsArgs& a, hipStream_t s);
 // jx_hpke.hip
 int hpke_device(const jx_hpke* h);
 // The context's slot of its device's key registry (jx_keyreg.h), its own from creation to jx_hpke_destroy, and the
@@ -240,6 +247,14 @@ struct jx_engine {
   jx::EncRow* d_encrows = nullptr;
   uint8_t *d_ct = nullptr, *d_pt = nullptr, *d_status = nullptr;
   uint64_t enc_ct_bytes = 0;
+  // SG_ENCC: the compact arrays of one launch
+  uint64_t *d_ec_times = nullptr, *d_ec_eoff = nullptr, *d_ec_poff = nullptr;
+  uint8_t* d_ec_kidx = nullptr;
+  // pinned host copy of a sealed fused device call's compact arrays, so that the call returns once queued: reused
+  // after ev_henc (the engine stream behind the last call that read it) has completed
+  uint8_t* h_enc = nullptr;
+  uint64_t h_enc_cap = 0;
+  hipEvent_t ev_henc = nullptr;
   uint32_t acc_chunks = 0;  // report chunks of the accumulate kernel (0: acc_nchunks picks)
   std::map<uint32_t, jxi::Segment> segs;  // running batch aggregations (the engine as one shard)
   std::vector<jxi::Slab> seg_slabs;       // their states, kSegsPerSlab per arena slab

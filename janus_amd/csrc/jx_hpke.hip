@@ -24,8 +24,9 @@
 //    input-share row K1 reads, with one status byte per report (include/jx_prio3.h, JX_OPEN_*).
 // C ABI in include/jx_hpke.h; the rows kernel's launcher is internal (jx_engine_internal.h).
 //
-// This unit holds the C ABI, the key registry, open_mask_kernel and the two dispatchers, launch_open and
-// jxi::launch_hpke_rows. Each kernel pair is a translation unit of its own, so that the three compile side by side:
+// This unit holds the C ABI, the key registry, open_mask_kernel, enc_rows_kernel (the rows of a launch of the sealed
+// fused call's device form, laid out on the device by the rule of jx_enc_rows.h) and the two dispatchers, launch_open
+// and jxi::launch_hpke_rows. Each kernel pair is a translation unit of its own, so that the three compile side by side:
 // jx_hpke_default.hip, jx_hpke_suite.hip and jx_hpke_p256.hip; what they share is in jx_hpke_open.h.
 #include <hip/hip_runtime.h>
 
@@ -48,6 +49,35 @@ namespace {
 __global__ __launch_bounds__(256) void open_mask_kernel(const uint8_t* status, uint8_t* verdicts, uint64_t n) {
   const uint64_t r = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (r < n && status[r] != JX_OPEN_OK) verdicts[r] = JX_OPEN_FAILURE;
+}
+
+// The EncRows of one launch from the caller's compact arrays (jx_enc_rows.h), one report per lane. A lane reads its
+// 26 bytes of the staged arrays (neighbouring lanes neighbouring addresses) and its encapsulated key where it lies in
+// the caller's array (32 contiguous bytes per lane when every key is an X25519 one), makes its row with the rule the
+// host loop uses, and the workgroup writes its ENC_ROWS_WG rows, which are contiguous in memory, through LDS in
+// whole dwords: lane t stores dwords t, t + 256, ... of the workgroup's span, so every store instruction covers 1 KiB
+// without a gap (a lane storing its own 104-byte row would touch 64 cache lines per instruction).
+constexpr uint32_t ENC_ROWS_WG = 256, ENC_ROW_WORDS = sizeof(EncRow) / 4;
+__global__ __launch_bounds__(ENC_ROWS_WG) void enc_rows_kernel(const EncRowsArgs a) {
+  __shared__ uint32_t sm[ENC_ROWS_WG * ENC_ROW_WORDS];
+  const uint64_t r0 = (uint64_t)blockIdx.x * ENC_ROWS_WG, r = r0 + threadIdx.x;
+  if (r < a.n) {
+    const uint64_t eo = a.enc_offsets ? a.enc_offsets[r] : 32 * (a.first + r);
+    const uint64_t elen = a.enc_offsets ? a.enc_offsets[r + 1] - eo : 32;
+    const uint64_t p0 = a.payload_offsets[r], p1 = a.payload_offsets[r + 1];
+    EncRow w;
+    enc_row_make(w, a.keys, a.task_id, a.times[r], a.key_index[2 * r], a.key_index[2 * r + 1], a.encs + eo, elen, p0,
+                 (uint32_t)(p1 - p0), a.enc65_base + 65 * r, a.enc65 + 65 * r);
+    uint32_t words[ENC_ROW_WORDS];
+    __builtin_memcpy(words, &w, sizeof w);
+#pragma unroll
+    for (uint32_t k = 0; k < ENC_ROW_WORDS; k++) sm[threadIdx.x * ENC_ROW_WORDS + k] = words[k];
+  }
+  __syncthreads();
+  const uint64_t left = a.n - r0;  // r0 < n: the grid is ceil(n / ENC_ROWS_WG) workgroups
+  const uint32_t nw = (uint32_t)(left < ENC_ROWS_WG ? left : ENC_ROWS_WG) * ENC_ROW_WORDS;
+  uint32_t* out = reinterpret_cast<uint32_t*>(a.rows + r0);
+  for (uint32_t i = threadIdx.x; i < nw; i += ENC_ROWS_WG) out[i] = sm[i];
 }
 
 }  // namespace
@@ -179,6 +209,12 @@ hipError_t launch_hpke_rows(const HpkeRowsArgs& a, bool suites, bool p256_rows, 
     launch_hpke_rows_default(ra, s);
   // the rows with a 65-byte encapsulated key (the others' rows it skips; both write his / status of their own rows)
   if (p256_rows) launch_hpke_rows_p256(ra, s);
+  return hipGetLastError();
+}
+
+hipError_t launch_enc_rows(const EncRowsArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(enc_rows_kernel, dim3((uint32_t)((a.n + ENC_ROWS_WG - 1) / ENC_ROWS_WG)), dim3(ENC_ROWS_WG), 0, s, a);
   return hipGetLastError();
 }
 

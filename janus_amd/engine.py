@@ -553,6 +553,99 @@ class HelperEngine:
                                                          d_out_prep_msgs, d_out_verdicts)
             check(st, self._h, "jx_helper_prep_aggregate_device")
 
+    def _sealed_inputs(self, n: int, times, task_id: bytes, keypairs, key_index, encs, payloads, payload_offsets):
+        """The sealed-share arguments of the fused calls as host arrays (the conventions of
+        helper_initialized_encrypted_batch): times, key-index pairs, the encapsulated keys packed with their
+        offsets (None: n x 32), the payloads packed with theirs, the task id and the keypair handles."""
+        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
+        ki = np.ascontiguousarray(np.asarray(key_index, dtype=np.uint8).reshape(n, 2)) if n else np.zeros((1, 2), np.uint8)
+        if isinstance(encs, (list, tuple)):
+            if len(encs) != n:
+                raise ValueError("one encapsulated key per report")
+            en = np.frombuffer(b"".join(bytes(x) for x in encs) or b"\0", np.uint8).copy()
+            eoff = np.zeros(n + 1, np.uint64)
+            if n:
+                eoff[1:] = np.cumsum([len(x) for x in encs])
+        else:
+            en = _u8(encs, n, 32, "encs").reshape(-1) if n else np.zeros(32, np.uint8)
+            eoff = None
+        if isinstance(payloads, (list, tuple)):
+            if len(payloads) != n or payload_offsets is not None:
+                raise ValueError("one payload per report (a list carries its own offsets)")
+            off = np.zeros(n + 1, np.uint64)
+            if n:
+                off[1:] = np.cumsum([len(p) for p in payloads])
+            ct = np.frombuffer(b"".join(payloads) or b"\0", np.uint8).copy()
+        else:
+            if payload_offsets is None:
+                raise ValueError("packed payloads need payload_offsets (n + 1)")
+            off = np.ascontiguousarray(np.asarray(payload_offsets, dtype=np.uint64).reshape(n + 1))
+            ct = np.ascontiguousarray(np.frombuffer(payloads, np.uint8) if isinstance(payloads, (bytes, bytearray))
+                                      else payloads, dtype=np.uint8).reshape(-1)
+            if ct.size == 0:
+                ct = np.zeros(1, np.uint8)
+        if len(task_id) != 32:
+            raise ValueError("task id is 32 bytes")
+        task = np.frombuffer(task_id, np.uint8).copy()
+        hs = (ctypes.c_void_p * max(1, len(keypairs)))(*[k.handle for k in keypairs])
+        return tm, ki, en, eoff, ct, off, task, hs
+
+    def prep_and_aggregate_encrypted(self, nonces, times, public_shares, task_id: bytes, keypairs, key_index, encs,
+                                     payloads, leader_prep_shares, payload_offsets=None, segment: int = 0,
+                                     require_taskprov: bool = False) -> "EncryptedResult":
+        """prep_and_aggregate from report shares still under HPKE, host buffers
+        (jx_helper_prep_aggregate_encrypted): every launch of the fused call opens its own reports, as
+        helper_initialized_encrypted_batch does for a job, and exactly the finished reports are accumulated into
+        `segment`. encs: an (n, 32) array or a list of keys of any lengths; payloads: a list of ciphertexts, or a
+        packed array with payload_offsets (n + 1, which may start above 0). Returns verdicts (OPEN_FAILURE where
+        the share did not open / decode), prep messages and the open status per report."""
+        n = int(np.asarray(nonces).reshape(-1, 16).shape[0])
+        nn = _u8(nonces, n, 16, "nonces")
+        ps = _u8(public_shares, n, self.public_share_len, "public_shares")
+        lps = _u8(leader_prep_shares, n, self.prep_share_len, "leader_prep_shares")
+        tm, ki, en, eoff, ct, off, task, hs = self._sealed_inputs(n, times, task_id, keypairs, key_index, encs, payloads,
+                                                                  payload_offsets)
+        verdicts = np.zeros(max(n, 1), np.uint8)
+        status = np.zeros(max(n, 1), np.uint8)
+        msgs = np.zeros((max(n, 1), max(self.prep_msg_len, 1)), np.uint8)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        st = self._L.jx_helper_prep_aggregate_encrypted(
+            self._h, n, _ptr(nn), tm.ctypes.data_as(u64p), _ptr(ps) if self.public_share_len else None, _ptr(task), hs,
+            len(keypairs), _ptr(ki), _ptr(en), eoff.ctypes.data_as(u64p) if eoff is not None else None, _ptr(ct),
+            off.ctypes.data_as(u64p), ENC_REQUIRE_TASKPROV if require_taskprov else 0, _ptr(lps), segment,
+            _ptr(msgs) if self.prep_msg_len else None, _ptr(verdicts), _ptr(status))
+        check(st, self._h, "jx_helper_prep_aggregate_encrypted")
+        return EncryptedResult(verdicts[:n], msgs[:n, : self.prep_msg_len], status[:n], 0)
+
+    def prep_and_aggregate_encrypted_device(self, d_nonces: int, times, d_public_shares: int | None, task_id: bytes,
+                                            keypairs, key_index, d_encs: int, d_payloads: int, payload_offsets,
+                                            d_leader_prep_shares: int, n: int, enc_offsets=None, segment: int = 0,
+                                            require_taskprov: bool = False, d_out_prep_msgs: int | None = None,
+                                            d_out_verdicts: int | None = None, d_out_open_status: int | None = None,
+                                            d_segments: int | None = None, segment_ids=None, stream=None):
+        """Same, with the bulk data resident in HBM (jx_helper_prep_aggregate_encrypted_device): device pointers
+        for the report ids, public shares, encapsulated keys (packed; enc_offsets None: n x 32 bytes), payloads
+        (packed, report i's at payload_offsets[i]) and leader prep shares and for the three optional outputs; host
+        arrays for times, key_index and the two offset arrays. The ciphertexts and keys are read in place.
+        Segments and stream ordering as prep_and_aggregate_device."""
+        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
+        ki = np.ascontiguousarray(np.asarray(key_index, dtype=np.uint8).reshape(n, 2)) if n else np.zeros((1, 2), np.uint8)
+        off = np.ascontiguousarray(np.asarray(payload_offsets, dtype=np.uint64).reshape(n + 1))
+        eoff = None if enc_offsets is None else np.ascontiguousarray(np.asarray(enc_offsets, dtype=np.uint64).reshape(n + 1))
+        if len(task_id) != 32:
+            raise ValueError("task id is 32 bytes")
+        task = np.frombuffer(task_id, np.uint8).copy()
+        hs = (ctypes.c_void_p * max(1, len(keypairs)))(*[k.handle for k in keypairs])
+        ids, ptr = _seg_table([segment] if segment_ids is None else segment_ids)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        with self._ordered(stream):
+            st = self._L.jx_helper_prep_aggregate_encrypted_device(
+                self._h, n, d_nonces, tm.ctypes.data_as(u64p), d_public_shares, _ptr(task), hs, len(keypairs), _ptr(ki),
+                d_encs, eoff.ctypes.data_as(u64p) if eoff is not None else None, d_payloads, off.ctypes.data_as(u64p),
+                ENC_REQUIRE_TASKPROV if require_taskprov else 0, d_leader_prep_shares, d_segments, ptr, ids.size,
+                d_out_prep_msgs, d_out_verdicts, d_out_open_status)
+            check(st, self._h, "jx_helper_prep_aggregate_encrypted_device")
+
     # ------------------------------------------------------------------ aggregation state
     def aggregate_share(self, segment: int = 0) -> tuple[bytes, int, bytes]:
         """(encoded aggregate share, report count, checksum) of one batch aggregation."""
