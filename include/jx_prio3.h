@@ -398,6 +398,37 @@ int32_t jx_leader_upload_open_device(jx_engine* e, uint64_t n, const void* d_rep
                                      void* d_out_rows, uint64_t lis_stride, void* d_out_extensions, void* d_out_ext_len,
                                      void* d_out_status);
 
+/* ---- The client: Prio3.shard (VDAF-08 §7.2.1) for n measurements, the first of the VDAF's four algorithms and the
+ * source of the rows every prepare call above takes. Per report: the helper's measurement and proof shares are
+ * expanded from its two seeds, the leader's measurement share is enc(measurement) - the helper's, the joint
+ * randomness is derived from both shares' parts, FlpGeneric.prove runs on the whole measurement (the gadget
+ * polynomial through number-theoretic transforms), and the leader's proof share is the proof minus the helper's.
+ * Every XOF stream is rejection-sampled exactly.
+ *   measurements  uint64: one per report for Count ({0, 1}), Sum (< 2^bits) and Histogram (a bucket index <
+ *                 length); `length` per report for SumVec (each < 2^bits)
+ *   nonces        n x 16
+ *   rands         n x jx_client_rand_bytes: k_helper_meas || k_helper_proofs || k_prove || [blind_leader ||
+ *                 blind_helper], 16 bytes each, the blinds only for instances with joint randomness. The engine
+ *                 never generates randomness: the caller owns the CSPRNG. The engine's verify key is not used.
+ * Outputs, fixed-stride rows in the encodings the prepare calls take: public shares n x PS, leader input shares
+ * (measurement share || proof share || [blind]; host call: rows of LIS bytes; device call: rows of lis_stride
+ * bytes, 0 = LIS, else >= LIS and a multiple of 16, zero padded, 16-byte aligned), helper input shares n x HIS.
+ * out_status (nullable): 0, or JX_SHARD_INVALID_MEASUREMENT for a report whose measurement is out of range, as
+ * prio's encode_measurement refuses it; its three rows are zeros.
+ * The device call is asynchronous on the engine stream under the ordering contract of the Conventions, takes its
+ * scratch from the device's arena, is cut into launches when n exceeds one launch's scratch, and is not coalesced.
+ * n == 0 is JX_OK. Algo ids 0-3 only: the multiproof (4) and FixedPoint (5) instances return JX_E_UNSUPPORTED, and so
+ * does an instance whose transform size P = next_pow2(1 + gadget calls) exceeds JX_SHARD_MAX_P. */
+#define JX_SHARD_INVALID_MEASUREMENT 1
+#define JX_SHARD_MAX_P 1024u
+int32_t jx_client_shard_batch(jx_engine* e, uint64_t n, const uint64_t* measurements, const uint8_t* nonces,
+                              const uint8_t* rands, uint8_t* out_public_shares, uint8_t* out_leader_input_shares,
+                              uint8_t* out_helper_input_shares, uint8_t* out_status);
+int32_t jx_client_shard_device(jx_engine* e, uint64_t n, const void* d_measurements, const void* d_nonces,
+                               const void* d_rands, void* d_out_public_shares, void* d_out_leader_input_shares,
+                               uint64_t lis_stride, void* d_out_helper_input_shares, void* d_out_status);
+int32_t jx_client_rand_bytes(const jx_engine* e, uint32_t* bytes);
+
 /* Accumulate the output shares of the resident batch `batch_id` (helper, or leader after finish) into
  * the engine's running batch aggregations (the engine as one shard, §8e): report i is added iff
  * verdict == FINISHED and accept_mask[i] != 0 (accept_mask nullable = all), into aggregation
@@ -512,7 +543,9 @@ int32_t jx_engine_timing_read(jx_engine* e, float ms[4], uint64_t launches[4]);
  *             (0: off); needs coalescing on (JX_E_STATE otherwise). Applies to the whole device coalescer;
  *   option 8: jx_accumulate of job-sized batches: 1 deferred and added together (default), 0 one launch per call
  *             (queued deferrals run first);
- *   option 9: run the deferred accumulations now. */
+ *   option 9: run the deferred accumulations now;
+ *   option 10: reports per launch of jx_client_shard_batch / _device: 0 automatic (what 4 GiB of scratch hold, at
+ *             least 64), else that many. */
 int32_t jx_engine_debug(jx_engine* e, int32_t option, int64_t value);
 
 const char* jx_status_str(int32_t status);

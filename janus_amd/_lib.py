@@ -26,6 +26,7 @@ EXPORTED_SYMBOLS = (
     "jx_engine_memory", "jx_engine_coalesce", "jx_leader_prep_init_device_ex", "jx_helper_prep_encrypted_batch",
     "jx_helper_prep_encrypted_batch2", "jx_leader_upload_open_batch", "jx_leader_upload_open_device",
     "jx_helper_prep_aggregate_encrypted", "jx_helper_prep_aggregate_encrypted_device",
+    "jx_client_shard_batch", "jx_client_shard_device", "jx_client_rand_bytes",
 )
 
 _lib = None
@@ -113,6 +114,9 @@ def load():
         "jx_shard_record_bytes": (i32, [vp, P(u32)]),
         "jx_shard_record_export_device": (i32, [vp, u32, vp]),
         "jx_shard_record_combine_device": (i32, [vp, vp, u32, vp]),
+        "jx_client_shard_batch": (i32, [vp, u64, u8p, u8p, u8p, u8p, u8p, u8p, u8p]),
+        "jx_client_shard_device": (i32, [vp, u64, vp, vp, vp, vp, vp, u64, vp, vp]),
+        "jx_client_rand_bytes": (i32, [vp, P(u32)]),
         "jx_engine_sync": (i32, [vp]),
         "jx_engine_stream": (i32, [vp, P(vp)]),
         "jx_engine_wait_stream": (i32, [vp, vp]),

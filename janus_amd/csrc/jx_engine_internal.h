@@ -287,6 +287,8 @@ struct jx_engine {
   hipEvent_t ev_flush = nullptr;
   uint64_t acc_flushes = 0, acc_deferred = 0;
   uint32_t* d_err = nullptr;  // combine kernels: non-canonical input seen (reported by jx_engine_sync)
+  uint4* d_shard_tab = nullptr;  // jx_client_shard_*: the prover's transform table (jx_ntt.h), made by the first call
+  uint64_t shard_chunk = 0;      // reports per launch of jx_client_shard_* (debug option 10; 0: by the scratch budget)
   // timing
   bool timing = false;
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;

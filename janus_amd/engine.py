@@ -60,6 +60,8 @@ VERDICT_LABELS = {
 # open status of an encrypted input share (include/jx_prio3.h JX_OPEN_*; aggregator.rs:1781-1910):
 # (janus_step_failures label, PrepareError value)
 OPEN_OK = 0
+SHARD_INVALID_MEASUREMENT = 1  # jx_client_shard_*: the measurement is out of range (JX_SHARD_INVALID_MEASUREMENT)
+SHARD_MAX_P = 1024             # JX_SHARD_MAX_P: the largest transform size (gadget-call points) the prover holds
 KEY_NONE, KEY_MALFORMED = 0xFF, 0xFE
 ENC_REQUIRE_TASKPROV = 1
 OPEN_STATUS = {
@@ -131,6 +133,14 @@ class UploadOpen:
     extensions: list           # per report: its extension list's bytes, without the u16 prefix (b"" when rejected)
     rows: object               # torch uint8[n, lis_stride] on the device: the leader input shares, zeros when rejected
     lis_stride: int
+
+
+@dataclass
+class ShardResult:
+    public_shares: np.ndarray        # uint8[n, PS]
+    leader_input_shares: np.ndarray  # uint8[n, LIS]: measurement share || proof share || [blind]
+    helper_input_shares: np.ndarray  # uint8[n, HIS]: k_meas || k_proofs || [blind]
+    status: np.ndarray               # uint8[n]: 0, or SHARD_INVALID_MEASUREMENT (the report's rows are zeros)
 
 
 class HelperEngine:
@@ -426,6 +436,58 @@ class HelperEngine:
         s = None if segments is None else np.ascontiguousarray(segments, dtype=np.uint32)
         bid = self.batch_id() if batch_id is None else batch_id
         check(self._L.jx_accumulate(self._h, bid, n, _ptr(m), _ptr(s)), self._h, "jx_accumulate")
+
+    # ------------------------------------------------------------------ the client (Prio3.shard)
+    def client_rand_bytes(self) -> int:
+        """Bytes of client randomness per report: k_helper_meas || k_helper_proofs || k_prove || [blind_leader ||
+        blind_helper], 16 bytes each."""
+        b = ctypes.c_uint32()
+        check(self._L.jx_client_rand_bytes(self._h, ctypes.byref(b)), self._h, "jx_client_rand_bytes")
+        return b.value
+
+    def _measurements(self, measurements, n: int) -> np.ndarray:
+        width = self.vdaf.length if self.vdaf.algo_id in (2, 4, 5) else 1  # the vector instances
+        m = np.ascontiguousarray(np.asarray(measurements, dtype=np.uint64))
+        if m.size != n * width:
+            raise ValueError(f"measurements: expected {n} x {width} uint64")
+        return m.reshape(n, width) if n else np.zeros((1, width), np.uint64)
+
+    def shard_batch(self, measurements, nonces, rands=None) -> ShardResult:
+        """Prio3.shard for n measurements on the GPU (jx_client_shard_batch; Count, Sum, SumVec, Histogram).
+        measurements: n uint64 (SumVec: n x length); nonces: n x 16; rands: n x client_rand_bytes() of client
+        randomness, drawn from os.urandom when None. The rows go into leader_initialized_batch /
+        helper_initialized_batch unchanged. A report whose measurement is out of range gets status
+        SHARD_INVALID_MEASUREMENT and zero rows."""
+        n = len(nonces) // 16 if isinstance(nonces, (bytes, bytearray)) else int(np.asarray(nonces).reshape(-1, 16).shape[0])
+        rb = self.client_rand_bytes()
+        if rands is None:
+            import os
+            rands = os.urandom(n * rb)
+        nn = _u8(nonces, n, 16, "nonces")
+        rd = _u8(rands, n, rb, "rands")
+        m = self._measurements(measurements, n)
+        ps = np.zeros((n, self.public_share_len), np.uint8)
+        lis = np.zeros((n, self.leader_input_share_len), np.uint8)
+        his = np.zeros((n, self.helper_input_share_len), np.uint8)
+        status = np.zeros(n, np.uint8)
+        check(self._L.jx_client_shard_batch(self._h, n, _ptr(m), _ptr(nn), _ptr(rd),
+                                            _ptr(ps) if self.public_share_len and n else None, _ptr(lis), _ptr(his),
+                                            _ptr(status)),
+              self._h, "jx_client_shard_batch")
+        return ShardResult(ps, lis, his, status)
+
+    def shard_device(self, n: int, d_measurements: int, d_nonces: int, d_rands: int, d_out_public_shares: int | None,
+                     d_out_leader_input_shares: int, d_out_helper_input_shares: int, d_out_status: int | None = None,
+                     lis_stride: int = 0, stream=None):
+        """Prio3.shard with everything in HBM (jx_client_shard_device). Asynchronous, ordered against `stream`
+        (module docstring). lis_stride: the row stride of the leader input shares written (0: packed rows; else at
+        least leader_input_share_len and a multiple of 16, zero padded), as leader_init_device reads them; the rows
+        must be 16-byte aligned."""
+        with self._ordered(stream):
+            check(self._L.jx_client_shard_device(self._h, n, d_measurements, d_nonces, d_rands, d_out_public_shares,
+                                                 d_out_leader_input_shares, lis_stride, d_out_helper_input_shares,
+                                                 d_out_status),
+                  self._h, "jx_client_shard_device")
 
     # ------------------------------------------------------------------ device-pointer paths (inputs in HBM)
     def leader_init_device(self, n: int, d_nonces: int, d_public_shares: int | None, d_leader_input_shares: int,

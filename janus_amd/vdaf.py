@@ -191,6 +191,35 @@ class Prio3:
                 PRIO3_FIXEDPOINT_L2: f"Prio3FixedPointBoundedL2VecSum{{bitsize=BitSize{self.bits},length={self.length}}}",
                 }[self.algo_id]
 
+    # -- the client side
+    @property
+    def client_rand_len(self) -> int:
+        """Bytes of client randomness Prio3.shard consumes (RAND_SIZE, VDAF-08 §7.2): the helper's two share
+        seeds, the prove seed and, with joint randomness, one blind per aggregator."""
+        return self.seed_size * (3 + (2 if self.joint_rand_len else 0))
+
+    def unshard(self, agg_shares: list, num_measurements: int):
+        """Prio3.unshard (VDAF-08 §7.2.5) for Count, Sum, SumVec and Histogram: the element-wise sum mod p of
+        the aggregators' encoded aggregate shares, decoded: an int for Count and Sum, a list of `length` ints for
+        SumVec and Histogram. Every share must hold `output_len` canonical field elements."""
+        if self.algo_id not in (PRIO3_COUNT, PRIO3_SUM, PRIO3_SUMVEC, PRIO3_HISTOGRAM):
+            raise ValueError(f"unshard: {self.name()} is not covered (Count, Sum, SumVec, Histogram are)")
+        if num_measurements < 0 or not agg_shares:
+            raise ValueError("unshard: needs at least one aggregate share and num_measurements >= 0")
+        fb = self.field_bytes
+        p = 2**64 - 2**32 + 1 if fb == 8 else 2**128 - 28 * 2**64 + 1
+        total = [0] * self.output_len
+        for share in agg_shares:
+            share = bytes(share)
+            if len(share) != self.output_len * fb:
+                raise ValueError(f"unshard: an aggregate share of {self.name()} is {self.output_len * fb} bytes")
+            for i in range(self.output_len):
+                v = int.from_bytes(share[fb * i:fb * i + fb], "little")
+                if v >= p:
+                    raise ValueError("unshard: non-canonical field element in an aggregate share")
+                total[i] = (total[i] + v) % p
+        return total[0] if self.algo_id in (PRIO3_COUNT, PRIO3_SUM) else total
+
     # -- FixedPointBoundedL2VecSum measurement / result codecs (host side; collection is out of scope)
     def encode_fixedpoint(self, values) -> list[int]:
         """f64 entries in [-1, 1) -> FixedI{n}<U{n-1}> bit patterns (round to nearest, like fixed!)."""
