@@ -350,19 +350,17 @@ static int32_t launch_lane(Coalescer* C, Lane& L, std::string& err) {
     return st == hipErrorOutOfMemory ? JX_E_NOMEM : JX_E_HIP;
   };
   if (hipSetDevice(C->device) != hipSuccess) return JX_E_HIP;
-  const bool inpl = leader && (c.algo == ALGO_SUM || c.algo == ALGO_SUMVEC || c.algo == ALGO_FIXEDPOINT_L2);
+  const bool inpl = leader && leader_inplace(c);
   uint32_t fl = SG_IN | SG_PREP | SG_RES | SG_VK | SG_JOBS;
   fl |= leader ? SG_LEAD : SG_HIN;
   if (!inpl) fl |= SG_MEAS;
-  if (L.has_enc) {
-    fl |= SG_ENC;
-    q->enc_ct_bytes = L.ct_cap;  // the lane's budget: launches of varying size reuse the lane's slab
-  }
+  if (L.has_enc) fl |= SG_ENC;
   // staging for a power of two of reports (>= 1,024): launches of varying size reuse the lane's slab
   uint64_t cap = 1024;
   while (cap < m) cap <<= 1;
   Stage st;
-  int32_t rc = stage_acquire(q, cap, fl, st);
+  // the ciphertext regions take the lane's budget, for the same reason
+  int32_t rc = stage_acquire(q, cap, fl, st, true, L.has_enc ? L.ct_cap : 0);
   if (rc) {
     err = thread_error();
     return rc;
@@ -384,7 +382,7 @@ static int32_t launch_lane(Coalescer* C, Lane& L, std::string& err) {
   // Helper: the leader prep shares are most of the bytes (SumVec 8x1000/88: 2,864 of 2,960 per report) and only
   // the FLP stage reads them whole; K1 reads each row's last 16 bytes (the leader's joint-rand part). Those go
   // first on the lane stream, the rest of the rows on the lane's upload stream beside K1, and K3 waits for it.
-  const bool split_lps = !leader && c.lps_bytes > 16 && c.algo != ALGO_COUNT && c.algo != ALGO_SUMVEC_F64_MULTIPROOF;
+  const bool split_lps = !leader && c.lps_bytes > 16 && !one_kernel_chain(c);
   const size_t P = c.lps_bytes;
   if (!leader && !split_lps) flat(ua, q->d_lps, L.o_lps, m * P);
   if (split_lps) add(ua, q->d_lps + P - 16, P, hin + L.o_lps + P - 16, P, 16, m);

@@ -1,6 +1,7 @@
-// jx_engine_internal.h — engine internals shared by jx_engine.cpp (the C ABI and launch sequencing),
-// jx_arena.cpp (the per-device memory arena) and jx_coalesce.cpp (the per-device job coalescer).
-// Not part of the ABI: include/jx_prio3.h is.
+// jx_engine_internal.h — engine internals shared by the engine's host sources: jx_engine.cpp (staging, resident
+// batches, the K1 -> K3 sequencing, the ABI's lifetime and plumbing calls), the call families jx_engine_cfg.cpp,
+// _prep.cpp, _acc.cpp, _fused.cpp, _upload.cpp and _shard.cpp, jx_arena.cpp (the per-device memory arena) and
+// jx_coalesce.cpp (the per-device job coalescer). Not part of the ABI: include/jx_prio3.h is.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -16,6 +17,7 @@
 #include <vector>
 
 #include "../../include/jx_prio3.h"
+#include "jx_carve.h"
 #include "jx_enc_rows.h"
 #include "jx_kernels.h"
 
@@ -112,6 +114,50 @@ struct AccSrc {
 };
 
 enum { ST_XOF = 0, ST_FLP = 1, ST_ACC = 2, ST_SLOW = 3, NST = 4 };
+
+// ---------------------------------------------------------------------------- what the algorithms differ in
+// the output shares alias the measurement-share staging (Histogram: output = measurement share)
+inline bool outs_alias_meas(const Cfg& c) { return c.out_is_meas && c.algo != jx::ALGO_COUNT; }
+// The leader's FLP kernels read its explicit measurement share in place (Bufs::meas_rs) instead of a
+// staged copy: every TurboSHAKE instance whose output is not the measurement share itself.
+inline bool leader_inplace(const Cfg& c) {
+  return c.algo == jx::ALGO_SUM || c.algo == jx::ALGO_SUMVEC || c.algo == jx::ALGO_FIXEDPOINT_L2;
+}
+// Count and the multiproof instance run as one kernel chain: their K1 never splits in two (prep_core), their fused
+// calls take no pipelines (jx_fused_plan.h), and a coalesced launch uploads their leader prep shares whole.
+inline bool one_kernel_chain(const Cfg& c) {
+  return c.algo == jx::ALGO_COUNT || c.algo == jx::ALGO_SUMVEC_F64_MULTIPROOF;
+}
+
+// A pinned host buffer that queued uploads read after the call has returned: rewritten only once the stream has
+// passed the event of its last reader, so no call waits for its own work.
+struct PinnedBuf {
+  void* p = nullptr;
+  size_t cap = 0;
+  hipEvent_t ev = nullptr;
+  // Wait for the last reader (first use: make the event), grow to `bytes` and give the buffer in *out.
+  hipError_t reserve(size_t bytes, void** out) {
+    hipError_t st = ev ? hipEventSynchronize(ev) : hipEventCreateWithFlags(&ev, hipEventDisableTiming);
+    if (st != hipSuccess) return st;
+    if (cap < bytes) {
+      if (p) (void)hipHostFree(p);
+      p = nullptr;
+      cap = 0;  // a failed allocation leaves an empty buffer, not a capacity without one
+      if ((st = hipHostMalloc(&p, bytes, hipHostMallocDefault)) != hipSuccess) return st;
+      cap = bytes;
+    }
+    *out = p;
+    return hipSuccess;
+  }
+  hipError_t mark(hipStream_t s) { return hipEventRecord(ev, s); }  // the last reader is queued on s
+  void destroy() {
+    if (p) (void)hipHostFree(p);
+    if (ev) (void)hipEventDestroy(ev);
+    p = nullptr;
+    cap = 0;
+    ev = nullptr;
+  }
+};
 
 // Per-call staging regions (stage_acquire flags)
 enum : uint32_t {
@@ -243,18 +289,15 @@ struct jx_engine {
   uint8_t *d_lis = nullptr, *d_lps_out = nullptr, *d_in_msgs = nullptr;
   uint8_t* d_vkeys = nullptr;
   jx::JobSlice* d_jobs = nullptr;
-  // SG_ENC: encrypted helper inputs (enc_ct_bytes: the ciphertext region's size, set before stage_acquire)
+  // SG_ENC: encrypted helper inputs (the ciphertext regions' size is stage_acquire's ct_bytes)
   jx::EncRow* d_encrows = nullptr;
   uint8_t *d_ct = nullptr, *d_pt = nullptr, *d_status = nullptr;
-  uint64_t enc_ct_bytes = 0;
   // SG_ENCC: the compact arrays of one launch
   uint64_t *d_ec_times = nullptr, *d_ec_eoff = nullptr, *d_ec_poff = nullptr;
   uint8_t* d_ec_kidx = nullptr;
-  // pinned host copy of a sealed fused device call's compact arrays, so that the call returns once queued: reused
-  // after ev_henc (the engine stream behind the last call that read it) has completed
-  uint8_t* h_enc = nullptr;
-  uint64_t h_enc_cap = 0;
-  hipEvent_t ev_henc = nullptr;
+  // pinned host copy of a sealed fused device call's compact arrays, so that the call returns once queued: its
+  // last reader is the engine stream behind the last call that read it
+  jxi::PinnedBuf h_enc;
   uint32_t acc_chunks = 0;  // report chunks of the accumulate kernel (0: acc_nchunks picks)
   std::map<uint32_t, jxi::Segment> segs;  // running batch aggregations (the engine as one shard)
   std::vector<jxi::Slab> seg_slabs;       // their states, kSegsPerSlab per arena slab
@@ -264,16 +307,12 @@ struct jx_engine {
   uint64_t batch_gen = 0;
   std::atomic<uint64_t> last_batch{0};  // a coalesced prepare sets it without the engine mutex
   // pinned host copies of the segments' pointer table (upload_targets), double-buffered: buffer k is rewritten
-  // only after the upload that last read it has completed (ev_ptrs[k]), so no call waits for its own work
-  void** h_ptrs[2] = {nullptr, nullptr};
-  uint64_t h_ptrs_cap[2] = {0, 0};
-  hipEvent_t ev_ptrs[2] = {nullptr, nullptr};
+  // only after the upload that last read it has completed, so no call waits for its own work
+  jxi::PinnedBuf h_ptrs[2];
   int ptrs_k = 0;
   // pinned host staging for the small host arrays of jx_accumulate (mask, dense segment index), so the
-  // call returns once queued: reused after ev_hacc (the last upload that read it) has completed
-  uint8_t* h_acc = nullptr;
-  uint64_t h_acc_cap = 0;
-  hipEvent_t ev_hacc = nullptr;
+  // call returns once queued
+  jxi::PinnedBuf h_acc;
   std::vector<uint32_t> h_dense;
   // deferred small accumulations: jx_accumulate of an unmasked batch of <= ACC_SMALL reports into one
   // aggregation parks the batch here; a flush runs one accumulate_multi launch per aggregation (a full queue,
@@ -318,6 +357,11 @@ namespace jxi {
 int32_t fail(jx_engine* e, int32_t code, const std::string& msg);
 std::string& thread_error();
 
+// every entry point: the engine mutex for the call, and a fresh per-thread error message
+#define LOCK(e)                                   \
+  std::lock_guard<jxi::FairMutex> _lk((e)->mu);   \
+  ::jxi::thread_error().clear()
+
 #define HIPCHK(e, call)                                                                                   \
   do {                                                                                                    \
     hipError_t _st = (call);                                                                              \
@@ -337,8 +381,29 @@ struct Stage {
   ~Stage() { release(); }
   void release();
 };
-int32_t stage_acquire(jx_engine* e, uint64_t n, uint32_t flags, Stage& st, bool may_wait = true);
-size_t stage_bytes(const jx_engine* e, uint64_t cap, uint32_t flags);
+// ct_bytes: the size of each of SG_ENC's two ciphertext regions (read only under SG_ENC)
+int32_t stage_acquire(jx_engine* e, uint64_t n, uint32_t flags, Stage& st, bool may_wait = true, uint64_t ct_bytes = 0);
+
+// Per-call device scratch from the arena, handed back stream-ordered on the engine stream when it goes out of
+// scope: no hipMalloc / hipFree / stream synchronize on a call path (hipFree waits for the device, and every
+// engine's launches on it).
+struct Scratch {
+  jx_engine* e = nullptr;
+  Slab s;
+  Scratch() = default;
+  Scratch(const Scratch&) = delete;
+  Scratch& operator=(const Scratch&) = delete;
+  ~Scratch() {
+    if (s.p) arena_put(e->arena, s, e->stream);
+  }
+  uint8_t* p() const { return (uint8_t*)s.p; }
+};
+// may_wait: the caller holds no other staging (arena_get's rule)
+int32_t scratch_get(jx_engine* e, size_t bytes, Scratch& out, bool may_wait = false);
+
+// ---- jx_engine_cfg.cpp
+int32_t make_cfg(const jx_prio3_params* p, const uint8_t* vk, uint32_t vk_len, Cfg& c, std::string& why);
+std::vector<uint4> make_consts(const Cfg& c);
 
 int32_t prep_core(jx_engine* e, uint64_t n, const uint8_t* nonces, const uint8_t* ps, const uint8_t* his,
                   const uint8_t* lps, uint8_t* verdicts, uint8_t* msgs, uint4* outs, const uint8_t* lis = nullptr,
@@ -348,11 +413,46 @@ int32_t prep_core(jx_engine* e, uint64_t n, const uint8_t* nonces, const uint8_t
 uint4* staging_outs(jx_engine* e);
 int32_t batch_new(jx_engine* e, uint64_t n, bool leader, uint64_t* id, Batch** out);
 void batch_free(jx_engine* e, std::map<uint64_t, Batch>::iterator it);
+int32_t find_batch(jx_engine* e, uint64_t id, uint64_t n, const char* what, Batch** out);
+int32_t get_segment(jx_engine* e, uint32_t id, Segment** out);
+// kernel timing (jx_engine_timing): the events around one launch of `stage`
+hipError_t stage_begin(jx_engine* e, hipEvent_t* ev);
+hipError_t stage_end(jx_engine* e, int stage, hipEvent_t ev0);
 int32_t drain_timing(jx_engine* e);
-size_t align256(size_t v);
+uint32_t acc_nchunks(const jx_engine* e);  // report chunks of accumulate_kernel
 uint32_t vk_row_bytes(const Cfg& c);
 void vk_row(const Cfg& c, uint8_t* dst);  // this engine's verify key as one SG_VK row
 jx_engine* new_child(jx_engine* parent);  // a pipeline / coalescer lane: own stream, shared consts
+
+// ---- jx_engine_acc.cpp
+// Run the deferred accumulations (jx_accumulate) before anything that reads, exports, resets or orders work
+// against the aggregations.
+int32_t flush_acc(jx_engine* e);
+#define FLUSH_ACC(e)                   \
+  do {                                 \
+    int32_t _fr = ::jxi::flush_acc(e); \
+    if (_fr) return _fr;               \
+  } while (0)
+// The device pointer table of a call's targets, [3][S]: aggs, counts, checksums. It owns the per-call scratch it
+// lies in, which goes back to the arena (stream-ordered) with it.
+struct PtrTable {
+  Scratch mem;
+  void** d() const { return (void**)mem.p(); }
+};
+int32_t upload_targets(jx_engine* e, const std::vector<Segment>& targets, PtrTable& tbl);
+// The running aggregations named by a caller's segment-id table (a repeated id is refused).
+int32_t segment_targets(jx_engine* e, const uint32_t* ids, uint64_t nids, std::vector<Segment>& out);
+// Accumulate src into targets[d_dense[r]] (d_dense nullable: all into targets[0]). One target takes the
+// coalesced select/accumulate path; several go through their pointer table (tbl, or null: uploaded here).
+int32_t accumulate_into(jx_engine* e, const AccSrc& src, const uint8_t* d_mask, const uint32_t* d_dense,
+                        const std::vector<Segment>& targets, const PtrTable* tbl = nullptr);
+
+// ---- jx_engine_prep.cpp
+// What every call that takes sealed helper input shares checks before anything is queued, and the request as an
+// EncJob. encs and payloads are only compared with null: the device forms pass device pointers.
+int32_t enc_job_check(jx_engine* e, uint64_t n, const uint64_t* times, const uint8_t* task_id, jx_hpke* const* keypairs,
+                      uint32_t nkeypairs, const uint8_t* key_index, const uint8_t* encs, const uint64_t* enc_offsets,
+                      const uint8_t* payloads, const uint64_t* payload_offsets, uint32_t flags, EncJob& job);
 
 // ---------------------------------------------------------------------------- coalescer (jx_coalesce.cpp)
 Coalescer* coalescer_for(jx_engine* e);

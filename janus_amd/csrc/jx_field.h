@@ -470,7 +470,7 @@ JX_HD f128 wacc_reduce(wacc26 a) {
   if (oi < 5) o[oi++] = buf_lo;
   if (oi < 5) o[oi++] = buf_hi;
   // Straight-line fold (value < 2^272, so o4 < 2^16: at most 2^16 products < 2^256, which make_cfg in
-  // jx_engine.cpp enforces by refusing Field128 ParallelSum instances with more gadget calls). Mod p,
+  // jx_engine_cfg.cpp enforces by refusing Field128 ParallelSum instances with more gadget calls). Mod p,
   // 2^128 = 28 2^64 - 1, 2^192 = 783 2^64 - 28, 2^256 = 21896 2^64 - 783, hence
   //   V = (o0 - S) + 2^64 H,  S = o2 + 28 o3 + 783 o4 (< 2^70),  H = o1 + 28 o2 + 783 o3 + 21896 o4 (< 2^74);
   // T = H 2^64 + o0 - S is >= 0 (H 2^64 >= S whenever S > 0) and < 2^139; folding T's bits >= 2^128 (t2 <

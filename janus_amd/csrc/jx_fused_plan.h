@@ -1,5 +1,5 @@
 // jx_fused_plan.h — how a fused prepare + aggregate call of n reports is cut into launches and how many pipelines
-// run them (jx_engine.cpp run_fused obeys; jx_engine_debug options 4 and 5 set npipes and default_chunk).
+// run them (jx_engine_fused.cpp run_fused obeys; jx_engine_debug options 4 and 5 set npipes and default_chunk).
 //
 // Host only and without HIP, so tests/csrc/hosttest_fused_plan.cpp pins the values on the CPU: a slip here costs
 // speed (or, at n == 0, a division by zero), never results, so no GPU parity test would see it.

@@ -1,6 +1,6 @@
 // jx_kernels.h — kernel argument structs and launchers shared by the kernel units (jx_kernels.hip, jx_flp.hip,
-// jx_accumulate.hip, jx_mp64.hip) and jx_engine.cpp, and the device helpers that address the interleaved staging.
-// See DESIGN.md for the HBM layout.
+// jx_accumulate.hip, jx_mp64.hip) and the engine's host sources (jx_engine*.cpp), and the device helpers that
+// address the interleaved staging. See DESIGN.md for the HBM layout.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,5 +1,5 @@
 // jx_upload.h — the leader's upload path on the device (jx_leader_upload_open_*, include/jx_prio3.h): what
-// jx_engine.cpp hands to the kernels of jx_hpke_long.hip. Plain structs, no device code.
+// jx_engine_upload.cpp hands to the kernels of jx_hpke_long.hip. Plain structs, no device code.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-"""GPU: the fused device path with concurrent pipelines (jx_engine.cpp `run_fused`, jx_fused_plan.h, debug option 4):
+"""GPU: the fused device path with concurrent pipelines (jx_engine_fused.cpp `run_fused`, jx_fused_plan.h, debug option 4):
 the launches of one jx_helper_prep_aggregate_device call alternate over P child engines (own stream and
 staging) and only their accumulations are ordered. Verdicts, prep messages, aggregate, count and checksum
 must equal the oracle's for P = 1..4, with a ragged last launch, with the inputs produced on torch's stream
