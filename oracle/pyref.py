@@ -524,9 +524,15 @@ class Prio3:
     def shard(self, measurement, nonce, rand):
         """rand = k_helper_meas || k_helper_proofs || k_prove || [blind_L || blind_H], SEED_SIZE each
         (same layout as the C oracle)."""
+        return self.shard_encoded(self.valid.encode(measurement), nonce, rand)
+
+    def shard_encoded(self, meas_elems, nonce, rand):
+        """shard of an already encoded measurement: MEAS_LEN field elements, which need not be a
+        valid encoding (a cheating client's consistent proof of an invalid measurement)."""
         p, S, V, NP = self.F.p, self.S, self.valid, self.PROOFS
         k_hm, k_hp, k_prove = rand[0:S], rand[S:2 * S], rand[2 * S:3 * S]
-        meas = V.encode(measurement)
+        meas = [int(x) % p for x in meas_elems]
+        assert len(meas) == V.MEAS_LEN
         hmeas = self.helper_meas_share(1, k_hm)
         lmeas = [(a - b) % p for a, b in zip(meas, hmeas)]
         jr, public = [], b""
