@@ -1,5 +1,5 @@
 /*
- * jx_hpke.h — C ABI of batched HPKE open on the MI355X.
+ * jx_hpke.h — C ABI of batched HPKE open, and seal, on the MI355X.
  *
  * Replaces the per-report HPKE open of the helper's aggregate-init loop,
  *   /root/reference/aggregator/src/aggregator.rs:1772-1832
@@ -82,6 +82,14 @@ int32_t jx_hpke_create_suite(uint32_t kem_id, uint32_t kdf_id, uint32_t aead_id,
 int32_t jx_hpke_create_key(uint32_t kem_id, uint32_t kdf_id, uint32_t aead_id, const uint8_t* sk, uint32_t sk_len,
                            const uint8_t* pk, uint32_t pk_len, const uint8_t* info, uint32_t info_len, int32_t device,
                            jx_hpke** out);
+/* A SENDER context: the recipient's public key alone, which is all a client has. It seals (below) and cannot open: its
+ * private-key words in the key registry are zero, and every call that opens refuses it before anything is queued
+ * (jx_hpke_open_*: JX_HPKE_E_INVALID; jx_helper_prep_encrypted_batch[2], jx_helper_prep_aggregate_encrypted[_device]
+ * and jx_leader_upload_open_* of jx_prio3.h: JX_E_INVALID). It takes a key-registry row like any other context. KEM
+ * 0x0020 (X25519, pk_len 32) with KDF 1..3 and AEAD 1..3; sealing under the P-256 KEM 0x0010 is out of scope and
+ * returns JX_HPKE_E_UNSUPPORTED, with the reason in jx_hpke_last_error. */
+int32_t jx_hpke_create_sender(uint32_t kem_id, uint32_t kdf_id, uint32_t aead_id, const uint8_t* pk, uint32_t pk_len,
+                              const uint8_t* info, uint32_t info_len, int32_t device, jx_hpke** out);
 /* The suite a context was created with (any of the three may be NULL). */
 int32_t jx_hpke_suite(const jx_hpke* h, uint32_t* kem_id, uint32_t* kdf_id, uint32_t* aead_id);
 /* The length of an encapsulated key under the context's KEM: 32 (X25519) or 65 (P-256); 0 for NULL. */
@@ -111,6 +119,34 @@ int32_t jx_hpke_open_long_batch(jx_hpke* h, uint64_t n, const uint8_t* encs, con
 int32_t jx_hpke_open_long_batch_device(jx_hpke* h, uint64_t n, const void* d_encs, const void* d_cts,
                                        const uint64_t* d_ct_offsets, const void* d_aads, const uint64_t* d_aad_offsets,
                                        void* d_out_plaintexts, void* d_out_ok);
+/* ---- Seal: RFC 9180 base-mode single-shot seal (sequence number 0, nonce = base_nonce; core/src/hpke.rs:167), the
+ * mirror of the open calls above, under any X25519 context: a sender context, or a recipient context (its public key
+ * is what the seal uses). A P-256 context returns JX_HPKE_E_UNSUPPORTED.
+ *  - ephemeral_sks: n x 32, the ephemeral X25519 private keys, one per seal, clamped by the engine. The engine draws
+ *                   no randomness: the caller owns the CSPRNG. They are secrets: on the device they pass through the
+ *                   masked-swap ladder only.
+ *  - pts:           plaintexts back to back, pt_offsets[n + 1]; aads / aad_offsets[n + 1] as for the opens
+ *  - out_encs:      n x 32, enc = X25519(skE, 9)
+ *  - out_cts:       ciphertext i (plaintext length + 16 bytes) at offset pt_offsets[i] + 16 i
+ *  - out_ok:        n bytes, 1 = sealed, 0 = X25519(skE, pkR) was all zero (a low-order recipient key): that seal's
+ *                   enc and ciphertext are zeros
+ * jx_hpke_seal_batch is the short form, one seal per lane pair, for payloads such as the helper's 54-byte plaintext;
+ * jx_hpke_seal_long_batch spreads the AEAD of each seal over a wave and gives the same bytes. The
+ * host forms check the offsets (decreasing offsets, or a plaintext of 2^32 - 16 bytes or more: JX_HPKE_E_INVALID); the
+ * device forms cannot read them, and their kernels fail such a seal (ok = 0, nothing written). n == 0 is
+ * JX_HPKE_OK. The device forms are asynchronous on the context's stream. */
+int32_t jx_hpke_seal_batch(jx_hpke* h, uint64_t n, const uint8_t* ephemeral_sks, const uint8_t* pts,
+                           const uint64_t* pt_offsets, const uint8_t* aads, const uint64_t* aad_offsets,
+                           uint8_t* out_encs, uint8_t* out_cts, uint8_t* out_ok);
+int32_t jx_hpke_seal_batch_device(jx_hpke* h, uint64_t n, const void* d_ephemeral_sks, const void* d_pts,
+                                  const uint64_t* d_pt_offsets, const void* d_aads, const uint64_t* d_aad_offsets,
+                                  void* d_out_encs, void* d_out_cts, void* d_out_ok);
+int32_t jx_hpke_seal_long_batch(jx_hpke* h, uint64_t n, const uint8_t* ephemeral_sks, const uint8_t* pts,
+                                const uint64_t* pt_offsets, const uint8_t* aads, const uint64_t* aad_offsets,
+                                uint8_t* out_encs, uint8_t* out_cts, uint8_t* out_ok);
+int32_t jx_hpke_seal_long_batch_device(jx_hpke* h, uint64_t n, const void* d_ephemeral_sks, const void* d_pts,
+                                       const uint64_t* d_pt_offsets, const void* d_aads, const uint64_t* d_aad_offsets,
+                                       void* d_out_encs, void* d_out_cts, void* d_out_ok);
 /* The context's stream (a hipStream_t), on which jx_hpke_open_batch_device enqueues: for events around an open,
  * or to order other work after it. Created by the first call that needs it (this one included). */
 int32_t jx_hpke_stream(const jx_hpke* h, void** out_stream);

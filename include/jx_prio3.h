@@ -429,6 +429,45 @@ int32_t jx_client_shard_device(jx_engine* e, uint64_t n, const void* d_measureme
                                uint64_t lis_stride, void* d_out_helper_input_shares, void* d_out_status);
 int32_t jx_client_rand_bytes(const jx_engine* e, uint32_t* bytes);
 
+/* ---- The client's second half: the two hpke::seal calls of the reference client's prepare_report (client/src/
+ * lib.rs:339-383; core/src/hpke.rs:167) for the n reports whose rows jx_client_shard_* wrote. Per report, under RFC
+ * 9180 base mode (single shot: sequence number 0): the leader's PlaintextInputShare, u16 0 (no extensions) || u32 LIS ||
+ * leader row (read in place at lis_stride), is sealed for the leader, and the helper's, u16 0 || u32 HIS || helper
+ * input share, for the helper, each under its own recipient context and its own ephemeral key, with the encoded
+ * InputShareAad, task_id || report_id || time (u64 BE) || u32 PS || public_share, built on the device.
+ *   report_ids[n x 16], times[n] (a HOST array in both forms), public_shares[n x PS] (NULL when PS is 0), leader rows
+ *   (lis_stride apart; 0 = LIS), helper rows [n x HIS], task_id, leader / helper: X25519 contexts created with the
+ *   (InputShare, Client -> Leader) and (InputShare, Client -> Helper) application infos, normally sender contexts
+ *   (jx_hpke_create_sender; their keys are read from the device's key registry), ephemeral_sks[n x 64]: the leader
+ *   seal's X25519 private key, then the helper seal's, clamped by the engine (the engine draws no randomness: the
+ *   caller owns the CSPRNG, as for jx_client_shard_*'s rands), shard_status (nullable): jx_client_shard_*'s
+ *   out_status, a non-zero entry leaves that report's outputs zero.
+ * Outputs: leader encapsulated keys [n x 32] and ciphertext rows [n x (6 + LIS + 16)], the helper's [n x 32] and
+ * [n x (6 + HIS + 16)] (jx_client_seal_sizes gives the two row lengths), and out_status[n]: JX_SEAL_OK,
+ * JX_SEAL_SKIPPED (shard_status was non-zero: all four outputs zero), or JX_SEAL_ZERO_DH (a recipient key of low
+ * order: X25519(skE, pkR) was all zero; that share's encapsulated key and ciphertext are zeros). The ciphertext rows
+ * are what jx_leader_upload_open_device and jx_helper_prep_aggregate_encrypted_device read with payload_offsets[i] =
+ * i x row length and enc_offsets = NULL.
+ * The device call is asynchronous on the engine stream under the ordering contract of the Conventions, takes its
+ * scratch from the device's arena, is cut into launches (debug option 11) and is not coalesced. It only reads rows,
+ * so it works for every algo id 0-5. n == 0 is JX_OK. A P-256 context returns JX_E_UNSUPPORTED. */
+#define JX_SEAL_OK 0
+#define JX_SEAL_SKIPPED 1
+#define JX_SEAL_ZERO_DH 2
+int32_t jx_client_seal_sizes(const jx_engine* e, uint32_t* leader_ct_len, uint32_t* helper_ct_len);
+int32_t jx_client_seal_batch(jx_engine* e, uint64_t n, const uint8_t* report_ids, const uint64_t* times,
+                             const uint8_t* public_shares, const uint8_t* leader_input_shares, uint64_t lis_stride,
+                             const uint8_t* helper_input_shares, const uint8_t task_id[32], jx_hpke* leader,
+                             jx_hpke* helper, const uint8_t* ephemeral_sks, const uint8_t* shard_status,
+                             uint8_t* out_leader_encs, uint8_t* out_leader_cts, uint8_t* out_helper_encs,
+                             uint8_t* out_helper_cts, uint8_t* out_status);
+int32_t jx_client_seal_device(jx_engine* e, uint64_t n, const void* d_report_ids, const uint64_t* times,
+                              const void* d_public_shares, const void* d_leader_input_shares, uint64_t lis_stride,
+                              const void* d_helper_input_shares, const uint8_t task_id[32], jx_hpke* leader,
+                              jx_hpke* helper, const void* d_ephemeral_sks, const void* d_shard_status,
+                              void* d_out_leader_encs, void* d_out_leader_cts, void* d_out_helper_encs,
+                              void* d_out_helper_cts, void* d_out_status);
+
 /* Accumulate the output shares of the resident batch `batch_id` (helper, or leader after finish) into
  * the engine's running batch aggregations (the engine as one shard, §8e): report i is added iff
  * verdict == FINISHED and accept_mask[i] != 0 (accept_mask nullable = all), into aggregation
@@ -545,7 +584,8 @@ int32_t jx_engine_timing_read(jx_engine* e, float ms[4], uint64_t launches[4]);
  *             (queued deferrals run first);
  *   option 9: run the deferred accumulations now;
  *   option 10: reports per launch of jx_client_shard_batch / _device: 0 automatic (what 4 GiB of scratch hold, at
- *             least 64), else that many. */
+ *             least 64), else that many;
+ *   option 11: reports per launch of jx_client_seal_batch / _device: 0 automatic (2^20), else that many. */
 int32_t jx_engine_debug(jx_engine* e, int32_t option, int64_t value);
 
 const char* jx_status_str(int32_t status);

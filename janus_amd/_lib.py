@@ -27,6 +27,7 @@ EXPORTED_SYMBOLS = (
     "jx_helper_prep_encrypted_batch2", "jx_leader_upload_open_batch", "jx_leader_upload_open_device",
     "jx_helper_prep_aggregate_encrypted", "jx_helper_prep_aggregate_encrypted_device",
     "jx_client_shard_batch", "jx_client_shard_device", "jx_client_rand_bytes",
+    "jx_client_seal_sizes", "jx_client_seal_batch", "jx_client_seal_device",
 )
 
 _lib = None
@@ -117,6 +118,10 @@ def load():
         "jx_client_shard_batch": (i32, [vp, u64, u8p, u8p, u8p, u8p, u8p, u8p, u8p]),
         "jx_client_shard_device": (i32, [vp, u64, vp, vp, vp, vp, vp, u64, vp, vp]),
         "jx_client_rand_bytes": (i32, [vp, P(u32)]),
+        "jx_client_seal_sizes": (i32, [vp, P(u32), P(u32)]),
+        "jx_client_seal_batch": (i32, [vp, u64, u8p, P(u64), u8p, u8p, u64, u8p, u8p, vp, vp, u8p, u8p, u8p, u8p, u8p,
+                                        u8p, u8p]),
+        "jx_client_seal_device": (i32, [vp, u64, vp, P(u64), vp, vp, u64, vp, u8p, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "jx_engine_sync": (i32, [vp]),
         "jx_engine_stream": (i32, [vp, P(vp)]),
         "jx_engine_wait_stream": (i32, [vp, vp]),

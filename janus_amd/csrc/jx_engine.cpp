@@ -808,6 +808,11 @@ int32_t jx_engine_debug(jx_engine* e, int32_t option, int64_t value) {
     e->shard_chunk = (uint64_t)value;
     return JX_OK;
   }
+  if (option == 11) {  // reports per launch of jx_client_seal_*: 0 automatic
+    if (value < 0) return JX_E_INVALID;
+    e->seal_chunk = (uint64_t)value;
+    return JX_OK;
+  }
   if (option == 7) {  // tests: the device coalescer's gathers wait (up to their window) for this many jobs
     if (value < 0 || value > (int64_t)MAX_JOBS_PER_LAUNCH) return JX_E_INVALID;
     if (!e->coal) return fail(e, JX_E_STATE, "debug option 7: coalescing is off");

@@ -213,6 +213,7 @@ int hpke_device(const jx_hpke* h);
 uint16_t hpke_slot(const jx_hpke* h);
 void hpke_registry(int device, const jx::HpkeKeyRow** rows, uint32_t* capacity);
 bool hpke_default_suite(const jx_hpke* h);  // X25519 with (HKDF-SHA256, AES-128-GCM)
+bool hpke_is_sender(const jx_hpke* h);      // jx_hpke_create_sender's: no private key, so no call may open with it
 uint32_t hpke_enc_len(const jx_hpke* h);    // the length of its KEM's encapsulated keys: 32 or 65
 // suites: a job of the launch holds a key of another suite than the default (every 32-byte row then goes through
 // hpke_rows_suite_kernel); p256_rows: the launch holds an ENC_ROW_ENC65 row (hpke_rows_p256_kernel runs too)
@@ -327,6 +328,7 @@ struct jx_engine {
   uint64_t acc_flushes = 0, acc_deferred = 0;
   uint32_t* d_err = nullptr;  // combine kernels: non-canonical input seen (reported by jx_engine_sync)
   uint4* d_shard_tab = nullptr;  // jx_client_shard_*: the prover's transform table (jx_ntt.h), made by the first call
+  uint64_t seal_chunk = 0;       // reports per launch of jx_client_seal_* (debug option 11; 0: automatic)
   uint64_t shard_chunk = 0;      // reports per launch of jx_client_shard_* (debug option 10; 0: by the scratch budget)
   // timing
   bool timing = false;

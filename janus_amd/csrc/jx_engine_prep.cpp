@@ -52,9 +52,12 @@ int32_t jxi::enc_job_check(jx_engine* e, uint64_t n, const uint64_t* times, cons
                            uint32_t flags, EncJob& job) {
   if (nkeypairs > JX_ENC_MAX_KEYPAIRS || (nkeypairs && !keypairs) || (flags & ~JX_ENC_REQUIRE_TASKPROV))
     return fail(e, JX_E_INVALID, "encrypted prepare: at most JX_ENC_MAX_KEYPAIRS keypairs, flags JX_ENC_*");
-  for (uint32_t k = 0; k < nkeypairs; k++)
+  for (uint32_t k = 0; k < nkeypairs; k++) {
     if (!keypairs[k] || hpke_device(keypairs[k]) != e->device)
       return fail(e, JX_E_INVALID, "encrypted prepare: every keypair must be an HPKE context on the engine's device");
+    if (hpke_is_sender(keypairs[k]))
+      return fail(e, JX_E_INVALID, "encrypted prepare: a sender context (jx_hpke_create_sender) holds no private key");
+  }
   for (uint64_t i = 0; i < n; i++) {
     const uint8_t k0 = key_index[2 * i], k1 = key_index[2 * i + 1];
     if ((k0 >= nkeypairs && k0 != JX_KEY_NONE && k0 != JX_KEY_MALFORMED) || (k1 >= nkeypairs && k1 != JX_KEY_NONE) ||

@@ -24,6 +24,8 @@ int32_t upload_rows(jx_engine* e, uint64_t n, const uint64_t* times, jx_hpke* co
   for (uint32_t k = 0; k < nkeypairs; k++) {
     if (!keypairs[k] || hpke_device(keypairs[k]) != e->device)
       return fail(e, JX_E_INVALID, "upload open: every keypair must be an HPKE context on the engine's device");
+    if (hpke_is_sender(keypairs[k]))
+      return fail(e, JX_E_INVALID, "upload open: a sender context (jx_hpke_create_sender) holds no private key");
     klen[k] = hpke_enc_len(keypairs[k]);
     slot[k] = hpke_slot(keypairs[k]);
     *any_p256 = *any_p256 || klen[k] == 65;

@@ -279,17 +279,12 @@ JX_HD int m_suite_kem(Msg128& m, int pos) {
   return pos + 2;
 }
 
-// Decap (RFC 9180 §4.1) for the recipient key (sk clamped, pk; 8 LE words each) and encapsulated key enc (8 LE
-// words): dh = X25519(sk, enc), eae_prk = LabeledExtract("", "eae_prk", dh), shared_secret = LabeledExpand(
-// eae_prk, "shared_secret", enc || pk, 32) as 8 big-endian words. The KEM's KDF is HKDF-SHA256 whatever the
-// suite's KDF is. zist / zost: the HMAC-SHA256 pads of the empty salt. False when the DH output is all zero (a
-// low-order point: the open fails).
-JX_HD bool hpke_decap(uint32_t ss[8], const uint32_t sk[8], const uint32_t pk[8], const uint32_t zist[8],
-                      const uint32_t zost[8], const uint32_t enc[8]) {
-  uint32_t dh[8];
-  x25519_ladder(dh, sk, enc);
-  uint32_t nz = 0;
-  for (int i = 0; i < 8; i++) nz |= dh[i];
+// ExtractAndExpand(dh, kem_context = enc || pk), the half that Decap and Encap (jx_hpke_seal.h) share: eae_prk =
+// LabeledExtract("", "eae_prk", dh), shared_secret = LabeledExpand(eae_prk, "shared_secret", enc || pk, 32) as 8
+// big-endian words. The KEM's KDF is HKDF-SHA256 whatever the suite's KDF is. zist / zost: the HMAC-SHA256 pads of
+// the empty salt.
+JX_HD void hpke_extract_and_expand(uint32_t ss[8], const uint32_t dh[8], const uint32_t pk[8], const uint32_t zist[8],
+                                   const uint32_t zost[8], const uint32_t enc[8]) {
   uint32_t eae_prk[8];
   {
     Msg128 m;
@@ -319,6 +314,18 @@ JX_HD bool hpke_decap(uint32_t ss[8], const uint32_t sk[8], const uint32_t pk[8]
     sha256_finish64(inner, ist, m, pos + 1);
     hmac_outer(ss, ost, inner);
   }
+}
+
+// Decap (RFC 9180 §4.1) for the recipient key (sk clamped, pk; 8 LE words each) and encapsulated key enc (8 LE
+// words): dh = X25519(sk, enc), then ExtractAndExpand. False when the DH output is all zero (a low-order point: the
+// open fails).
+JX_HD bool hpke_decap(uint32_t ss[8], const uint32_t sk[8], const uint32_t pk[8], const uint32_t zist[8],
+                      const uint32_t zost[8], const uint32_t enc[8]) {
+  uint32_t dh[8];
+  x25519_ladder(dh, sk, enc);
+  uint32_t nz = 0;
+  for (int i = 0; i < 8; i++) nz |= dh[i];
+  hpke_extract_and_expand(ss, dh, pk, zist, zost, enc);
   return nz != 0;
 }
 

@@ -27,7 +27,8 @@
 // This unit holds the C ABI, the key registry, open_mask_kernel, enc_rows_kernel (the rows of a launch of the sealed
 // fused call's device form, laid out on the device by the rule of jx_enc_rows.h) and the two dispatchers, launch_open
 // and jxi::launch_hpke_rows. Each kernel pair is a translation unit of its own, so that the three compile side by side:
-// jx_hpke_default.hip, jx_hpke_suite.hip and jx_hpke_p256.hip; what they share is in jx_hpke_open.h.
+// jx_hpke_default.hip, jx_hpke_suite.hip and jx_hpke_p256.hip; what they share is in jx_hpke_open.h. The seal calls
+// (jx_hpke_create_sender, jx_hpke_seal_*) are here too; their kernels are in jx_hpke_seal.hip.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -39,6 +40,7 @@
 #include "jx_engine_internal.h"
 #include "jx_hpke_long.h"
 #include "jx_hpke_open.h"
+#include "jx_hpke_seal.h"
 #include "jx_hpke_suites.h"
 #include "jx_keyreg.h"
 
@@ -86,6 +88,7 @@ struct jx_hpke {
   HpkeCfg cfg{};
   bool default_suite = true;  // X25519 with (HKDF-SHA256, AES-128-GCM): opened by hpke_open_kernel / hpke_rows_kernel
   uint32_t kem = HPKE_KEM_X25519_SHA256;
+  bool sender = false;  // jx_hpke_create_sender: the recipient's public key alone (sk is zero); it seals, never opens
   int device = 0;
   uint32_t slot = 0;            // the context's row of the device's key registry, for as long as it lives
   hipStream_t stream = nullptr;  // created at the first standalone open or jx_hpke_stream (ensure_stream)
@@ -173,6 +176,11 @@ int32_t ensure_stream(jx_hpke* h) {
 }
 }  // namespace
 
+// a context of jx_hpke_create_sender holds no private key: refused before anything is queued
+static int32_t refuse_sender() {
+  return hfail(JX_HPKE_E_INVALID, "a sender context (jx_hpke_create_sender) holds no private key: it cannot open");
+}
+
 // the default suite keeps its own kernel; any other goes through the suite kernel of its KEM
 static void launch_open(const jx_hpke* h, const HpkeBufs& b) {
   if (h->kem == HPKE_KEM_P256_SHA256)
@@ -194,6 +202,7 @@ void hpke_registry(int device, const HpkeKeyRow** rows, uint32_t* capacity) {
   *capacity = KEY_SLOTS;
 }
 bool hpke_default_suite(const jx_hpke* h) { return h->default_suite; }
+bool hpke_is_sender(const jx_hpke* h) { return h->sender; }
 uint32_t hpke_enc_len(const jx_hpke* h) { return jx::hpke_enc_len(h->kem); }
 
 hipError_t launch_hpke_rows(const HpkeRowsArgs& a, bool suites, bool p256_rows, hipStream_t s) {
@@ -225,6 +234,38 @@ hipError_t launch_open_mask(const uint8_t* status, uint8_t* verdicts, uint64_t n
 }
 
 }  // namespace jxi
+
+// The context of a key row whose sk / pk / pky are filled in: the device, the key_schedule_context under the key's
+// own suite, the registry row.
+static int32_t create_context(const HpkeKeyRow& key, uint32_t kem_id, uint32_t kdf_id, uint32_t aead_id,
+                              const uint8_t* info, uint32_t info_len, int32_t device, bool sender, jx_hpke** out) {
+  const bool p256 = kem_id == HPKE_KEM_P256_SHA256;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return JX_HPKE_E_NODEVICE;
+  if (device < 0 || device >= ndev) return JX_HPKE_E_INVALID;
+  jx_hpke* h = new jx_hpke();
+  h->device = device;
+  h->cfg.key = key;
+  h->kem = kem_id;
+  h->sender = sender;
+  const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  hmac_pads(zero, h->cfg.zero_ist, h->cfg.zero_ost);
+  // the key_schedule_context under the key's own suite and hash (jx_hpke_suites.h)
+  static_assert(sizeof(h->cfg.key.ksc) >= HPKE_KSC_MAX, "HpkeKeyRow holds the longest key_schedule_context");
+  hpke_key_schedule_context(kdf_id, aead_id, info, info_len, h->cfg.key.ksc, kem_id);
+  h->cfg.key.kdf = (uint8_t)kdf_id;
+  h->cfg.key.aead = (uint8_t)aead_id;
+  h->cfg.key.kem = (uint8_t)kem_id;
+  h->default_suite = !p256 && kdf_id == HPKE_KDF_SHA256 && aead_id == HPKE_AEAD_AES128GCM;
+  // the context's row of the device's key registry (full: JX_HPKE_E_NOMEM)
+  if (const int32_t rc = registry_add(device, h->cfg.key, &h->slot)) {
+    delete h;
+    return rc;
+  }
+  h->arena = jxi::arena_for(device);
+  *out = h;
+  return JX_HPKE_OK;
+}
 
 extern "C" {
 
@@ -276,30 +317,25 @@ int32_t jx_hpke_create_key(uint32_t kem_id, uint32_t kdf_id, uint32_t aead_id, c
       memcpy(&key.pk[i], pk + 4 * i, 4);
     }
   }
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return JX_HPKE_E_NODEVICE;
-  if (device < 0 || device >= ndev) return JX_HPKE_E_INVALID;
-  jx_hpke* h = new jx_hpke();
-  h->device = device;
-  h->cfg.key = key;
-  h->kem = kem_id;
-  const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  hmac_pads(zero, h->cfg.zero_ist, h->cfg.zero_ost);
-  // the key_schedule_context under the key's own suite and hash (jx_hpke_suites.h)
-  static_assert(sizeof(h->cfg.key.ksc) >= HPKE_KSC_MAX, "HpkeKeyRow holds the longest key_schedule_context");
-  hpke_key_schedule_context(kdf_id, aead_id, info, info_len, h->cfg.key.ksc, kem_id);
-  h->cfg.key.kdf = (uint8_t)kdf_id;
-  h->cfg.key.aead = (uint8_t)aead_id;
-  h->cfg.key.kem = (uint8_t)kem_id;
-  h->default_suite = !p256 && kdf_id == HPKE_KDF_SHA256 && aead_id == HPKE_AEAD_AES128GCM;
-  // the context's row of the device's key registry (full: JX_HPKE_E_NOMEM)
-  if (const int32_t rc = registry_add(device, h->cfg.key, &h->slot)) {
-    delete h;
-    return rc;
-  }
-  h->arena = jxi::arena_for(device);
-  *out = h;
-  return JX_HPKE_OK;
+  return create_context(key, kem_id, kdf_id, aead_id, info, info_len, device, false, out);
+}
+
+int32_t jx_hpke_create_sender(uint32_t kem_id, uint32_t kdf_id, uint32_t aead_id, const uint8_t* pk, uint32_t pk_len,
+                              const uint8_t* info, uint32_t info_len, int32_t device, jx_hpke** out) {
+  if (!pk || !out || (info_len && !info)) return JX_HPKE_E_INVALID;
+  *out = nullptr;
+  if (kem_id == HPKE_KEM_P256_SHA256 && kdf_id >= 1 && kdf_id <= 3 && aead_id >= 1 && aead_id <= 3)
+    return hfail(JX_HPKE_E_UNSUPPORTED,
+                 "sealing under KEM 0x0010 (P-256) is out of scope: the engine seals under KEM 0x0020 (X25519) only");
+  if (!hpke_suite_supported(kem_id, kdf_id, aead_id))
+    return hfail(JX_HPKE_E_UNSUPPORTED,
+                 "unsupported HPKE suite (KEM " + std::to_string(kem_id) + ", KDF " + std::to_string(kdf_id) + ", AEAD " +
+                     std::to_string(aead_id) + "): a sender seals under KEM 0x0020 (X25519), KDF 1..3 (HKDF-SHA256/384/512), "
+                     "AEAD 1..3 (AES-128-GCM, AES-256-GCM, ChaCha20Poly1305)");
+  if (pk_len != 32) return hfail(JX_HPKE_E_INVALID, "X25519 sender: the recipient's public key is 32 bytes");
+  HpkeKeyRow key{};  // the private-key words stay zero
+  for (int i = 0; i < 8; i++) memcpy(&key.pk[i], pk + 4 * i, 4);
+  return create_context(key, kem_id, kdf_id, aead_id, info, info_len, device, true, out);
 }
 
 int32_t jx_hpke_suite(const jx_hpke* h, uint32_t* kem_id, uint32_t* kdf_id, uint32_t* aead_id) {
@@ -338,6 +374,7 @@ int32_t jx_hpke_open_batch_device(jx_hpke* h, uint64_t n, const void* d_encs, co
   if (!h || (n && (!d_encs || !d_cts || !d_ct_offsets || !d_aad_offsets || !d_out_plaintexts || !d_out_ok))) {
     return JX_HPKE_E_INVALID;
   }
+  if (h->sender) return refuse_sender();
   if (n == 0) return JX_HPKE_OK;
   std::lock_guard<std::mutex> lk(h->mu);
   HCHK(hipSetDevice(h->device));
@@ -362,6 +399,7 @@ int32_t jx_hpke_open_batch(jx_hpke* h, uint64_t n, const uint8_t* encs, const ui
                            uint8_t* out_plaintexts, uint8_t* out_ok) {
   if (!h || (n && (!encs || !cts || !ct_offsets || !aad_offsets || !out_plaintexts || !out_ok)))
     return JX_HPKE_E_INVALID;
+  if (h->sender) return refuse_sender();
   if (n == 0) return JX_HPKE_OK;
   for (uint64_t i = 0; i < n; i++)
     if (ct_offsets[i + 1] < ct_offsets[i] + 16 || aad_offsets[i + 1] < aad_offsets[i])
@@ -439,6 +477,7 @@ int32_t jx_hpke_open_long_batch_device(jx_hpke* h, uint64_t n, const void* d_enc
   if (!h || (n && (!d_encs || !d_cts || !d_ct_offsets || !d_aad_offsets || !d_out_plaintexts || !d_out_ok))) {
     return JX_HPKE_E_INVALID;
   }
+  if (h->sender) return refuse_sender();
   if (n == 0) return JX_HPKE_OK;
   std::lock_guard<std::mutex> lk(h->mu);
   HCHK(hipSetDevice(h->device));
@@ -459,6 +498,7 @@ int32_t jx_hpke_open_long_batch(jx_hpke* h, uint64_t n, const uint8_t* encs, con
                                 uint8_t* out_plaintexts, uint8_t* out_ok) {
   if (!h || (n && (!encs || !cts || !ct_offsets || !aad_offsets || !out_plaintexts || !out_ok)))
     return JX_HPKE_E_INVALID;
+  if (h->sender) return refuse_sender();
   if (n == 0) return JX_HPKE_OK;
   for (uint64_t i = 0; i < n; i++) {
     if (ct_offsets[i + 1] < ct_offsets[i] + 16 || aad_offsets[i + 1] < aad_offsets[i])
@@ -501,6 +541,138 @@ int32_t jx_hpke_open_long_batch(jx_hpke* h, uint64_t n, const uint8_t* encs, con
   } while (0);
   jxi::arena_put(h->arena, slab, h->stream);  // reused after this stream's work
   return rc;
+}
+
+// ---- seal (jx_hpke_seal.hip)
+
+// with h->mu held and the device set: the launches on the context's stream; the long form's context rows in a slab of
+// the arena that goes back stream-ordered
+static int32_t launch_seal(jx_hpke* h, SealArgs& a, bool long_form) {
+  uint32_t cap = 0;
+  jxi::hpke_registry(h->device, &a.keys, &cap);
+  a.slot = h->slot;
+  memcpy(a.zero_ist, h->cfg.zero_ist, 32);
+  memcpy(a.zero_ost, h->cfg.zero_ost, 32);
+  jxi::Slab slab;
+  if (long_form) {
+    const hipError_t ga = jxi::arena_get(h->arena, jxi::align256(a.n * SEAL_CTX_BYTES), h->stream, true, true, slab);
+    if (ga == hipErrorOutOfMemory) return hfail(JX_HPKE_E_NOMEM, "device allocation failed (arena)");
+    HCHK(ga);
+    a.ctx = slab.p;
+  }
+  const hipError_t st = launch_hpke_seal(a, long_form, h->stream);
+  if (long_form) jxi::arena_put(h->arena, slab, h->stream);
+  if (st != hipSuccess) return hfail(JX_HPKE_E_HIP, std::string("seal launch: ") + hipGetErrorString(st));
+  return JX_HPKE_OK;
+}
+
+static int32_t seal_device(jx_hpke* h, uint64_t n, const void* d_sks, const void* d_pts, const uint64_t* d_pt_offsets,
+                           const void* d_aads, const uint64_t* d_aad_offsets, void* d_out_encs, void* d_out_cts,
+                           void* d_out_ok, bool long_form) {
+  if (!h || (n && (!d_sks || !d_pt_offsets || !d_aad_offsets || !d_out_encs || !d_out_cts || !d_out_ok)))
+    return JX_HPKE_E_INVALID;
+  if (h->kem != HPKE_KEM_X25519_SHA256)
+    return hfail(JX_HPKE_E_UNSUPPORTED, "sealing under KEM 0x0010 (P-256) is out of scope");
+  if (n == 0) return JX_HPKE_OK;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HCHK(hipSetDevice(h->device));
+  if (const int32_t rc = ensure_stream(h)) return rc;
+  SealArgs a{};
+  a.n = n;
+  a.sks = (const uint8_t*)d_sks;
+  a.pts = (const uint8_t*)d_pts;
+  a.pt_off = d_pt_offsets;
+  a.aads = (const uint8_t*)d_aads;
+  a.aad_off = d_aad_offsets;
+  a.encs = (uint8_t*)d_out_encs;
+  a.cts = (uint8_t*)d_out_cts;
+  a.ok = (uint8_t*)d_out_ok;
+  return launch_seal(h, a, long_form);
+}
+
+// Host buffers: one staging slab from the device's arena, as the opens take theirs.
+static int32_t seal_host(jx_hpke* h, uint64_t n, const uint8_t* sks, const uint8_t* pts, const uint64_t* pt_offsets,
+                         const uint8_t* aads, const uint64_t* aad_offsets, uint8_t* out_encs, uint8_t* out_cts,
+                         uint8_t* out_ok, bool long_form) {
+  if (!h || (n && (!sks || !pt_offsets || !aad_offsets || !out_encs || !out_cts || !out_ok))) return JX_HPKE_E_INVALID;
+  if (h->kem != HPKE_KEM_X25519_SHA256)
+    return hfail(JX_HPKE_E_UNSUPPORTED, "sealing under KEM 0x0010 (P-256) is out of scope");
+  if (n == 0) return JX_HPKE_OK;
+  for (uint64_t i = 0; i < n; i++) {
+    if (pt_offsets[i + 1] < pt_offsets[i] || aad_offsets[i + 1] < aad_offsets[i])
+      return hfail(JX_HPKE_E_INVALID, "offsets must be non-decreasing");
+    if (pt_offsets[i + 1] - pt_offsets[i] >= (1ull << 32) - 16)
+      return hfail(JX_HPKE_E_INVALID, "a plaintext of 2^32 - 16 bytes or more is no report share");
+  }
+  const uint64_t p0 = pt_offsets[0], pt_bytes = pt_offsets[n] - p0, a0 = aad_offsets[0], aad_bytes = aad_offsets[n] - a0;
+  if ((pt_bytes && !pts) || (aad_bytes && !aads)) return JX_HPKE_E_INVALID;
+  std::lock_guard<std::mutex> lk(h->mu);
+  HCHK(hipSetDevice(h->device));
+  if (const int32_t rc = ensure_stream(h)) return rc;
+  const uint64_t ct_bytes = pt_bytes + 16 * n;
+  const size_t o_sk = 0, o_pt = o_sk + jxi::align256(32 * n), o_aad = o_pt + jxi::align256(pt_bytes ? pt_bytes : 1),
+               o_enc = o_aad + jxi::align256(aad_bytes ? aad_bytes : 1), o_ct = o_enc + jxi::align256(32 * n),
+               o_ok = o_ct + jxi::align256(ct_bytes), o_po = o_ok + jxi::align256(n), o_ao = o_po + jxi::align256((n + 1) * 8),
+               bytes = o_ao + jxi::align256((n + 1) * 8);
+  jxi::Slab slab;
+  const hipError_t ga = jxi::arena_get(h->arena, bytes, h->stream, true, true, slab);
+  if (ga == hipErrorOutOfMemory) return hfail(JX_HPKE_E_NOMEM, "device allocation failed (arena)");
+  HCHK(ga);
+  uint8_t* base = (uint8_t*)slab.p;
+  int32_t rc = JX_HPKE_OK;
+  do {
+    if (hipMemcpyAsync(base + o_sk, sks, 32 * n, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        (pt_bytes && hipMemcpyAsync(base + o_pt, pts + p0, pt_bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) ||
+        (aad_bytes && hipMemcpyAsync(base + o_aad, aads + a0, aad_bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess) ||
+        hipMemcpyAsync(base + o_po, pt_offsets, (n + 1) * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipMemcpyAsync(base + o_ao, aad_offsets, (n + 1) * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) {
+      rc = hfail(JX_HPKE_E_HIP, "host-to-device copy failed");
+      break;
+    }
+    SealArgs a{};
+    a.n = n;
+    a.sks = base + o_sk;
+    a.pts = base + o_pt - p0;  // the kernels index by the caller's offsets
+    a.pt_off = (const uint64_t*)(base + o_po);
+    a.aads = base + o_aad - a0;
+    a.aad_off = (const uint64_t*)(base + o_ao);
+    a.encs = base + o_enc;
+    a.cts = base + o_ct - p0;
+    a.ok = base + o_ok;
+    if ((rc = launch_seal(h, a, long_form)) != JX_HPKE_OK) break;
+    if (hipMemcpyAsync(out_encs, base + o_enc, 32 * n, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        hipMemcpyAsync(out_cts + p0, base + o_ct, ct_bytes, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        hipMemcpyAsync(out_ok, base + o_ok, n, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
+        hipStreamSynchronize(h->stream) != hipSuccess) {
+      rc = hfail(JX_HPKE_E_HIP, "device-to-host copy failed");
+      break;
+    }
+  } while (0);
+  jxi::arena_put(h->arena, slab, h->stream);  // reused after this stream's work
+  return rc;
+}
+
+int32_t jx_hpke_seal_batch(jx_hpke* h, uint64_t n, const uint8_t* ephemeral_sks, const uint8_t* pts,
+                           const uint64_t* pt_offsets, const uint8_t* aads, const uint64_t* aad_offsets,
+                           uint8_t* out_encs, uint8_t* out_cts, uint8_t* out_ok) {
+  return seal_host(h, n, ephemeral_sks, pts, pt_offsets, aads, aad_offsets, out_encs, out_cts, out_ok, false);
+}
+int32_t jx_hpke_seal_long_batch(jx_hpke* h, uint64_t n, const uint8_t* ephemeral_sks, const uint8_t* pts,
+                                const uint64_t* pt_offsets, const uint8_t* aads, const uint64_t* aad_offsets,
+                                uint8_t* out_encs, uint8_t* out_cts, uint8_t* out_ok) {
+  return seal_host(h, n, ephemeral_sks, pts, pt_offsets, aads, aad_offsets, out_encs, out_cts, out_ok, true);
+}
+int32_t jx_hpke_seal_batch_device(jx_hpke* h, uint64_t n, const void* d_ephemeral_sks, const void* d_pts,
+                                  const uint64_t* d_pt_offsets, const void* d_aads, const uint64_t* d_aad_offsets,
+                                  void* d_out_encs, void* d_out_cts, void* d_out_ok) {
+  return seal_device(h, n, d_ephemeral_sks, d_pts, d_pt_offsets, d_aads, d_aad_offsets, d_out_encs, d_out_cts, d_out_ok,
+                     false);
+}
+int32_t jx_hpke_seal_long_batch_device(jx_hpke* h, uint64_t n, const void* d_ephemeral_sks, const void* d_pts,
+                                       const uint64_t* d_pt_offsets, const void* d_aads, const uint64_t* d_aad_offsets,
+                                       void* d_out_encs, void* d_out_cts, void* d_out_ok) {
+  return seal_device(h, n, d_ephemeral_sks, d_pts, d_pt_offsets, d_aads, d_aad_offsets, d_out_encs, d_out_cts, d_out_ok,
+                     true);
 }
 
 const char* jx_hpke_last_error(const jx_hpke* h) {

@@ -33,21 +33,6 @@
 namespace jx {
 namespace {
 
-constexpr uint32_t WAVES = 4;  // per workgroup
-
-__device__ __forceinline__ void write_ctx(LongCtxRow& o, uint32_t aead, const uint8_t kb[32], const uint8_t nb[12],
-                                          bool ok) {
-  for (int i = 0; i < 8; i++)
-    o.kw[i] = (uint32_t)kb[4 * i] | ((uint32_t)kb[4 * i + 1] << 8) | ((uint32_t)kb[4 * i + 2] << 16) |
-              ((uint32_t)kb[4 * i + 3] << 24);
-  for (int i = 0; i < 3; i++)
-    o.nw[i] = (uint32_t)nb[4 * i] | ((uint32_t)nb[4 * i + 1] << 8) | ((uint32_t)nb[4 * i + 2] << 16) |
-              ((uint32_t)nb[4 * i + 3] << 24);
-  o.aead = aead;
-  o.ok = ok ? 1u : 0u;
-  o.pad[0] = o.pad[1] = o.pad[2] = 0;
-}
-
 __global__ __launch_bounds__(64) void hpke_long_ctx_x25519_kernel(LongCtxArgs a) {
   const uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= a.n) return;
@@ -72,54 +57,6 @@ __global__ __launch_bounds__(64) void hpke_long_ctx_p256_kernel(LongCtxArgs a) {
   write_ctx(a.out[r], key.aead, kb, nb, ok);
 }
 
-// len (1..16) bytes at p as 4 little-endian words, zero padded: the aligned 16 bytes that hold p[0] and, when the
-// block goes past them, the next aligned 16 (which then hold p[len - 1]), so no load leaves the 16-byte lines of
-// the block's own bytes
-__device__ __forceinline__ void ld16(const uint8_t* p, uint32_t len, uint32_t w[4]) {
-  const uintptr_t a = (uintptr_t)p;
-  const uint32_t sh = (uint32_t)(a & 15);
-  const uint4* q = reinterpret_cast<const uint4*>(a - sh);
-  const uint4 lo = q[0];
-  uint4 hi = make_uint4(0, 0, 0, 0);
-  if (sh + len > 16) hi = q[1];
-  uint32_t v0 = lo.x, v1 = lo.y, v2 = lo.z, v3 = lo.w, v4 = hi.x, v5 = hi.y, v6 = hi.z, v7 = hi.w;
-  if (sh & 8) {
-    v0 = v2, v1 = v3, v2 = v4, v3 = v5, v4 = v6, v5 = v7;
-  }
-  if (sh & 4) {
-    v0 = v1, v1 = v2, v2 = v3, v3 = v4, v4 = v5;
-  }
-  const uint32_t b = 8 * (sh & 3);
-  w[0] = __funnelshift_r(v0, v1, b);
-  w[1] = __funnelshift_r(v1, v2, b);
-  w[2] = __funnelshift_r(v2, v3, b);
-  w[3] = __funnelshift_r(v3, v4, b);
-  if (len < 16) {
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-      const uint32_t nb = len > 4u * i ? len - 4u * i : 0u;
-      w[i] &= nb >= 4 ? 0xffffffffu : ((1u << (8 * nb)) - 1u);
-    }
-  }
-}
-
-__device__ __forceinline__ void st16(uint8_t* p, uint32_t len, const uint32_t w[4]) {
-  const uintptr_t a = (uintptr_t)p;
-  if (len == 16 && (a & 15) == 0) {
-    *reinterpret_cast<uint4*>(p) = make_uint4(w[0], w[1], w[2], w[3]);
-  } else if (len == 16 && (a & 3) == 0) {
-    uint32_t* q = reinterpret_cast<uint32_t*>(p);
-    q[0] = w[0], q[1] = w[1], q[2] = w[2], q[3] = w[3];
-  } else {
-    for (uint32_t j = 0; j < len; j++) p[j] = (uint8_t)(w[j >> 2] >> (8 * (j & 3)));
-  }
-}
-
-__device__ __forceinline__ void shfl4(uint32_t out[4], const uint32_t in[4], uint32_t src) {
-#pragma unroll
-  for (int k = 0; k < 4; k++) out[k] = __shfl(in[k], (int)src);
-}
-
 // AES-GCM open by the whole wave; every lane returns the same verdict. tt: the T-table; m4: the wave's 16 x 4 words.
 // aad_ld(o, len, x): len (1..16) bytes of the associated data from offset o as 4 little-endian words, zero padded.
 template <int NK, class AadLd>
@@ -127,38 +64,8 @@ __device__ bool gcm_wave_open(const uint32_t* tt, uint32_t* m4, uint32_t lane, c
                               uint64_t alen, const uint8_t* ct, uint64_t clen, uint8_t* pt) {
   const uint32_t* tl = tt + (lane & 31u);
   auto T = [tl](uint32_t x) { return tl[x << 5]; };
-  uint32_t rk[4 * (NK + 7)];
-  aes_expand_key_t<NK>(T, c.kw, rk);
-  uint32_t h[4];
-  {
-    const uint32_t zero4[4] = {0, 0, 0, 0};
-    uint32_t hb[4];
-    aes_encrypt_t_nk<NK>(T, rk, zero4, hb);
-    for (int i = 0; i < 4; i++) h[i] = bswap32(hb[i]);
-  }
-  // lane l: H^(l+1), by doubling
-  uint32_t pw[4] = {h[0], h[1], h[2], h[3]};
-#pragma unroll 1
-  for (int s = 0; s < 6; s++) {
-    uint32_t base[4], other[4];
-    shfl4(base, pw, gl_pow_src_base(s));
-    shfl4(other, pw, gl_pow_src_other(s, lane));
-    ghash_mul(other, base);
-    if (gl_pow_active(s, lane))
-      for (int k = 0; k < 4; k++) pw[k] = other[k];
-  }
-  // the table of H^64 (lane 63's power): entry n by lane n
-  {
-    uint32_t h64[4], e[4];
-    shfl4(h64, pw, 63);
-    gl_tab4_entry(lane & 15u, h64, e);
-    if (lane < 16) {
-      uint4* dst = reinterpret_cast<uint4*>(m4) + lane;
-      *dst = make_uint4(e[0], e[1], e[2], e[3]);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-  }
+  uint32_t rk[4 * (NK + 7)], h[4], pw[4];
+  gcm_wave_setup<NK>(T, m4, lane, c.kw, rk, h, pw);
   const uint4* m4v = reinterpret_cast<const uint4*>(m4);
   auto M = [m4v](uint32_t n, uint32_t e[4]) {
     const uint4 v = m4v[n];
@@ -209,11 +116,6 @@ __device__ bool gcm_wave_open(const uint32_t* tt, uint32_t* m4, uint32_t lane, c
   return true;
 }
 
-__device__ __forceinline__ void shfl5(uint32_t out[5], const uint32_t in[5], uint32_t src) {
-#pragma unroll
-  for (int k = 0; k < 5; k++) out[k] = __shfl(in[k], (int)src);
-}
-
 // ChaCha20-Poly1305 open by the whole wave; every lane returns the same verdict. aad_ld as for gcm_wave_open: its
 // zero-padded little-endian words are Poly1305's byte order. Every shuffle sits outside the per-lane block loops.
 template <class AadLd>
@@ -223,18 +125,8 @@ __device__ bool chapoly_wave_open(uint32_t lane, const LongCtxRow& c, AadLd aad_
   chacha20_block(c.kw, 0, c.nw, ks);  // every lane: the one-time key r || s is the first 32 bytes of block 0
   Poly1305 st;
   poly1305_init(st, ks);
-  // lane l: r^(l+1), by doubling
-  uint32_t pw[5] = {st.r[0], st.r[1], st.r[2], st.r[3], st.r[4]};
-#pragma unroll 1
-  for (int s = 0; s < 6; s++) {
-    uint32_t base[5], other[5];
-    shfl5(base, pw, gl_pow_src_base(s));
-    shfl5(other, pw, gl_pow_src_other(s, lane));
-    pl_mul(other, base);
-    if (gl_pow_active(s, lane))
-      for (int k = 0; k < 5; k++) pw[k] = other[k];
-  }
-  uint32_t r64[5];
+  uint32_t pw[5], r64[5];
+  poly_wave_powers(lane, st.r, pw);
   shfl5(r64, pw, 63);
   const uint64_t na = (alen + 15) / 16, nc = (clen + 15) / 16, N = pl_mac_blocks(alen, clen);
   uint32_t p[5];
@@ -294,10 +186,6 @@ __device__ __forceinline__ bool aead_wave_open(const uint32_t* tt, uint32_t* m4,
   if (c.aead == HPKE_AEAD_AES128GCM) return gcm_wave_open<4>(tt, m4, lane, c, aad_ld, alen, ct, clen, pt);
   if (c.aead == HPKE_AEAD_AES256GCM) return gcm_wave_open<8>(tt, m4, lane, c, aad_ld, alen, ct, clen, pt);
   return chapoly_wave_open(lane, c, aad_ld, alen, ct, clen, pt);
-}
-
-__device__ __forceinline__ void fill_ttable(uint32_t* tt) {
-  for (uint32_t i = threadIdx.x; i < 256 * 32; i += blockDim.x) tt[i] = aes_t0_entry(AES_SBOX[i >> 5]);
 }
 
 __global__ __launch_bounds__(64 * WAVES) void hpke_long_open_kernel(const LongCtxRow* ctx, HpkeBufs b) {
