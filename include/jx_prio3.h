@@ -468,6 +468,98 @@ int32_t jx_client_seal_device(jx_engine* e, uint64_t n, const void* d_report_ids
                               void* d_out_leader_encs, void* d_out_leader_cts, void* d_out_helper_encs,
                               void* d_out_helper_cts, void* d_out_status);
 
+/* ---- Wire in, wire out: the helper's aggregate-init exchange from the bytes it receives to the bytes it answers.
+ * jx_init_req_decode* cuts an AggregationJobInitializeReq body (u32 + aggregation parameter || PartialBatchSelector ||
+ * u32 + PrepareInits; messages/src/lib.rs:2482-2553) on the device into the arrays the sealed fused call reads, and
+ * jx_init_resp_encode* writes the AggregationJobResp body (u32 + PrepareResps) from that call's outputs. The request
+ * is decoded as the reference's get_decoded does: any framing error fails the whole request, and so does a repeated
+ * report id (aggregator.rs:1748-1758); what the reference's loop fails per report stays per report (wire_status).
+ *
+ * Decode returns a handle also for a request it refuses (jx_init_req_info says why); a refused request has no arrays
+ * and queues nothing. The body is copied to the device once (host form) or read in place (device form, asynchronous
+ * inputs ordered by the Conventions; the call itself waits for its own results, since n is one of them). After the
+ * call the body is no longer read. A handle holds device memory of the engine's arena until jx_init_req_release,
+ * which must come before jx_engine_destroy.
+ *   expected_query_type  JX_QUERY_TIME_INTERVAL or JX_QUERY_FIXED_SIZE: the task's (decode_expecting_value)
+ *   key_first/second     two 256-entry tables, config id -> keypair index of the request's keypairs as the sealed
+ *                        calls take them (first trial, second trial; JX_KEY_NONE where there is none)
+ *   report_deadline      NULL, or the latest report time that is not too early (aggregator.rs:1929-1940)
+ * Per report i the arrays hold: report id, time (native u64), public-share row (PS bytes), leader prep-share row (LPS
+ * bytes), the encapsulated keys and payloads packed with enc_offsets[n + 1] / payload_offsets[n + 1], key_index[2i..],
+ * wire_status[i] and route[i]. wire_status: 0; JX_WIRE_REPORT_ODD_PUBLIC_SHARE (the public share is not PS bytes: the
+ * row is zeros, both key indices are JX_KEY_NONE, and the host resolves the report from the body);
+ * JX_WIRE_REPORT_NOT_INITIALIZE (the ping-pong message is not Initialize) and JX_WIRE_REPORT_ODD_PREP_SHARE (its prep
+ * share is not LPS bytes) ride with a zero prep-share row. route[i] is 0, or 0xFFFFFFFF for a report that must not
+ * reach an aggregation (wire_status != 0, or its time is after the deadline): pass it as d_segment with one segment id.
+ * The host pointers of jx_init_req_arrays are one pinned copy made by the decode. */
+#define JX_WIRE_OK 0
+#define JX_WIRE_MALFORMED 1        /* info.error_offset: the read that failed */
+#define JX_WIRE_WRONG_QUERY_TYPE 2 /* info.error_offset: the query-type byte */
+#define JX_WIRE_DUPLICATE_ID 3     /* info.duplicate_index: the lowest index with an equal id at a lower index */
+#define JX_WIRE_REPORT_ODD_PUBLIC_SHARE 1
+#define JX_WIRE_REPORT_NOT_INITIALIZE 2
+#define JX_WIRE_REPORT_ODD_PREP_SHARE 3
+#define JX_QUERY_TIME_INTERVAL 1
+#define JX_QUERY_FIXED_SIZE 2
+#define JX_WIRE_NO_ERROR 0xFF /* host_errors[i]: no host-resolved error */
+typedef struct jx_init_req jx_init_req;
+typedef struct jx_wire_record { /* one PrepareInit: absolute offsets into the body and lengths of its fields */
+  uint64_t off, len;
+  uint64_t public_share_off, enc_off, payload_off, message_off, prep_msg_off, prep_share_off;
+  uint32_t public_share_len, enc_len, payload_len, message_len, prep_msg_len, prep_share_len;
+  uint8_t config_id, ping_pong_type, pad_[6];
+} jx_wire_record;
+typedef struct jx_init_req_info_t {
+  uint32_t status;          /* JX_WIRE_* */
+  uint32_t has_batch_id;    /* FixedSize */
+  uint64_t error_offset;    /* JX_WIRE_MALFORMED / JX_WIRE_WRONG_QUERY_TYPE */
+  uint64_t duplicate_index; /* JX_WIRE_DUPLICATE_ID */
+  uint64_t n;               /* PrepareInits (0 unless status is JX_WIRE_OK or JX_WIRE_DUPLICATE_ID) */
+  uint64_t agg_param_off, agg_param_len;
+  uint64_t fallback_iterations; /* iterations of the index's fallback loop: 0 for a uniform body */
+  uint64_t odd_public_shares;   /* reports of wire_status JX_WIRE_REPORT_ODD_PUBLIC_SHARE */
+  uint64_t enc_bytes, payload_bytes;
+  uint8_t batch_id[32];
+} jx_init_req_info_t;
+typedef struct jx_init_req_arrays_t {
+  const void *d_report_ids, *d_times, *d_public_shares, *d_leader_prep_shares, *d_encs, *d_enc_offsets, *d_payloads,
+      *d_payload_offsets, *d_key_index, *d_wire_status, *d_route, *d_records;
+  const uint64_t *times, *enc_offsets, *payload_offsets;
+  const jx_wire_record* records;
+  const uint8_t *report_ids, *key_index, *wire_status;
+} jx_init_req_arrays_t;
+int32_t jx_init_req_decode(jx_engine* e, const uint8_t* body, uint64_t len, uint32_t expected_query_type,
+                           const uint8_t key_first[256], const uint8_t key_second[256], const uint64_t* report_deadline,
+                           jx_init_req** out);
+int32_t jx_init_req_decode_device(jx_engine* e, const void* d_body, uint64_t len, uint32_t expected_query_type,
+                                  const uint8_t key_first[256], const uint8_t key_second[256],
+                                  const uint64_t* report_deadline, jx_init_req** out);
+int32_t jx_init_req_info(const jx_init_req* r, jx_init_req_info_t* out);
+/* JX_E_STATE unless the request's status is JX_WIRE_OK. */
+int32_t jx_init_req_arrays(const jx_init_req* r, jx_init_req_arrays_t* out);
+/* Route the reports with exclude[i] != 0 (a host array of n) away from every aggregation: route[i] = 0xFFFFFFFF. For
+ * reports the caller knows before the prepare call that it will not accept, such as replayed ones. */
+int32_t jx_init_req_exclude(jx_init_req* r, const uint8_t* exclude);
+/* The AggregationJobResp body of the request: per report, by the helper loop's precedence (aggregator.rs:1781-2013,
+ * :2127-2132): host_errors[i] (a PrepareError code point, JX_WIRE_NO_ERROR: none) for reports the host resolved; the
+ * open status (1: HpkeDecryptError, 2-6: InvalidMessage, 7: HpkeUnknownConfigId); a time after the decode's deadline:
+ * ReportTooEarly; wire_status 2 or 3: VdafPrepError; a verdict other than 0: VdafPrepError; replayed[i] != 0:
+ * ReportReplayed; otherwise Continue{Finish{prep_msg}}: id || 00 || u32(5 + S) || 02 || u32(S) || prep_msg[S], S the
+ * engine's prep-message length. d_verdicts, d_open_status, d_prep_msgs (rows prep_msg_stride apart, 0: S; NULL when S
+ * is 0): the device arrays the sealed calls wrote; host_errors, replayed: host arrays of n, nullable. The body goes to
+ * out (capacity bytes; 4 + n x (26 + S) always suffices, JX_E_INVALID when it does not fit), its length to *out_len,
+ * and finished[i] = 1 for exactly the reports answered with Continue (d_out_finished / out_finished, nullable). Both
+ * calls wait for their result: the length is part of it. */
+int32_t jx_init_resp_encode_device(jx_engine* e, jx_init_req* r, const void* d_verdicts, const void* d_open_status,
+                                   const void* d_prep_msgs, uint64_t prep_msg_stride, const uint8_t* host_errors,
+                                   const uint8_t* replayed, void* d_out, uint64_t capacity, uint64_t* out_len,
+                                   void* d_out_finished);
+int32_t jx_init_resp_encode(jx_engine* e, jx_init_req* r, const void* d_verdicts, const void* d_open_status,
+                            const void* d_prep_msgs, uint64_t prep_msg_stride, const uint8_t* host_errors,
+                            const uint8_t* replayed, uint8_t* out, uint64_t capacity, uint64_t* out_len,
+                            uint8_t* out_finished);
+void jx_init_req_release(jx_init_req* r);
+
 /* Accumulate the output shares of the resident batch `batch_id` (helper, or leader after finish) into
  * the engine's running batch aggregations (the engine as one shard, §8e): report i is added iff
  * verdict == FINISHED and accept_mask[i] != 0 (accept_mask nullable = all), into aggregation

@@ -28,6 +28,8 @@ EXPORTED_SYMBOLS = (
     "jx_helper_prep_aggregate_encrypted", "jx_helper_prep_aggregate_encrypted_device",
     "jx_client_shard_batch", "jx_client_shard_device", "jx_client_rand_bytes",
     "jx_client_seal_sizes", "jx_client_seal_batch", "jx_client_seal_device",
+    "jx_init_req_decode", "jx_init_req_decode_device", "jx_init_req_info", "jx_init_req_arrays", "jx_init_req_exclude",
+    "jx_init_resp_encode_device", "jx_init_resp_encode", "jx_init_req_release",
 )
 
 _lib = None
@@ -46,6 +48,29 @@ class JxMemoryStats(ctypes.Structure):
         "coalesce_enqueue_us", "coalesce_device_us", "arena_cross_stream_waits", "coalesce_pinned_bytes",
         "coalesced_helper_launches", "coalesced_helper_jobs", "coalesced_leader_launches", "coalesced_leader_jobs",
         "coalesced_encrypted_jobs", "arena_frees")]
+
+
+class JxWireRecord(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in (
+        "off", "len", "public_share_off", "enc_off", "payload_off", "message_off", "prep_msg_off", "prep_share_off")]
+    _fields_ += [(name, ctypes.c_uint32) for name in (
+        "public_share_len", "enc_len", "payload_len", "message_len", "prep_msg_len", "prep_share_len")]
+    _fields_ += [("config_id", ctypes.c_uint8), ("ping_pong_type", ctypes.c_uint8), ("pad_", ctypes.c_uint8 * 6)]
+
+
+class JxInitReqInfo(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_uint32), ("has_batch_id", ctypes.c_uint32)]
+    _fields_ += [(name, ctypes.c_uint64) for name in (
+        "error_offset", "duplicate_index", "n", "agg_param_off", "agg_param_len", "fallback_iterations",
+        "odd_public_shares", "enc_bytes", "payload_bytes")]
+    _fields_ += [("batch_id", ctypes.c_uint8 * 32)]
+
+
+class JxInitReqArrays(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "d_report_ids", "d_times", "d_public_shares", "d_leader_prep_shares", "d_encs", "d_enc_offsets", "d_payloads",
+        "d_payload_offsets", "d_key_index", "d_wire_status", "d_route", "d_records",
+        "times", "enc_offsets", "payload_offsets", "records", "report_ids", "key_index", "wire_status")]
 
 
 class EngineError(RuntimeError):
@@ -122,6 +147,14 @@ def load():
         "jx_client_seal_batch": (i32, [vp, u64, u8p, P(u64), u8p, u8p, u64, u8p, u8p, vp, vp, u8p, u8p, u8p, u8p, u8p,
                                         u8p, u8p]),
         "jx_client_seal_device": (i32, [vp, u64, vp, P(u64), vp, vp, u64, vp, u8p, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "jx_init_req_decode": (i32, [vp, u8p, u64, u32, u8p, u8p, P(u64), P(vp)]),
+        "jx_init_req_decode_device": (i32, [vp, vp, u64, u32, u8p, u8p, P(u64), P(vp)]),
+        "jx_init_req_info": (i32, [vp, P(JxInitReqInfo)]),
+        "jx_init_req_arrays": (i32, [vp, P(JxInitReqArrays)]),
+        "jx_init_req_exclude": (i32, [vp, u8p]),
+        "jx_init_resp_encode_device": (i32, [vp, vp, vp, vp, vp, u64, u8p, u8p, vp, u64, P(u64), vp]),
+        "jx_init_resp_encode": (i32, [vp, vp, vp, vp, vp, u64, u8p, u8p, u8p, u64, P(u64), u8p]),
+        "jx_init_req_release": (None, [vp]),
         "jx_engine_sync": (i32, [vp]),
         "jx_engine_stream": (i32, [vp, P(vp)]),
         "jx_engine_wait_stream": (i32, [vp, vp]),

@@ -483,6 +483,113 @@ def _open_alone(pi: PrepareInit, opener, hpke_config_id: int, globals_: dict, ta
     return PrepareError.InvalidMessage
 
 
+# ----------------------------------------------------------------------------- wire in, wire out
+
+
+class EmptyAggregation(ValueError):
+    """Error::EmptyAggregation (aggregator.rs:2017-2028): the request holds no PrepareInit."""
+
+
+def handle_aggregate_init_wire(engine: HelperEngine, body: bytes, task_id: bytes, opener, hpke_config_id: int,
+                               query_type: int, global_keypairs=None, require_taskprov: bool = False,
+                               report_deadline: int | None = None, replayed=None, segment: int = 0):
+    """The helper's aggregate-init exchange from the request body to the response body (aggregator.rs:1740-2013), with
+    no per-report host work but for reports the fixed-stride rows cannot carry: the body is decoded on the GPU
+    (engine.decode_init_req), the sealed fused call opens, prepares and aggregates from the decoded arrays with the
+    decode's route as its segment index (so a report with a wrong leader message, from after report_deadline or
+    replayed never reaches the aggregation `segment`), and the AggregationJobResp body is encoded on the GPU.
+    replayed: report ids the datastore already saw (a set of bytes), or a mask of n; they are known before the call
+    and answered with ReportReplayed unless an earlier check fails them. A malformed request raises CodecError, a
+    repeated report id ValueError (invalidMessage), a request without reports EmptyAggregation; none of them queues
+    anything. Returns (response body, finished mask, janus_step_failures counter)."""
+    import torch
+
+    from .engine import (KEY_NONE, OPEN_STATUS, WIRE_DUPLICATE_ID, WIRE_NO_ERROR, WIRE_OK, WIRE_REPORT_NOT_INITIALIZE,
+                         WIRE_REPORT_ODD_PREP_SHARE, WIRE_REPORT_ODD_PUBLIC_SHARE, WIRE_WRONG_QUERY_TYPE)
+
+    v = engine.vdaf
+    globals_ = dict(global_keypairs or {})
+    keypairs = [opener]
+    slot = {id(opener): 0}
+
+    def key_slot(k) -> int:
+        if id(k) not in slot:
+            slot[id(k)] = len(keypairs)
+            keypairs.append(k)
+        return slot[id(k)]
+
+    key_first, key_second = np.full(256, KEY_NONE, np.uint8), np.full(256, KEY_NONE, np.uint8)
+    for cfg in range(256):
+        task_k = opener if cfg == hpke_config_id else None
+        glob_k = globals_.get(cfg)
+        first, second = (task_k, glob_k) if task_k is not None else (glob_k, None)
+        if first is not None:
+            key_first[cfg] = key_slot(first)
+            if second is not None:
+                key_second[cfg] = key_slot(second)
+    if len(keypairs) > 8:
+        raise ValueError("more than JX_ENC_MAX_KEYPAIRS distinct keypairs for one task")
+    failures: Counter = Counter()
+    with engine.decode_init_req(body, query_type, key_first, key_second, report_deadline) as req:
+        if req.status == WIRE_DUPLICATE_ID:  # aggregator.rs:1750-1758
+            raise ValueError(f"aggregate request contains duplicate report IDs (invalidMessage): report {req.duplicate_index}")
+        if req.status != WIRE_OK:
+            what = "unexpected query type" if req.status == WIRE_WRONG_QUERY_TYPE else "malformed"
+            raise CodecError(f"AggregationJobInitializeReq: {what} at byte {req.error_offset}")
+        n = req.n
+        if n == 0:
+            raise EmptyAggregation("aggregation job request holds no report")
+        ws = req.wire_status
+        host_err = None
+        odd = np.nonzero(ws == WIRE_REPORT_ODD_PUBLIC_SHARE)[0]
+        if odd.size:  # the reports the rows cannot carry: the reference's checks on the host, from the body's bytes
+            host_err = np.full(n, WIRE_NO_ERROR, np.uint8)
+            for i in odd:
+                rec = req.records[i]
+                pi = PrepareInit.decode(body[int(rec["off"]):int(rec["off"]) + int(rec["len"])])
+                host_err[i] = int(_open_alone(pi, opener, hpke_config_id, globals_, task_id, v, require_taskprov, failures))
+        rep = None
+        if replayed is not None and not isinstance(replayed, (set, frozenset)):
+            rep = np.asarray(replayed).astype(bool).reshape(n)
+        elif replayed:
+            rep = np.fromiter((r.tobytes() in replayed for r in req.report_ids), bool, n)
+        if rep is not None and rep.any():
+            req.exclude(rep)
+        dev = torch.device("cuda", engine.device)
+        with torch.cuda.device(dev):
+            d_v = torch.zeros(n, dtype=torch.uint8, device=dev)
+            d_st = torch.zeros(n, dtype=torch.uint8, device=dev)
+            d_m = torch.zeros((n, max(engine.prep_msg_len, 1)), dtype=torch.uint8, device=dev)
+            a = req.d
+            engine.prep_and_aggregate_encrypted_device(
+                a.d_report_ids, req.times, a.d_public_shares, task_id, keypairs, req.key_index, a.d_encs, a.d_payloads,
+                req.payload_offsets, a.d_leader_prep_shares, n, enc_offsets=req.enc_offsets,
+                require_taskprov=require_taskprov, d_out_prep_msgs=d_m.data_ptr() if engine.prep_msg_len else None,
+                d_out_verdicts=d_v.data_ptr(), d_out_open_status=d_st.data_ptr(), d_segments=a.d_route,
+                segment_ids=[segment])
+            out, finished = engine.encode_init_resp(req, d_v.data_ptr(), d_st.data_ptr(),
+                                                    d_m.data_ptr() if engine.prep_msg_len else None, host_err, rep,
+                                                    prep_msg_stride=max(engine.prep_msg_len, 1) if engine.prep_msg_len else 0)
+            st, vd = d_st.cpu().numpy(), d_v.cpu().numpy()
+        # the counters, by the same precedence, whole arrays at a time
+        live = ws != WIRE_REPORT_ODD_PUBLIC_SHARE
+        for code, cnt in enumerate(np.bincount(st[live & (st != 0)], minlength=8)):
+            if cnt:
+                failures[OPEN_STATUS[code][0]] += int(cnt)
+        rest = live & (st == 0)
+        if report_deadline is not None:
+            rest &= req.times <= np.uint64(report_deadline)
+        for code, label in ((WIRE_REPORT_NOT_INITIALIZE, "leader_ping_pong_message_mismatch"),
+                            (WIRE_REPORT_ODD_PREP_SHARE, "leader_prep_share_decode_failure")):
+            cnt = int((rest & (ws == code)).sum())
+            if cnt:
+                failures[label] += cnt
+        for code, cnt in enumerate(np.bincount(vd[rest & (ws == 0) & (vd != FINISHED)], minlength=1)):
+            if cnt:
+                failures[VERDICT_LABELS[code]] += int(cnt)
+    return out, finished, failures
+
+
 # ----------------------------------------------------------------------------- upload (leader)
 
 

@@ -1,6 +1,6 @@
 // jx_engine_internal.h — engine internals shared by the engine's host sources: jx_engine.cpp (staging, resident
 // batches, the K1 -> K3 sequencing, the ABI's lifetime and plumbing calls), the call families jx_engine_cfg.cpp,
-// _prep.cpp, _acc.cpp, _fused.cpp, _upload.cpp and _shard.cpp, jx_arena.cpp (the per-device memory arena) and
+// _prep.cpp, _acc.cpp, _fused.cpp, _upload.cpp, _shard.cpp, _seal.cpp and _wire.cpp, jx_arena.cpp (the per-device memory arena) and
 // jx_coalesce.cpp (the per-device job coalescer). Not part of the ABI: include/jx_prio3.h is.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -329,6 +329,9 @@ struct jx_engine {
   uint32_t* d_err = nullptr;  // combine kernels: non-canonical input seen (reported by jx_engine_sync)
   uint4* d_shard_tab = nullptr;  // jx_client_shard_*: the prover's transform table (jx_ntt.h), made by the first call
   uint64_t seal_chunk = 0;       // reports per launch of jx_client_seal_* (debug option 11; 0: automatic)
+  // jx_init_req_decode*: the key of the duplicate check's slot hash, drawn once per engine (jx_engine_wire.cpp)
+  uint64_t wire_key[2] = {0, 0};
+  bool wire_key_set = false;
   uint64_t shard_chunk = 0;      // reports per launch of jx_client_shard_* (debug option 10; 0: by the scratch budget)
   // timing
   bool timing = false;

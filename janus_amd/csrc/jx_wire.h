@@ -1,0 +1,398 @@
+// jx_wire.h — the framing rule of the DAP aggregate-init exchange, once: how an AggregationJobInitializeReq body is
+// cut into its header and its PrepareInits, and how long the PrepareResps of the answer are.
+//
+// The rule is wire_parse_prepare_init: one PrepareInit at a byte offset, every read checked against the end of the
+// prepare_inits vector, all offsets and sums in 64 bits (a u32 length near 2^32 must not wrap). Three callers walk a
+// body with it: the sequential host walk wire_walk (what a host decoder does, and what the kernels are tested
+// against), the index kernels of jx_wire.hip (a candidate offset that is not a true boundary reads garbage lengths:
+// the bounds checks are what makes that harmless), and wire_gallop_lane, a lane of one iteration of the fallback loop, which the
+// kernel runs with one candidate per lane and tests/csrc/hosttest_wire.cpp replays on the CPU one candidate per loop
+// iteration. __host__ __device__ and without HIP calls.
+#pragma once
+#include <stdint.h>
+
+#include "jx_field.h"
+
+namespace jx {
+
+// request status (jx_init_req_info: JX_WIRE_*)
+enum : uint32_t { WIRE_OK = 0, WIRE_MALFORMED = 1, WIRE_WRONG_QUERY_TYPE = 2, WIRE_DUPLICATE_ID = 3 };
+// per-report status (wire_status[n])
+enum : uint8_t { WIRE_REPORT_OK = 0, WIRE_REPORT_ODD_PUBLIC_SHARE = 1, WIRE_REPORT_NOT_INITIALIZE = 2, WIRE_REPORT_ODD_PREP_SHARE = 3 };
+enum : uint8_t { WIRE_QUERY_TIME_INTERVAL = 1, WIRE_QUERY_FIXED_SIZE = 2 };
+// PrepareError code points (messages/src/lib.rs:2338-2349) the response encoder writes
+enum : uint8_t {
+  WIRE_ERR_REPORT_REPLAYED = 1, WIRE_ERR_UNKNOWN_CONFIG = 3, WIRE_ERR_DECRYPT = 4, WIRE_ERR_VDAF_PREP = 5,
+  WIRE_ERR_INVALID_MESSAGE = 8, WIRE_ERR_TOO_EARLY = 9, WIRE_ERR_NONE = 0xFF
+};
+constexpr uint64_t WIRE_MIN_PREPARE_INIT = 16 + 8 + 4 + 1 + 2 + 4 + 4 + 1 + 4;  // every field empty, a one-field message
+constexpr uint32_t WIRE_LANES = 64;  // candidates one iteration of the fallback loop tests
+
+// One PrepareInit of a body: absolute byte offsets and lengths of its fields. The report id is at off, the time at
+// off + 16. A ping-pong field the message's type does not carry has length 0 and the offset where it would start.
+struct WireRec {
+  uint64_t off, len;          // the whole PrepareInit
+  uint64_t ps_off, enc_off, pay_off, msg_off, pm_off, sh_off;
+  uint32_t ps_len, enc_len, pay_len, msg_len, pm_len, sh_len;
+  uint8_t config_id, pp_type, pad_[6];
+};
+static_assert(sizeof(WireRec) == 96, "WireRec is copied to the host as bytes");
+
+struct WireHeader {
+  uint32_t status;            // WIRE_OK, WIRE_MALFORMED or WIRE_WRONG_QUERY_TYPE
+  uint32_t has_batch_id;
+  uint64_t err_off;           // the read that failed
+  uint64_t param_off, param_len;
+  uint64_t start, end;        // the prepare_inits vector: [start, end), end == the body's length
+  uint64_t l0;                // the first PrepareInit's length (0: none, or it does not parse)
+  uint8_t batch_id[32];
+};
+
+JX_HD uint32_t wire_be32(const uint8_t* p) {
+  return ((uint32_t)p[0] << 24) | ((uint32_t)p[1] << 16) | ((uint32_t)p[2] << 8) | (uint32_t)p[3];
+}
+JX_HD uint64_t wire_be64(const uint8_t* p) { return ((uint64_t)wire_be32(p) << 32) | wire_be32(p + 4); }
+JX_HD void wire_put32(uint8_t* p, uint32_t v) {
+  p[0] = (uint8_t)(v >> 24);
+  p[1] = (uint8_t)(v >> 16);
+  p[2] = (uint8_t)(v >> 8);
+  p[3] = (uint8_t)v;
+}
+
+// A cursor over body[.., lim): pos <= lim always, so `lim - pos` never wraps and no sum of a position and a length is
+// formed before it is known to fit. A failed read leaves pos at the read that failed.
+struct WireCur {
+  const uint8_t* b;
+  uint64_t pos, lim;
+  bool ok;
+};
+JX_HD bool wire_need(WireCur& c, uint64_t n) {
+  if (c.ok && c.lim - c.pos < n) c.ok = false;
+  return c.ok;
+}
+JX_HD uint32_t wire_u8(WireCur& c) {
+  if (!wire_need(c, 1)) return 0;
+  return c.b[c.pos++];
+}
+JX_HD uint32_t wire_u16(WireCur& c) {
+  if (!wire_need(c, 2)) return 0;
+  const uint32_t v = ((uint32_t)c.b[c.pos] << 8) | c.b[c.pos + 1];
+  c.pos += 2;
+  return v;
+}
+JX_HD uint32_t wire_u32(WireCur& c) {
+  if (!wire_need(c, 4)) return 0;
+  const uint32_t v = wire_be32(c.b + c.pos);
+  c.pos += 4;
+  return v;
+}
+// a length prefix of `width` bytes and its bytes: where they start and how many
+JX_HD void wire_opaque(WireCur& c, int width, uint64_t& off, uint32_t& len) {
+  const uint64_t at = c.pos;
+  const uint32_t l = width == 2 ? wire_u16(c) : wire_u32(c);
+  off = c.pos;
+  len = l;
+  if (!c.ok) return;
+  if (!wire_need(c, l)) {
+    c.pos = at;  // the read that failed is the opaque as a whole
+    return;
+  }
+  c.pos += l;
+}
+
+// The PrepareInit at byte `off` of body, which ends at `lim` (off <= lim). False: it does not parse, *err_off is the
+// read that failed (an unknown ping-pong type: the type byte; bytes left over inside the message: the first of them).
+JX_HD bool wire_parse_prepare_init(const uint8_t* body, uint64_t lim, uint64_t off, WireRec& r, uint64_t* err_off) {
+  WireCur c{body, off, lim, true};
+  r = WireRec{};
+  r.off = off;
+  if (wire_need(c, 24)) c.pos += 24;  // report id, time
+  wire_opaque(c, 4, r.ps_off, r.ps_len);
+  r.config_id = (uint8_t)wire_u8(c);
+  wire_opaque(c, 2, r.enc_off, r.enc_len);
+  wire_opaque(c, 4, r.pay_off, r.pay_len);
+  wire_opaque(c, 4, r.msg_off, r.msg_len);
+  if (!c.ok) {
+    *err_off = c.pos;
+    return false;
+  }
+  r.len = c.pos - off;
+  // the message's bytes are exactly one PingPongMessage
+  WireCur m{body, r.msg_off, r.msg_off + r.msg_len, true};
+  const uint64_t type_at = m.pos;
+  r.pp_type = (uint8_t)wire_u8(m);
+  if (m.ok && r.pp_type > 2) {
+    *err_off = type_at;
+    return false;
+  }
+  r.pm_off = r.sh_off = m.pos;
+  if (r.pp_type >= 1) wire_opaque(m, 4, r.pm_off, r.pm_len);
+  if (r.pp_type == 1) wire_opaque(m, 4, r.sh_off, r.sh_len);
+  else r.sh_off = m.pos;
+  if (r.pp_type == 0) {
+    wire_opaque(m, 4, r.sh_off, r.sh_len);
+    r.pm_off = r.sh_off;
+  }
+  if (!m.ok || m.pos != m.lim) {
+    *err_off = m.pos;
+    return false;
+  }
+  return true;
+}
+
+// The request header: u32 + aggregation parameter, the PartialBatchSelector of the task's query type, the u32 byte
+// length of the prepare_inits vector, which must end where the body ends. l0: the first PrepareInit's length.
+JX_HD void wire_parse_header(const uint8_t* body, uint64_t len, uint32_t query_type, WireHeader& h) {
+  h = WireHeader{};
+  WireCur c{body, 0, len, true};
+  uint32_t pl = 0;
+  wire_opaque(c, 4, h.param_off, pl);
+  h.param_len = pl;
+  const uint64_t q_at = c.pos;
+  const uint32_t q = wire_u8(c);
+  if (c.ok && q != query_type) {
+    h.status = WIRE_WRONG_QUERY_TYPE;
+    h.err_off = q_at;
+    return;
+  }
+  if (query_type == WIRE_QUERY_FIXED_SIZE && wire_need(c, 32)) {
+    for (int i = 0; i < 32; i++) h.batch_id[i] = body[c.pos + i];
+    h.has_batch_id = 1;
+    c.pos += 32;
+  }
+  uint32_t vl = 0;
+  wire_opaque(c, 4, h.start, vl);
+  if (!c.ok) {
+    h.status = WIRE_MALFORMED;
+    h.err_off = c.pos;
+    return;
+  }
+  h.end = h.start + vl;
+  if (h.end != len) {  // bytes after the vector
+    h.status = WIRE_MALFORMED;
+    h.err_off = h.end;
+    return;
+  }
+  WireRec r;
+  uint64_t eo;
+  if (h.start < h.end && wire_parse_prepare_init(body, h.end, h.start, r, &eo)) h.l0 = r.len;
+}
+
+// One iteration of the fallback loop from the true boundary `off` < end. The stride is re-learnt as a pair: la, the
+// length of the message at off, and lb, the length of the message before it (la again when there is none), so that a
+// body whose lengths alternate (two KEMs' encapsulated keys, say) still moves a wave's worth per iteration. Lane k
+// tests candidate k: it lies at off + (k / 2) (la + lb) + (k odd: la), must parse inside [.., end) and must have the
+// length the pattern expects there (la for even k, lb for odd k). The candidates up to the first that fails are
+// accepted: each one starts where the one before it ends, so by induction every accepted candidate is a true boundary,
+// and so is the first that fails when it only has another length: the next iteration starts there. The fast pass is
+// the same test with la == lb == l0 and as many lanes as candidates. The decision of lane k, as the kernel's lanes and
+// the CPU replay take it; *at: where the candidate lies (when it lies inside the body).
+JX_HD bool wire_gallop_lane(const uint8_t* body, uint64_t end, uint64_t off, uint64_t la, uint64_t lb, uint64_t k,
+                            uint64_t* at) {
+  *at = off;
+  if (k == 0) return true;
+  const uint64_t pair = la + lb, pairs = k / 2;
+  if ((end - off) / pair < pairs) return false;  // off + pairs * pair would pass the end (and cannot wrap)
+  uint64_t p = off + pairs * pair;
+  if (k & 1) {
+    if (end - p < la) return false;
+    p += la;
+  }
+  if (p >= end) return false;
+  *at = p;
+  WireRec r;
+  uint64_t eo;
+  return wire_parse_prepare_init(body, end, p, r, &eo) && r.len == ((k & 1) ? lb : la);
+}
+
+// ---- the response: a PrepareResp is id || 00 || u32(5 + S) || 02 || u32(S) || prep_msg[S] when the report finished
+// (S: the engine's prep-message length), id || 02 || error otherwise; the AggregationJobResp is u32 + the items.
+JX_HD uint32_t wire_resp_len(bool finished, uint32_t S) { return finished ? 16 + 1 + 4 + 1 + 4 + S : 18; }
+
+// The outcome of report i by the helper loop's precedence: the PrepareError to answer with, or WIRE_ERR_NONE when the
+// report finished. host_err: a host-resolved error (WIRE_ERR_NONE: none); open: JX_OPEN_*; too_early: its time is after
+// the deadline; wire: wire_status; verdict: the engine's; replayed: the datastore saw the id before.
+JX_HD uint8_t wire_outcome(uint8_t host_err, uint8_t open, bool too_early, uint8_t wire, uint8_t verdict, bool replayed) {
+  if (host_err != WIRE_ERR_NONE) return host_err;
+  if (open == 1) return WIRE_ERR_DECRYPT;
+  if (open == 7) return WIRE_ERR_UNKNOWN_CONFIG;
+  if (open != 0) return WIRE_ERR_INVALID_MESSAGE;
+  if (too_early) return WIRE_ERR_TOO_EARLY;
+  if (wire == WIRE_REPORT_NOT_INITIALIZE || wire == WIRE_REPORT_ODD_PREP_SHARE) return WIRE_ERR_VDAF_PREP;
+  if (verdict != 0) return WIRE_ERR_VDAF_PREP;
+  if (replayed) return WIRE_ERR_REPORT_REPLAYED;
+  return WIRE_ERR_NONE;
+}
+
+// ---- the duplicate check's slot hash: SipHash-2-4 of the 16-byte id under a per-engine 128-bit key
+JX_HD uint64_t wire_rotl(uint64_t x, int b) { return (x << b) | (x >> (64 - b)); }
+JX_HD uint64_t wire_le64(const uint8_t* p) {
+  uint64_t v = 0;
+  for (int i = 7; i >= 0; i--) v = (v << 8) | p[i];
+  return v;
+}
+JX_HD uint64_t wire_id_hash(const uint8_t id[16], uint64_t k0, uint64_t k1) {
+  uint64_t v0 = k0 ^ 0x736f6d6570736575ull, v1 = k1 ^ 0x646f72616e646f6dull, v2 = k0 ^ 0x6c7967656e657261ull,
+           v3 = k1 ^ 0x7465646279746573ull;
+#define JX_SIPROUND                                  \
+  do {                                               \
+    v0 += v1; v1 = wire_rotl(v1, 13); v1 ^= v0; v0 = wire_rotl(v0, 32); \
+    v2 += v3; v3 = wire_rotl(v3, 16); v3 ^= v2;      \
+    v0 += v3; v3 = wire_rotl(v3, 21); v3 ^= v0;      \
+    v2 += v1; v1 = wire_rotl(v1, 17); v1 ^= v2; v2 = wire_rotl(v2, 32); \
+  } while (0)
+  const uint64_t m[3] = {wire_le64(id), wire_le64(id + 8), 16ull << 56};
+  for (int i = 0; i < 3; i++) {
+    v3 ^= m[i];
+    JX_SIPROUND;
+    JX_SIPROUND;
+    v0 ^= m[i];
+  }
+  v2 ^= 0xff;
+  JX_SIPROUND;
+  JX_SIPROUND;
+  JX_SIPROUND;
+  JX_SIPROUND;
+#undef JX_SIPROUND
+  return v0 ^ v1 ^ v2 ^ v3;
+}
+
+// The whole index as the kernels compute it, one loop iteration per lane: the fast pass over every candidate at
+// start + i * l0 (the kernel takes the minimum of the failing i with one atomic), then the fallback loop. iters: the
+// fallback's iterations (0 for a uniform body).
+struct WireIndex {
+  uint32_t status;
+  uint32_t iters;
+  uint64_t err_off;
+  uint64_t n;
+  uint64_t nfast;  // boundaries the fast pass accepted: message i < nfast starts at start + i * l0
+};
+JX_HD uint32_t wire_gallop_accept(const uint8_t* body, uint64_t end, uint64_t off, uint64_t la, uint64_t lb) {
+  uint32_t m = 1;
+  uint64_t at;
+  while (m < WIRE_LANES && wire_gallop_lane(body, end, off, la, lb, m, &at)) m++;
+  return m;
+}
+// offs (nullable): offs[j] takes the start of message nfast + j, for up to cap of them
+inline WireIndex wire_index_replay(const uint8_t* body, const WireHeader& h, uint64_t* offs, uint64_t cap) {
+  WireIndex x{h.status, 0, h.err_off, 0, 0};
+  if (h.status != WIRE_OK || h.start == h.end) return x;
+  uint64_t off = h.start, at;
+  if (h.l0) {
+    const uint64_t cands = (h.end - h.start) / h.l0;
+    uint64_t bad = cands;
+    for (uint64_t i = 0; i < cands; i++)
+      if (!wire_gallop_lane(body, h.end, h.start, h.l0, h.l0, i, &at)) {
+        bad = i;
+        break;
+      }
+    x.nfast = x.n = bad;
+    off = h.start + bad * h.l0;
+  }
+  uint64_t prev = x.nfast ? h.l0 : 0;  // the length of the message before off (0: there is none)
+  while (off < h.end) {
+    WireRec r;
+    if (!wire_parse_prepare_init(body, h.end, off, r, &x.err_off)) {
+      x.status = WIRE_MALFORMED;
+      return x;
+    }
+    const uint64_t la = r.len, lb = prev ? prev : r.len;
+    const uint32_t m = wire_gallop_accept(body, h.end, off, la, lb);
+    for (uint32_t k = 0; k < m; k++) {
+      (void)wire_gallop_lane(body, h.end, off, la, lb, k, &at);
+      if (offs && x.n - x.nfast + k < cap) offs[x.n - x.nfast + k] = at;
+    }
+    x.n += m;
+    off += (uint64_t)(m / 2) * (la + lb) + ((m & 1) ? la : 0);
+    prev = (m & 1) ? la : lb;  // the last accepted message is candidate m - 1
+    x.iters++;
+  }
+  return x;
+}
+
+// ---- the sequential walk: the host decoder's pass, and the reference the kernels are compared with
+struct WireWalk {
+  uint32_t status;
+  uint64_t err_off;
+  uint64_t n;
+};
+// recs (nullable) takes up to cap records
+inline WireWalk wire_walk(const uint8_t* body, const WireHeader& h, WireRec* recs, uint64_t cap) {
+  WireWalk w{h.status, h.err_off, 0};
+  if (h.status != WIRE_OK) return w;
+  uint64_t off = h.start;
+  while (off < h.end) {
+    WireRec r;
+    if (!wire_parse_prepare_init(body, h.end, off, r, &w.err_off)) {
+      w.status = WIRE_MALFORMED;
+      return w;
+    }
+    if (recs && w.n < cap) recs[w.n] = r;
+    w.n++;
+    off += r.len;
+  }
+  return w;
+}
+
+// ---- what the kernels of jx_wire.hip and the engine (jx_engine_wire.cpp) share
+constexpr uint32_t WIRE_NO_DUPLICATE = 0xFFFFFFFFu;
+
+// One decode's state on the device, zeroed before the header kernel; the host reads it back between the phases.
+struct WireState {
+  WireHeader hdr;
+  unsigned long long first_bad;  // the fast pass: the lowest candidate index that failed (~0: none)
+  uint64_t n, nfast, err_off;
+  uint64_t enc_total, pay_total;
+  uint32_t status, iters;
+  uint32_t dup;     // the lowest index with an equal id at a lower index (WIRE_NO_DUPLICATE: none)
+  uint32_t odd_ps;  // reports of wire_status 1
+};
+
+struct WireDecodeArgs {
+  const uint8_t* body;
+  uint64_t n, nfast, start, end, l0;
+  const uint64_t* offs;  // the starts of messages nfast.. (null when nfast == n)
+  uint32_t ps_bytes, lps_bytes;
+  uint32_t has_deadline;
+  uint64_t deadline;
+  const uint8_t *key_first, *key_second;  // [256] each: config id -> keypair index
+  WireState* st;
+  WireRec* recs;
+  uint64_t* times;
+  uint8_t *wire_status, *key_index;
+  uint32_t* route;
+  uint64_t *enc_offsets, *payload_offsets;
+  uint8_t *ids, *ps, *lps, *encs, *payloads;
+};
+
+struct WireEncodeArgs {
+  uint64_t n;
+  const uint8_t* ids;
+  const uint64_t* times;
+  const uint8_t *wire_status, *verdicts, *open_status, *prep_msgs;
+  const uint8_t *host_err, *replayed;  // nullable
+  uint32_t prep_msg_bytes, prep_msg_stride;
+  uint32_t has_deadline;
+  uint64_t deadline;
+  uint8_t *err, *finished;  // [n]
+  uint64_t* offsets;        // [n + 1]: PrepareResp i at 4 + offsets[i] of out
+  uint8_t* out;
+};
+
+#if defined(__HIPCC__) || defined(__HIP__)
+hipError_t launch_wire_header(const uint8_t* body, uint64_t len, uint32_t query_type, WireState* st, hipStream_t s);
+// the fast pass over `cands` candidates (fast: not yet run for this body) and the fallback loop; offs / cap: where the
+// starts of the messages the fallback accepts go (null: only count them)
+hipError_t launch_wire_index(const uint8_t* body, WireState* st, uint64_t cands, bool fast, uint64_t* offs, uint64_t cap,
+                             hipStream_t s);
+// records and per-report scalars, the duplicate check (dup_tab: `slots` zeroed words; dup_result: WIRE_NO_DUPLICATE)
+// and the two scans
+hipError_t launch_wire_records(const WireDecodeArgs& a, uint32_t* dup_tab, uint64_t slots, uint32_t* dup_result, uint64_t k0,
+                               uint64_t k1, hipStream_t s);
+hipError_t launch_wire_gather(const WireDecodeArgs& a, hipStream_t s);
+hipError_t launch_wire_exclude(uint32_t* route, const uint8_t* mask, uint64_t n, hipStream_t s);
+hipError_t launch_wire_encode_sizes(const WireEncodeArgs& a, hipStream_t s);
+hipError_t launch_wire_encode_pack(const WireEncodeArgs& a, hipStream_t s);
+#endif
+
+}  // namespace jx

@@ -1,0 +1,328 @@
+// jx_wire.hip — the aggregate-init request decoded and its response encoded on the device (the rule: jx_wire.h).
+//
+// Decode: wire_header_kernel reads the header and the first PrepareInit's length l0. wire_fast_kernel tests the
+// candidate boundary start + i * l0 in lane i of many workgroups and takes the lowest failing i with one agent-scope
+// atomicMin; nothing else crosses workgroups, and the minimum is read by the next kernel, behind the kernel boundary.
+// Every candidate below it has length l0 and starts where its predecessor ends, so by induction it is a true
+// boundary. wire_gallop_kernel (one wave) continues from there for a body that is not uniform to the end, a pair of
+// alternating lengths at a time. Then one thread per report writes its record and scalars, the duplicate check claims
+// hash slots, one workgroup scans the encapsulated-key and payload lengths, and one wave per report copies its fields
+// into the rows the prepare calls read.
+//
+// Encode: one thread per report decides its outcome (wire_outcome) and length, one workgroup scans the lengths, one
+// thread per report writes its PrepareResp.
+#include <hip/hip_runtime.h>
+
+#include "../../include/jx_prio3.h"
+#include "jx_wire.h"
+
+namespace jx {
+namespace {
+
+__global__ void wire_header_kernel(const uint8_t* body, uint64_t len, uint32_t query_type, WireState* st) {
+  if (blockIdx.x | threadIdx.x) return;
+  WireHeader h;
+  wire_parse_header(body, len, query_type, h);
+  st->hdr = h;
+  st->first_bad = ~0ull;
+  st->status = h.status;
+  st->err_off = h.err_off;
+  st->dup = WIRE_NO_DUPLICATE;
+}
+
+__global__ __launch_bounds__(256) void wire_fast_kernel(const uint8_t* body, WireState* st, uint64_t cands) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const WireHeader& h = st->hdr;
+  uint64_t at;
+  const bool bad = i < cands && !wire_gallop_lane(body, h.end, h.start, h.l0, h.l0, i, &at);
+  // one atomic per wave: its lowest failing lane's index
+  const unsigned long long m = __ballot(bad);
+  if (bad && (threadIdx.x & 63u) == (uint32_t)__ffsll((long long)m) - 1u)
+    __hip_atomic_fetch_min(&st->first_bad, (unsigned long long)i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// One wave. offs (nullable): the start of message nfast + j for j < cap. Every lane holds the same off / n / iters.
+__global__ __launch_bounds__(64) void wire_gallop_kernel(const uint8_t* body, WireState* st, uint64_t cands, uint64_t* offs,
+                                                         uint64_t cap) {
+  const uint32_t lane = threadIdx.x;
+  const WireHeader h = st->hdr;
+  uint64_t nfast = 0, off = h.start;
+  if (h.l0) {
+    const uint64_t fb = st->first_bad;  // the fast pass's, complete behind the kernel boundary
+    nfast = fb < cands ? fb : cands;
+    off = h.start + nfast * h.l0;
+  }
+  uint64_t n = nfast, err = 0, prev = nfast ? h.l0 : 0;  // prev: the length of the message before off (0: none)
+  uint32_t iters = 0, status = WIRE_OK;
+  while (off < h.end) {
+    WireRec r;
+    if (!wire_parse_prepare_init(body, h.end, off, r, &err)) {
+      status = WIRE_MALFORMED;
+      break;
+    }
+    const uint64_t la = r.len, lb = prev ? prev : r.len;
+    uint64_t at;
+    const bool ok = wire_gallop_lane(body, h.end, off, la, lb, lane, &at);
+    const unsigned long long bad = ~__ballot(ok);
+    const uint32_t m = bad ? (uint32_t)__ffsll((long long)bad) - 1u : WIRE_LANES;  // lane 0 is always accepted: m >= 1
+    if (offs && lane < m && n - nfast + lane < cap) offs[n - nfast + lane] = at;
+    n += m;
+    off += (uint64_t)(m / 2) * (la + lb) + ((m & 1u) ? la : 0);
+    prev = (m & 1u) ? la : lb;  // the last accepted message is candidate m - 1
+    iters++;
+  }
+  if (lane == 0) {
+    st->n = n;
+    st->nfast = nfast;
+    st->iters = iters;
+    st->status = status;
+    st->err_off = err;
+  }
+}
+
+__global__ __launch_bounds__(256) void wire_records_kernel(WireDecodeArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  const uint64_t off = i < a.nfast ? a.start + i * a.l0 : a.offs[i - a.nfast];
+  WireRec r;
+  uint64_t eo;
+  (void)wire_parse_prepare_init(a.body, a.end, off, r, &eo);  // a true boundary: it parsed when it was accepted
+  a.recs[i] = r;
+  const uint64_t t = wire_be64(a.body + off + 16);
+  a.times[i] = t;
+  uint8_t ws = WIRE_REPORT_OK;
+  if (r.ps_len != a.ps_bytes) ws = WIRE_REPORT_ODD_PUBLIC_SHARE;
+  else if (r.pp_type != 0) ws = WIRE_REPORT_NOT_INITIALIZE;
+  else if (r.sh_len != a.lps_bytes) ws = WIRE_REPORT_ODD_PREP_SHARE;
+  a.wire_status[i] = ws;
+  const bool odd = ws == WIRE_REPORT_ODD_PUBLIC_SHARE;
+  a.key_index[2 * i] = odd ? (uint8_t)JX_KEY_NONE : a.key_first[r.config_id];
+  a.key_index[2 * i + 1] = odd ? (uint8_t)JX_KEY_NONE : a.key_second[r.config_id];
+  a.route[i] = (ws != WIRE_REPORT_OK || (a.has_deadline && t > a.deadline)) ? 0xFFFFFFFFu : 0u;
+  if (odd) atomicAdd(&a.st->odd_ps, 1u);
+}
+
+// ---- duplicate report ids. tab: 2n slots, zeroed; a slot holds index + 1. A report walks its probe chain from its
+// keyed hash: an empty slot is claimed with a compare-exchange; an occupied one names its holder in the value the
+// atomic returned, and the two ids are compared in the body, the kernel's input, never in anything this launch
+// writes. Equal ids: the slot keeps the lower index (atomicMin), and what the atomicMin returns is an index with the
+// same id, so max(i, that) has an equal id at a lower index. The atomics of one slot are totally ordered, so whichever
+// of the two lowest members of a set of equal ids comes second reports the higher of them: the minimum over the
+// reports is the lowest index with an earlier equal id.
+__device__ bool wire_id_equal(const uint8_t* a, const uint8_t* b) {
+  uint32_t d = 0;
+  for (int k = 0; k < 16; k++) d |= (uint32_t)(a[k] ^ b[k]);
+  return d == 0;
+}
+
+__global__ __launch_bounds__(256) void wire_dup_kernel(const uint8_t* body, const WireRec* recs, uint64_t n, uint32_t* tab,
+                                                       uint64_t slots, uint64_t k0, uint64_t k1, uint32_t* result) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const uint8_t* id = body + recs[i].off;
+  uint64_t s = wire_id_hash(id, k0, k1) % slots;
+  for (uint64_t probes = 0; probes < slots; probes++) {
+    uint32_t seen = 0;
+    if (__hip_atomic_compare_exchange_strong(&tab[s], &seen, (uint32_t)i + 1u, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT))
+      return;  // claimed
+    if (wire_id_equal(id, body + recs[seen - 1u].off)) {
+      const uint32_t before = __hip_atomic_fetch_min(&tab[s], (uint32_t)i + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const uint32_t j = before - 1u;
+      if (j != (uint32_t)i)
+        __hip_atomic_fetch_min(result, j > (uint32_t)i ? j : (uint32_t)i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return;
+    }
+    s = s + 1 == slots ? 0 : s + 1;
+  }
+}
+
+// the second kernel: the result, complete behind the kernel boundary, into the state the host reads
+__global__ void wire_dup_read_kernel(const uint32_t* result, WireState* st) {
+  if (blockIdx.x | threadIdx.x) return;
+  st->dup = *result;
+}
+
+// ---- exclusive scan by one workgroup of 1024: out[i] = sum of load(j) for j < i, out[n] the total
+template <class F>
+__device__ void block_exclusive_scan(uint64_t n, F load, uint64_t* out) {
+  __shared__ uint64_t wsum[16];
+  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
+  uint64_t carry = 0;
+  for (uint64_t base = 0; base < n; base += 1024) {
+    const uint64_t i = base + t;
+    const uint64_t v = i < n ? load(i) : 0;
+    uint64_t x = v;
+    for (int d = 1; d < 64; d <<= 1) {
+      const uint64_t y = __shfl_up((unsigned long long)x, d);
+      if (lane >= (uint32_t)d) x += y;
+    }
+    if (lane == 63) wsum[w] = x;
+    __syncthreads();
+    uint64_t pre = 0, total = 0;
+    for (uint32_t k = 0; k < 16; k++) {
+      if (k < w) pre += wsum[k];
+      total += wsum[k];
+    }
+    if (i < n) out[i] = carry + pre + x - v;
+    carry += total;
+    __syncthreads();
+  }
+  if (t == 0) out[n] = carry;
+}
+
+__global__ __launch_bounds__(1024) void wire_scan_kernel(const WireRec* recs, uint64_t n, uint64_t* enc_offsets,
+                                                         uint64_t* payload_offsets, WireState* st) {
+  block_exclusive_scan(n, [&](uint64_t i) { return (uint64_t)recs[i].enc_len; }, enc_offsets);
+  block_exclusive_scan(n, [&](uint64_t i) { return (uint64_t)recs[i].pay_len; }, payload_offsets);
+  if (threadIdx.x == 0) {
+    st->enc_total = enc_offsets[n];
+    st->pay_total = payload_offsets[n];
+  }
+}
+
+// len bytes from src (any alignment) to dst by one wave: bytes up to dst's 16-byte boundary, 16 bytes per lane, the tail
+__device__ void wave_copy(uint8_t* dst, const uint8_t* src, uint64_t len, uint32_t lane) {
+  uint64_t head = (16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15;
+  if (head > len) head = len;
+  if (lane < head) dst[lane] = src[lane];
+  dst += head;
+  src += head;
+  len -= head;
+  const uint64_t nv = len / 16;
+  for (uint64_t v = lane; v < nv; v += 64) {
+    uint4 x;
+    __builtin_memcpy(&x, src + 16 * v, 16);
+    *reinterpret_cast<uint4*>(dst + 16 * v) = x;
+  }
+  const uint64_t t0 = nv * 16;
+  if (lane < len - t0) dst[t0 + lane] = src[t0 + lane];
+}
+
+__global__ __launch_bounds__(256) void wire_gather_kernel(WireDecodeArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63u;
+  if (i >= a.n) return;
+  const WireRec r = a.recs[i];
+  if (lane < 16) a.ids[16 * i + lane] = a.body[r.off + lane];
+  if (a.ps_bytes) {
+    uint8_t* row = a.ps + i * a.ps_bytes;
+    if (r.ps_len == a.ps_bytes) wave_copy(row, a.body + r.ps_off, a.ps_bytes, lane);
+    else for (uint32_t b = lane; b < a.ps_bytes; b += 64) row[b] = 0;
+  }
+  {
+    uint8_t* row = a.lps + i * a.lps_bytes;
+    if (r.pp_type == 0 && r.sh_len == a.lps_bytes) wave_copy(row, a.body + r.sh_off, a.lps_bytes, lane);
+    else for (uint32_t b = lane; b < a.lps_bytes; b += 64) row[b] = 0;
+  }
+  wave_copy(a.encs + a.enc_offsets[i], a.body + r.enc_off, r.enc_len, lane);
+  wave_copy(a.payloads + a.payload_offsets[i], a.body + r.pay_off, r.pay_len, lane);
+}
+
+__global__ __launch_bounds__(256) void wire_exclude_kernel(uint32_t* route, const uint8_t* mask, uint64_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n && mask[i]) route[i] = 0xFFFFFFFFu;
+}
+
+// ---- the response
+__global__ __launch_bounds__(256) void wire_resp_outcome_kernel(WireEncodeArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  const uint8_t err = wire_outcome(a.host_err ? a.host_err[i] : (uint8_t)WIRE_ERR_NONE, a.open_status[i],
+                                   a.has_deadline && a.times[i] > a.deadline, a.wire_status[i], a.verdicts[i],
+                                   a.replayed && a.replayed[i]);
+  a.err[i] = err;
+  a.finished[i] = err == WIRE_ERR_NONE;
+}
+
+__global__ __launch_bounds__(1024) void wire_resp_scan_kernel(WireEncodeArgs a) {
+  block_exclusive_scan(a.n, [&](uint64_t i) { return (uint64_t)wire_resp_len(a.err[i] == WIRE_ERR_NONE, a.prep_msg_bytes); },
+                       a.offsets);
+}
+
+__global__ __launch_bounds__(256) void wire_resp_pack_kernel(WireEncodeArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i == 0) wire_put32(a.out, (uint32_t)a.offsets[a.n]);  // the host refuses a body of 2^32 bytes or more
+  if (i >= a.n) return;
+  uint8_t* p = a.out + 4 + a.offsets[i];
+  const uint8_t* id = a.ids + 16 * i;
+  for (int k = 0; k < 16; k++) p[k] = id[k];
+  const uint8_t err = a.err[i];
+  if (err != WIRE_ERR_NONE) {
+    p[16] = 2;
+    p[17] = err;
+    return;
+  }
+  const uint32_t S = a.prep_msg_bytes;
+  p[16] = 0;
+  wire_put32(p + 17, 5 + S);
+  p[21] = 2;
+  wire_put32(p + 22, S);
+  const uint8_t* m = a.prep_msgs + i * a.prep_msg_stride;
+  for (uint32_t k = 0; k < S; k++) p[26 + k] = m[k];
+}
+
+inline uint32_t blocks(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
+
+}  // namespace
+
+hipError_t launch_wire_header(const uint8_t* body, uint64_t len, uint32_t query_type, WireState* st, hipStream_t s) {
+  hipLaunchKernelGGL(wire_header_kernel, dim3(1), dim3(1), 0, s, body, len, query_type, st);
+  return hipGetLastError();
+}
+
+hipError_t launch_wire_index(const uint8_t* body, WireState* st, uint64_t cands, bool fast, uint64_t* offs, uint64_t cap,
+                             hipStream_t s) {
+  if (fast && cands) {
+    hipLaunchKernelGGL(wire_fast_kernel, dim3(blocks(cands, 256)), dim3(256), 0, s, body, st, cands);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(wire_gallop_kernel, dim3(1), dim3(64), 0, s, body, st, cands, offs, cap);
+  return hipGetLastError();
+}
+
+hipError_t launch_wire_records(const WireDecodeArgs& a, uint32_t* dup_tab, uint64_t slots, uint32_t* dup_result, uint64_t k0,
+                               uint64_t k1, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(wire_records_kernel, dim3(blocks(a.n, 256)), dim3(256), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(wire_dup_kernel, dim3(blocks(a.n, 256)), dim3(256), 0, s, a.body, (const WireRec*)a.recs, a.n, dup_tab,
+                     slots, k0, k1, dup_result);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(wire_dup_read_kernel, dim3(1), dim3(1), 0, s, (const uint32_t*)dup_result, a.st);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(wire_scan_kernel, dim3(1), dim3(1024), 0, s, (const WireRec*)a.recs, a.n, a.enc_offsets,
+                     a.payload_offsets, a.st);
+  return hipGetLastError();
+}
+
+hipError_t launch_wire_gather(const WireDecodeArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(wire_gather_kernel, dim3(blocks(a.n, 4)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_wire_exclude(uint32_t* route, const uint8_t* mask, uint64_t n, hipStream_t s) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(wire_exclude_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, route, mask, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_wire_encode_sizes(const WireEncodeArgs& a, hipStream_t s) {
+  if (a.n) {
+    hipLaunchKernelGGL(wire_resp_outcome_kernel, dim3(blocks(a.n, 256)), dim3(256), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(wire_resp_scan_kernel, dim3(1), dim3(1024), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_wire_encode_pack(const WireEncodeArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(wire_resp_pack_kernel, dim3(blocks(a.n ? a.n : 1, 256)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+}  // namespace jx

@@ -34,6 +34,7 @@ from __future__ import annotations
 import contextlib
 import ctypes
 import threading
+import weakref
 from dataclasses import dataclass
 
 import numpy as np
@@ -153,6 +154,100 @@ class SealResult:
     status: np.ndarray        # uint8[n]: SEAL_OK, SEAL_SKIPPED or SEAL_ZERO_DH
 
 
+WIRE_OK, WIRE_MALFORMED, WIRE_WRONG_QUERY_TYPE, WIRE_DUPLICATE_ID = 0, 1, 2, 3  # JX_WIRE_* (request status)
+WIRE_REPORT_ODD_PUBLIC_SHARE, WIRE_REPORT_NOT_INITIALIZE, WIRE_REPORT_ODD_PREP_SHARE = 1, 2, 3  # wire_status
+WIRE_NO_ERROR = 0xFF           # JX_WIRE_NO_ERROR: no host-resolved error for the report
+ROUTE_OUT = 0xFFFFFFFF         # route[i] of a report that must not reach an aggregation
+WIRE_RECORD = np.dtype([(name, "<u8") for name in ("off", "len", "public_share_off", "enc_off", "payload_off", "message_off",
+                                                    "prep_msg_off", "prep_share_off")] +
+                       [(name, "<u4") for name in ("public_share_len", "enc_len", "payload_len", "message_len",
+                                                    "prep_msg_len", "prep_share_len")] +
+                       [("config_id", "u1"), ("ping_pong_type", "u1"), ("pad_", "u1", 6)])
+
+
+class _DeviceBytes:
+    """Device memory as torch sees it (__cuda_array_interface__): no copy, no ownership."""
+
+    def __init__(self, ptr: int, nbytes: int):
+        self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
+
+
+class InitReq:
+    """A decoded AggregationJobInitializeReq (jx_init_req): the request's status, and for an accepted one the device
+    arrays the sealed fused call reads (`d`, a _lib.JxInitReqArrays of device pointers) with the pinned host copy of
+    the small ones as numpy views: times, enc_offsets, payload_offsets, key_index, wire_status, report_ids, records
+    (WIRE_RECORD). Holds device memory until release() (or the end of a `with`), which must come before the engine's
+    close()."""
+
+    def __init__(self, engine: "HelperEngine", handle):
+        self._engine, self._h = engine, handle
+        L = engine._L
+        info = _lib.JxInitReqInfo()
+        check(L.jx_init_req_info(handle, ctypes.byref(info)), engine._h, "jx_init_req_info")
+        self.status, self.error_offset, self.duplicate_index = int(info.status), int(info.error_offset), int(info.duplicate_index)
+        self.n = int(info.n)
+        self.batch_id = bytes(info.batch_id) if info.has_batch_id else None
+        self.agg_param_span = (int(info.agg_param_off), int(info.agg_param_len))
+        self.fallback_iterations, self.odd_public_shares = int(info.fallback_iterations), int(info.odd_public_shares)
+        self.enc_bytes, self.payload_bytes = int(info.enc_bytes), int(info.payload_bytes)
+        self.d = None
+        n = self.n
+        if self.status == WIRE_OK and n:
+            a = _lib.JxInitReqArrays()
+            check(L.jx_init_req_arrays(handle, ctypes.byref(a)), engine._h, "jx_init_req_arrays")
+            self.d = a
+
+            def view(ptr, dtype, count):
+                buf = (ctypes.c_uint8 * (np.dtype(dtype).itemsize * count)).from_address(ptr)
+                return np.frombuffer(buf, dtype=dtype, count=count)
+
+            self.times = view(a.times, np.uint64, n)
+            self.enc_offsets = view(a.enc_offsets, np.uint64, n + 1)
+            self.payload_offsets = view(a.payload_offsets, np.uint64, n + 1)
+            self.records = view(a.records, WIRE_RECORD, n)
+            self.report_ids = view(a.report_ids, np.uint8, 16 * n).reshape(n, 16)
+            self.key_index = view(a.key_index, np.uint8, 2 * n).reshape(n, 2)
+            self.wire_status = view(a.wire_status, np.uint8, n)
+        else:
+            self.n = n if self.status == WIRE_DUPLICATE_ID else 0
+            self.times, self.enc_offsets, self.payload_offsets = np.zeros(0, np.uint64), np.zeros(1, np.uint64), np.zeros(1, np.uint64)
+            self.records, self.report_ids = np.zeros(0, WIRE_RECORD), np.zeros((0, 16), np.uint8)
+            self.key_index, self.wire_status = np.zeros((0, 2), np.uint8), np.zeros(0, np.uint8)
+
+    def device_bytes(self, name: str):
+        """One of the device arrays (report_ids, times, public_shares, leader_prep_shares, encs, enc_offsets, payloads,
+        payload_offsets, key_index, wire_status, route, records) as a torch uint8 tensor over the handle's memory."""
+        import torch
+
+        e, n = self._engine, self.n
+        size = {"report_ids": 16 * n, "times": 8 * n, "public_shares": n * e.public_share_len,
+                "leader_prep_shares": n * e.prep_share_len, "encs": self.enc_bytes, "enc_offsets": 8 * (n + 1),
+                "payloads": self.payload_bytes, "payload_offsets": 8 * (n + 1), "key_index": 2 * n, "wire_status": n,
+                "route": 4 * n, "records": WIRE_RECORD.itemsize * n}[name]
+        ptr = getattr(self.d, "d_" + name) if self.d is not None else None
+        if not size or not ptr:
+            return torch.zeros(0, dtype=torch.uint8, device=torch.device("cuda", e.device))
+        return torch.as_tensor(_DeviceBytes(ptr, size), device=torch.device("cuda", e.device))
+
+    def exclude(self, mask):
+        """Route the reports with mask[i] away from every aggregation (jx_init_req_exclude)."""
+        m = np.ascontiguousarray(np.asarray(mask).astype(np.uint8).reshape(self.n)) if self.n else np.zeros(1, np.uint8)
+        check(self._engine._L.jx_init_req_exclude(self._h, _ptr(m)), self._engine._h, "jx_init_req_exclude")
+
+    def release(self):
+        if self._h:
+            self.times = self.enc_offsets = self.payload_offsets = self.records = self.report_ids = None
+            self.key_index = self.wire_status = self.d = None  # the views' memory goes with the handle
+            self._engine._L.jx_init_req_release(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.release()
+
+
 class HelperEngine:
     """One engine per (Prio3 instance, verify key, GPU). Serves the helper role (the north-star
     path) and the leader role of the same ping-pong exchange."""
@@ -191,6 +286,8 @@ class HelperEngine:
     # ------------------------------------------------------------------ lifecycle
     def close(self):
         if getattr(self, "_h", None):
+            for r in list(getattr(self, "_init_reqs", ())):  # decoded requests hold the engine's arena memory
+                r.release()
             self._L.jx_engine_destroy(self._h)
             self._h = None
 
@@ -780,6 +877,61 @@ class HelperEngine:
                 d_out_prep_msgs, d_out_verdicts, d_out_open_status)
             check(st, self._h, "jx_helper_prep_aggregate_encrypted_device")
 
+    # ------------------------------------------------------------------ wire in, wire out
+    def decode_init_req(self, body, query_type: int, key_first, key_second, report_deadline: int | None = None,
+                        length: int | None = None, stream=None) -> InitReq:
+        """Decode an AggregationJobInitializeReq body on the GPU (jx_init_req_decode / _device). body: bytes (copied to
+        the device once) or, with `length`, a device pointer or torch tensor holding the body (ordered against `stream`
+        like the other device-pointer methods). query_type: the task's (messages.QUERY_TIME_INTERVAL / _FIXED_SIZE).
+        key_first / key_second: 256 keypair indices by HPKE config id (KEY_NONE: none). report_deadline: the latest
+        report time that is not too early. Returns an InitReq also for a request that is refused: see its status."""
+        kf = np.ascontiguousarray(np.asarray(key_first, dtype=np.uint8).reshape(256))
+        ks = np.ascontiguousarray(np.asarray(key_second, dtype=np.uint8).reshape(256))
+        dl = None if report_deadline is None else ctypes.byref(ctypes.c_uint64(report_deadline))
+        h = ctypes.c_void_p()
+        if length is None:
+            b = np.frombuffer(bytes(body) or b"\0", np.uint8)
+            st = self._L.jx_init_req_decode(self._h, _ptr(b), len(body), query_type, _ptr(kf), _ptr(ks), dl, ctypes.byref(h))
+            check(st, self._h, "jx_init_req_decode")
+        else:
+            ptr = int(body.data_ptr()) if hasattr(body, "data_ptr") else int(body)
+            with self._ordered(stream):
+                st = self._L.jx_init_req_decode_device(self._h, ptr, length, query_type, _ptr(kf), _ptr(ks), dl,
+                                                       ctypes.byref(h))
+                check(st, self._h, "jx_init_req_decode_device")
+        req = InitReq(self, h)
+        with self._lock:
+            if not hasattr(self, "_init_reqs"):
+                self._init_reqs = weakref.WeakSet()
+            self._init_reqs.add(req)
+        return req
+
+    def encode_init_resp(self, req: InitReq, d_verdicts: int | None, d_open_status: int | None, d_prep_msgs: int | None,
+                         host_errors=None, replayed=None, prep_msg_stride: int = 0, d_out: int | None = None,
+                         capacity: int = 0, d_out_finished: int | None = None, stream=None):
+        """The AggregationJobResp body of a decoded request from the device arrays the sealed calls wrote
+        (jx_init_resp_encode / _device). host_errors: uint8[n] PrepareError code points of reports the host resolved
+        (WIRE_NO_ERROR: none); replayed: a mask of n. Returns (body bytes, finished mask); with d_out (a device buffer of
+        `capacity` bytes) the body is written there and its length is returned."""
+        n = req.n
+        he = None if host_errors is None else np.ascontiguousarray(np.asarray(host_errors, dtype=np.uint8).reshape(n))
+        rp = None if replayed is None else np.ascontiguousarray(np.asarray(replayed).astype(np.uint8).reshape(n))
+        ln = ctypes.c_uint64()
+        with self._ordered(stream):
+            if d_out is not None:
+                st = self._L.jx_init_resp_encode_device(self._h, req._h, d_verdicts, d_open_status, d_prep_msgs,
+                                                        prep_msg_stride, _ptr(he), _ptr(rp), d_out, capacity,
+                                                        ctypes.byref(ln), d_out_finished)
+                check(st, self._h, "jx_init_resp_encode_device")
+                return ln.value
+            cap = 4 + n * (26 + self.prep_msg_len)
+            out = np.zeros(cap, np.uint8)
+            fin = np.zeros(max(n, 1), np.uint8)
+            st = self._L.jx_init_resp_encode(self._h, req._h, d_verdicts, d_open_status, d_prep_msgs, prep_msg_stride,
+                                             _ptr(he), _ptr(rp), _ptr(out), cap, ctypes.byref(ln), _ptr(fin))
+            check(st, self._h, "jx_init_resp_encode")
+        return out[:ln.value].tobytes(), fin[:n].astype(bool)
+
     # ------------------------------------------------------------------ aggregation state
     def aggregate_share(self, segment: int = 0) -> tuple[bytes, int, bytes]:
         """(encoded aggregate share, report count, checksum) of one batch aggregation."""
@@ -861,5 +1013,5 @@ class HelperEngine:
 
 Prio3Engine = HelperEngine
 
-__all__ = ["HelperEngine", "Prio3Engine", "BatchResult", "EncryptedResult", "LeaderInit", "EngineError",
+__all__ = ["HelperEngine", "Prio3Engine", "BatchResult", "EncryptedResult", "LeaderInit", "EngineError", "InitReq",
            "VERDICT_LABELS", "FINISHED", "OPEN_STATUS"]

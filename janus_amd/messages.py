@@ -285,3 +285,117 @@ class PlaintextInputShare:
         payload = r.opaque32()
         r.done()
         return cls(tuple(exts), payload)
+
+
+# ----------------------------------------------------------------------------- aggregate-init request / response
+
+QUERY_TIME_INTERVAL, QUERY_FIXED_SIZE = 1, 2  # messages/src/query_type.rs: the query-type code points
+
+
+@dataclass(frozen=True)
+class PartialBatchSelector:
+    """query type byte, then the batch id (32 bytes) under FixedSize and nothing under TimeInterval
+    (messages/src/lib.rs:1606-1700). Decoding expects the task's query type (decode_expecting_value, :1659-1666)."""
+
+    query_type: int
+    batch_id: bytes | None = None
+
+    @classmethod
+    def time_interval(cls) -> "PartialBatchSelector":
+        return cls(QUERY_TIME_INTERVAL)
+
+    @classmethod
+    def fixed_size(cls, batch_id: bytes) -> "PartialBatchSelector":
+        return cls(QUERY_FIXED_SIZE, bytes(batch_id))
+
+    def encode(self) -> bytes:
+        if self.query_type == QUERY_TIME_INTERVAL:
+            return b"\x01"
+        if self.query_type != QUERY_FIXED_SIZE or self.batch_id is None or len(self.batch_id) != 32:
+            raise CodecError("FixedSize carries a 32-byte batch id; no other query type is known")
+        return b"\x02" + self.batch_id
+
+    @classmethod
+    def decode_from(cls, r: _Reader, query_type: int) -> "PartialBatchSelector":
+        if query_type not in (QUERY_TIME_INTERVAL, QUERY_FIXED_SIZE):
+            raise ValueError("unknown query type")
+        if r.u8() != query_type:
+            raise CodecError("unexpected query type")
+        return cls(query_type, r.take(32) if query_type == QUERY_FIXED_SIZE else None)
+
+    @classmethod
+    def decode(cls, b: bytes, query_type: int) -> "PartialBatchSelector":
+        r = _Reader(b)
+        s = cls.decode_from(r, query_type)
+        r.done()
+        return s
+
+
+def _prepare_init_from(r: _Reader) -> PrepareInit:
+    rs = ReportShare.decode_from(r)
+    return PrepareInit(rs, PingPongMessage.decode(r.opaque32()))
+
+
+@dataclass(frozen=True)
+class AggregationJobInitializeReq:
+    """u32-prefixed aggregation parameter || PartialBatchSelector || u32 byte length of the PrepareInits || the
+    PrepareInits (messages/src/lib.rs:2482-2553)."""
+
+    aggregation_parameter: bytes
+    partial_batch_selector: PartialBatchSelector
+    prepare_inits: tuple
+
+    MEDIA_TYPE = "application/dap-aggregation-job-init-req"
+
+    def encode(self) -> bytes:
+        items = b"".join(p.encode() for p in self.prepare_inits)
+        return _o32(self.aggregation_parameter) + self.partial_batch_selector.encode() + _o32(items)
+
+    @classmethod
+    def decode(cls, b: bytes, query_type: int) -> "AggregationJobInitializeReq":
+        r = _Reader(b)
+        param = r.opaque32()
+        sel = PartialBatchSelector.decode_from(r, query_type)
+        ir = _Reader(r.opaque32())
+        r.done()
+        inits = []
+        while ir.i < len(ir.b):
+            inits.append(_prepare_init_from(ir))
+        return cls(param, sel, tuple(inits))
+
+
+def _prepare_resp_from(r: _Reader) -> PrepareResp:
+    rid = r.take(16)
+    k = r.u8()
+    if k == 0:
+        return PrepareResp(rid, PrepareStepResult(0, message=PingPongMessage.decode(r.opaque32())))
+    if k == 1:
+        return PrepareResp(rid, PrepareStepResult(1))
+    if k == 2:
+        e = r.u8()
+        if e not in PrepareError._value2member_map_:
+            raise CodecError("unexpected PrepareError")
+        return PrepareResp(rid, PrepareStepResult(2, error=PrepareError(e)))
+    raise CodecError("unexpected PrepareStepResult")
+
+
+@dataclass(frozen=True)
+class AggregationJobResp:
+    """u32 byte length of the PrepareResps || the PrepareResps (messages/src/lib.rs:2669-2700)."""
+
+    prepare_resps: tuple
+
+    MEDIA_TYPE = "application/dap-aggregation-job-resp"
+
+    def encode(self) -> bytes:
+        return _o32(b"".join(p.encode() for p in self.prepare_resps))
+
+    @classmethod
+    def decode(cls, b: bytes) -> "AggregationJobResp":
+        r = _Reader(b)
+        ir = _Reader(r.opaque32())
+        r.done()
+        resps = []
+        while ir.i < len(ir.b):
+            resps.append(_prepare_resp_from(ir))
+        return cls(tuple(resps))
