@@ -560,6 +560,87 @@ int32_t jx_init_resp_encode(jx_engine* e, jx_init_req* r, const void* d_verdicts
                             uint8_t* out_finished);
 void jx_init_req_release(jx_init_req* r);
 
+/* ---- The leader's end of the same exchange: step_aggregation_job_aggregate_init's request written and
+ * process_response_from_helper's response read (aggregation_job_driver.rs:296-425, :540-701), with the prep shares
+ * staying on the device between jx_leader_prep_init_device* and the body, and the response's prep messages going
+ * straight into the rows jx_leader_prep_finish_device reads.
+ *
+ * jx_init_req_encode* writes the AggregationJobInitializeReq body: u32 + aggregation parameter || PartialBatchSelector
+ * (query type, and the 32-byte batch id under FixedSize) || u32 + PrepareInits. Report i is sent iff verdicts[i] ==
+ * JX_FINISHED and exclude[i] == 0 (exclude nullable): a report whose leader init failed, or that the caller knows it
+ * must not send (a collected batch, duplicate extensions), takes no room in the body. The reports sent keep their order:
+ * the response is matched by position. Per sent report: id[16] || time u64 || u32 PS || public share || config id ||
+ * u16 + encapsulated key || u32 + payload || u32 (5 + LPS) || 00 || u32 LPS || prep share.
+ *   device form  device pointers for report ids [n x 16], public shares [n x PS] (NULL when PS is 0), encapsulated
+ *                keys and payloads (packed by their offset arrays), prep shares (rows prep_share_stride apart, 0 = LPS:
+ *                jx_leader_prep_init_device*'s d_out_prep_shares) and that call's d_out_verdicts, all of any alignment;
+ *                HOST arrays for times[n], config_ids[n], enc_offsets[n + 1] (NULL: n x 32 bytes), payload_offsets
+ *                [n + 1] and exclude[n]; the aggregation parameter, the query type and batch_id (FixedSize) on the host.
+ *   host form    host pointers throughout, and the body in host memory.
+ * Refused before a byte is written: an encapsulated key of 2^16 bytes or more, a payload of 2^32 bytes or more,
+ * decreasing offsets (JX_E_INVALID); PrepareInits of more than 2^32 - 1 bytes together (JX_E_UNSUPPORTED); a body longer
+ * than `capacity` (JX_E_INVALID). jx_init_req_encode_bound gives the body's length if every report were sent, from the
+ * host arrays alone. Both forms wait for their result, since the length is part of it (inputs written on another
+ * stream are ordered by the Conventions). n_sent == 0 is JX_OK with a body that holds an empty vector; the reference
+ * then sends nothing (aggregation_job_driver.rs:388-423), which is the caller's choice.
+ * The handle remembers which reports were sent (jx_leader_req_sent: the compaction list, sent_index[k] = i, as a pinned
+ * host array and on the device, n_sent entries) and their ids. It holds arena memory until jx_leader_req_release,
+ * which must come before jx_engine_destroy.
+ *
+ * jx_init_resp_decode reads the helper's AggregationJobResp body (host memory) for the handle's request. The body is
+ * walked on the host (a response is ~42 bytes per report and a dependent chain), as AggregationJobResp::get_decoded
+ * does: a framing error anywhere (a truncation, a length that overruns, a tag above 2, a PrepareError above 9, a
+ * ping-pong type above 2, bytes left over) refuses the response with JX_WIRE_MALFORMED and the offset of the read that
+ * failed; a response whose PrepareResps are not exactly the sent reports in order is JX_WIRE_RESP_MISMATCH with the
+ * first position that differs. A refused response queues nothing and writes nothing; the call can be repeated with
+ * another body. Otherwise out_result[k] / out_error[k] (n_sent entries, host) say what a one-round leader makes of
+ * response k (aggregation_job_driver.rs:584-663): JX_RESP_CONTINUED (Continue{Finish{prep_msg}} with a prep message of
+ * PM bytes; error JX_WIRE_NO_ERROR), JX_RESP_REJECTED (error: the helper's PrepareError), JX_RESP_FINISHED and
+ * JX_RESP_MESSAGE_MISMATCH (a Continue carrying another message, or a prep message of another length; error 5,
+ * VdafPrepError). One upload and one kernel on the engine stream then write, for every row i < n of the leader batch,
+ * d_out_prep_msgs row i (prep_msg_stride apart, 0 = PM; NULL when PM is 0) and d_out_peer_verdicts[i]: the prep message
+ * and 0 where the row's response continued, zeros and a non-zero verdict everywhere else, rows never sent included, so
+ * jx_leader_prep_finish_device(e, batch_id, n, d_out_prep_msgs, d_out_peer_verdicts, ..) can never finish such a row.
+ * The device outputs are queued, not waited for. */
+#define JX_WIRE_RESP_MISMATCH 4 /* info.mismatch_index */
+#define JX_RESP_CONTINUED 0
+#define JX_RESP_REJECTED 1
+#define JX_RESP_FINISHED 2
+#define JX_RESP_MESSAGE_MISMATCH 3
+typedef struct jx_leader_req jx_leader_req;
+typedef struct jx_leader_req_info_t {
+  uint64_t n, n_sent, body_len;
+} jx_leader_req_info_t;
+typedef struct jx_init_resp_info_t {
+  uint32_t status; /* JX_WIRE_OK, JX_WIRE_MALFORMED or JX_WIRE_RESP_MISMATCH */
+  uint32_t pad_;
+  uint64_t error_offset;   /* JX_WIRE_MALFORMED */
+  uint64_t mismatch_index; /* JX_WIRE_RESP_MISMATCH */
+  uint64_t n;              /* PrepareResps in the body (0 when malformed) */
+} jx_init_resp_info_t;
+int32_t jx_init_req_encode_bound(const jx_engine* e, uint64_t n, const uint64_t* enc_offsets, const uint64_t* payload_offsets,
+                                 uint64_t agg_param_len, uint32_t query_type, uint64_t* out_bound);
+int32_t jx_init_req_encode_device(jx_engine* e, uint64_t n, const void* d_report_ids, const uint64_t* times,
+                                  const void* d_public_shares, const uint8_t* config_ids, const void* d_encs,
+                                  const uint64_t* enc_offsets, const void* d_payloads, const uint64_t* payload_offsets,
+                                  const void* d_prep_shares, uint64_t prep_share_stride, const void* d_verdicts,
+                                  const uint8_t* exclude, const uint8_t* agg_param, uint64_t agg_param_len,
+                                  uint32_t query_type, const uint8_t* batch_id, void* d_out, uint64_t capacity,
+                                  uint64_t* out_len, jx_leader_req** out_req);
+int32_t jx_init_req_encode(jx_engine* e, uint64_t n, const uint8_t* report_ids, const uint64_t* times,
+                           const uint8_t* public_shares, const uint8_t* config_ids, const uint8_t* encs,
+                           const uint64_t* enc_offsets, const uint8_t* payloads, const uint64_t* payload_offsets,
+                           const uint8_t* prep_shares, uint64_t prep_share_stride, const uint8_t* verdicts,
+                           const uint8_t* exclude, const uint8_t* agg_param, uint64_t agg_param_len, uint32_t query_type,
+                           const uint8_t* batch_id, uint8_t* out, uint64_t capacity, uint64_t* out_len,
+                           jx_leader_req** out_req);
+int32_t jx_leader_req_info(const jx_leader_req* r, jx_leader_req_info_t* out);
+int32_t jx_leader_req_sent(const jx_leader_req* r, const uint32_t** sent_index, const void** d_sent_index);
+int32_t jx_init_resp_decode(jx_engine* e, jx_leader_req* r, const uint8_t* body, uint64_t len, void* d_out_prep_msgs,
+                            uint64_t prep_msg_stride, void* d_out_peer_verdicts, uint8_t* out_result, uint8_t* out_error,
+                            jx_init_resp_info_t* info);
+void jx_leader_req_release(jx_leader_req* r);
+
 /* Accumulate the output shares of the resident batch `batch_id` (helper, or leader after finish) into
  * the engine's running batch aggregations (the engine as one shard, §8e): report i is added iff
  * verdict == FINISHED and accept_mask[i] != 0 (accept_mask nullable = all), into aggregation

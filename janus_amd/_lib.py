@@ -30,6 +30,8 @@ EXPORTED_SYMBOLS = (
     "jx_client_seal_sizes", "jx_client_seal_batch", "jx_client_seal_device",
     "jx_init_req_decode", "jx_init_req_decode_device", "jx_init_req_info", "jx_init_req_arrays", "jx_init_req_exclude",
     "jx_init_resp_encode_device", "jx_init_resp_encode", "jx_init_req_release",
+    "jx_init_req_encode_bound", "jx_init_req_encode_device", "jx_init_req_encode", "jx_leader_req_info",
+    "jx_leader_req_sent", "jx_init_resp_decode", "jx_leader_req_release",
 )
 
 _lib = None
@@ -71,6 +73,15 @@ class JxInitReqArrays(ctypes.Structure):
         "d_report_ids", "d_times", "d_public_shares", "d_leader_prep_shares", "d_encs", "d_enc_offsets", "d_payloads",
         "d_payload_offsets", "d_key_index", "d_wire_status", "d_route", "d_records",
         "times", "enc_offsets", "payload_offsets", "records", "report_ids", "key_index", "wire_status")]
+
+
+class JxLeaderReqInfo(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in ("n", "n_sent", "body_len")]
+
+
+class JxInitRespInfo(ctypes.Structure):
+    _fields_ = [("status", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
+    _fields_ += [(name, ctypes.c_uint64) for name in ("error_offset", "mismatch_index", "n")]
 
 
 class EngineError(RuntimeError):
@@ -155,6 +166,15 @@ def load():
         "jx_init_resp_encode_device": (i32, [vp, vp, vp, vp, vp, u64, u8p, u8p, vp, u64, P(u64), vp]),
         "jx_init_resp_encode": (i32, [vp, vp, vp, vp, vp, u64, u8p, u8p, u8p, u64, P(u64), u8p]),
         "jx_init_req_release": (None, [vp]),
+        "jx_init_req_encode_bound": (i32, [vp, u64, P(u64), P(u64), u64, u32, P(u64)]),
+        "jx_init_req_encode_device": (i32, [vp, u64, vp, P(u64), vp, u8p, vp, P(u64), vp, P(u64), vp, u64, vp, u8p, u8p,
+                                            u64, u32, u8p, vp, u64, P(u64), P(vp)]),
+        "jx_init_req_encode": (i32, [vp, u64, u8p, P(u64), u8p, u8p, u8p, P(u64), u8p, P(u64), u8p, u64, u8p, u8p, u8p,
+                                     u64, u32, u8p, u8p, u64, P(u64), P(vp)]),
+        "jx_leader_req_info": (i32, [vp, P(JxLeaderReqInfo)]),
+        "jx_leader_req_sent": (i32, [vp, P(vp), P(vp)]),
+        "jx_init_resp_decode": (i32, [vp, vp, u8p, u64, vp, u64, vp, u8p, u8p, P(JxInitRespInfo)]),
+        "jx_leader_req_release": (None, [vp]),
         "jx_engine_sync": (i32, [vp]),
         "jx_engine_stream": (i32, [vp, P(vp)]),
         "jx_engine_wait_stream": (i32, [vp, vp]),

@@ -326,6 +326,215 @@ def leader_process_helper_response(engine: HelperEngine, step: LeaderStep, prepa
     return AggregateInitOutcome(responses, finished, failures)
 
 
+# ----------------------------------------------------------------------------- leader side, through wire bytes
+
+
+@dataclass
+class LeaderWireStep:
+    body: bytes                                # the AggregationJobInitializeReq body
+    req: object                                # the engine's LeaderReq (released by the response, or by leader_abandon_wire)
+    stepped: list[int]                         # index into `stored` of each PrepareInit of the body, in order
+    failed: dict[int, PrepareError]            # reports that failed before the helper
+    n: int                                     # rows of the engine's leader batch
+    step_failures: Counter = field(default_factory=Counter)
+    batch_id: int = 0                          # the resident leader batch when n > 0
+    report_ids: list = field(default_factory=list)
+    _row_of: list = field(default_factory=list)  # engine row of each report
+    _times: list = field(default_factory=list)
+
+
+def leader_aggregate_init_wire(engine: HelperEngine, stored: list, rows, lis_stride: int, agg_param: bytes, selector,
+                               segments: list[int] | None = None, writer=None) -> LeaderWireStep:
+    """leader_aggregate_init from the StoredReports and device rows of a handle_upload outcome to the request body,
+    with the prep shares staying in HBM: the duplicate-extension check on the host (aggregation_job_driver.rs:
+    325-341: InvalidMessage, counted as duplicate_extension), leader_init_device on the rows in place, the initial
+    write and the collected-batch exclusion as leader_aggregate_init does them, then engine.encode_init_req over
+    the reports whose init succeeded and that are not excluded. The engine batch holds every row of `rows`; a row no
+    StoredReport names (a report the upload rejected) is never sent, so it is never continued or accumulated.
+    selector: the job's messages.PartialBatchSelector."""
+    import torch
+
+    from .messages import QUERY_FIXED_SIZE
+
+    v = engine.vdaf
+    nrep = len(stored)
+    m = 0 if rows is None else int(rows.shape[0])
+    PS, LPS = v.public_share_len, engine.prep_share_len
+    failures: Counter = Counter()
+    failed: dict[int, PrepareError] = {}
+    seg_of = lambda i: int(segments[i]) if segments else 0  # noqa: E731
+    ids = np.zeros((max(m, 1), 16), np.uint8)
+    ps = np.zeros((max(m, 1), max(PS, 1)), np.uint8)
+    times = np.zeros(max(m, 1), np.uint64)
+    cfg = np.zeros(max(m, 1), np.uint8)
+    encs, pays = [b""] * m, [b""] * m
+    exclude = np.ones(max(m, 1), np.uint8)
+    rep_of_row: dict[int, int] = {}
+    dup = np.zeros(nrep, bool)
+    for i, s in enumerate(stored):
+        types = [e.extension_type for e in s.extensions]
+        if len(set(types)) != len(types):
+            dup[i] = True
+            failed[i] = PrepareError.InvalidMessage
+            failures["duplicate_extension"] += 1
+        r, ct = s.row, s.helper_encrypted_input_share
+        if r in rep_of_row or not 0 <= r < m:
+            raise ValueError("each StoredReport names its own row of the upload's rows")
+        rep_of_row[r] = i
+        ids[r] = np.frombuffer(s.metadata.report_id, np.uint8)
+        if PS:
+            ps[r] = np.frombuffer(s.public_share, np.uint8)
+        times[r], cfg[r] = s.metadata.time, ct.config_id
+        encs[r], pays[r] = ct.encapsulated_key, ct.payload
+        exclude[r] = dup[i]
+    eoff, poff = np.zeros(m + 1, np.uint64), np.zeros(m + 1, np.uint64)
+    if m:
+        eoff[1:] = np.cumsum([len(x) for x in encs])
+        poff[1:] = np.cumsum([len(x) for x in pays])
+    row_of = [s.row for s in stored]
+    job_times = [(seg_of(i), s.metadata.time) for i, s in enumerate(stored)]
+    dev = torch.device("cuda", engine.device)
+    batch_id = 0
+    verdicts = np.zeros(m, np.uint8)
+    with torch.cuda.device(dev):
+        d_ids, d_ps = torch.from_numpy(ids.reshape(-1)).to(dev), torch.from_numpy(ps.reshape(-1)).to(dev)
+        d_en = torch.from_numpy(np.frombuffer(b"".join(encs) or b"\0", np.uint8).copy()).to(dev)
+        d_pay = torch.from_numpy(np.frombuffer(b"".join(pays) or b"\0", np.uint8).copy()).to(dev)
+        d_lps = torch.empty(max(m, 1) * max(LPS, 1), dtype=torch.uint8, device=dev)
+        d_v = torch.zeros(max(m, 1), dtype=torch.uint8, device=dev)
+        if m:
+            batch_id = engine.leader_init_device(m, d_ids.data_ptr(), d_ps.data_ptr() if PS else None, rows.data_ptr(),
+                                                 d_lps.data_ptr(), d_v.data_ptr(), lis_stride=lis_stride)
+            verdicts = d_v.cpu().numpy()[:m]
+        try:
+            for i in range(nrep):
+                vd = int(verdicts[row_of[i]])
+                if not dup[i] and vd != FINISHED:  # handle_ping_pong_error(Role::Leader, ...)
+                    failed[i] = PrepareError.VdafPrepError
+                    failures[VERDICT_LABELS[vd]] += 1
+            if writer is not None:  # InitialWrite of the in-progress job, as leader_aggregate_init
+                collected = writer.write_job(engine, 0, 0, None, None, [], job_times, initial_write=True, terminal=False)
+                for i in range(nrep):
+                    if i not in failed and seg_of(i) in collected:
+                        failed[i] = PrepareError.BatchCollected
+                        exclude[row_of[i]] = 1
+            req = engine.encode_init_req(m, d_ids.data_ptr(), times, d_ps.data_ptr() if PS else None, cfg, d_en.data_ptr(),
+                                         d_pay.data_ptr(), poff, d_lps.data_ptr(), d_v.data_ptr(), agg_param,
+                                         selector.query_type,
+                                         selector.batch_id if selector.query_type == QUERY_FIXED_SIZE else None,
+                                         enc_offsets=eoff, exclude=exclude)
+            body = req.body
+        except BaseException:
+            if batch_id:
+                engine.release(batch_id, missing_ok=True)
+            raise
+    stepped = [rep_of_row[int(r)] for r in req.sent_index]
+    return LeaderWireStep(body, req, stepped, failed, m, failures, batch_id, [s.metadata.report_id for s in stored],
+                          row_of, job_times)
+
+
+def leader_abandon_wire(engine: HelperEngine, step: LeaderWireStep) -> None:
+    """Drop a wire step's leader state: its resident engine batch and its request handle."""
+    if step.batch_id:
+        engine.release(step.batch_id, missing_ok=True)
+    step.req.release()
+
+
+def leader_process_helper_response_wire(engine: HelperEngine, step: LeaderWireStep, resp_body: bytes,
+                                        segments: list[int] | None = None, writer=None) -> AggregateInitOutcome:
+    """leader_process_helper_response from the AggregationJobResp body: engine.decode_init_resp puts the prep
+    messages and peer verdicts into device rows, leader_finish_device continues them, and the finished reports are
+    accumulated (or written by `writer`) as the object path does. A malformed response raises CodecError, one whose
+    PrepareResps are not the sent reports in order the reference's ValueError; in both cases the batch is abandoned."""
+    import torch
+
+    from .engine import RESP_CONTINUED, RESP_FINISHED, RESP_REJECTED, WIRE_MALFORMED, WIRE_RESP_MISMATCH
+
+    n, pm = step.n, engine.prep_msg_len
+    dev = torch.device("cuda", engine.device)
+    failures = Counter(step.step_failures)
+    nrep = max([*step.stepped, *step.failed, -1]) + 1
+    finished = np.zeros(nrep, bool)
+    results: dict[int, PrepareError | None] = dict(step.failed)
+    with torch.cuda.device(dev):
+        d_m = torch.empty((max(n, 1), max(pm, 1)), dtype=torch.uint8, device=dev)
+        d_p = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        d_fv = torch.empty(max(n, 1), dtype=torch.uint8, device=dev)
+        try:
+            dec = engine.decode_init_resp(step.req, resp_body, d_m.data_ptr() if pm else None, d_p.data_ptr(),
+                                          prep_msg_stride=max(pm, 1) if pm else 0)
+        except BaseException:
+            leader_abandon_wire(engine, step)
+            raise
+        if dec.status == WIRE_MALFORMED:
+            leader_abandon_wire(engine, step)
+            raise CodecError(f"AggregationJobResp: malformed at byte {dec.error_offset}")
+        if dec.status == WIRE_RESP_MISMATCH:
+            # the job step fails (process_response_from_helper's error): its device state is released
+            leader_abandon_wire(engine, step)
+            raise ValueError("missing, duplicate, out-of-order, or unexpected prepare steps in response")
+        for k, i in enumerate(step.stepped):
+            res = int(dec.results[k])
+            if res == RESP_REJECTED:
+                results[i] = PrepareError(int(dec.errors[k]))
+                failures["helper_step_failure"] += 1
+            elif res == RESP_FINISHED:
+                results[i] = PrepareError.VdafPrepError
+                failures["finish_mismatch"] += 1
+            elif res != RESP_CONTINUED:
+                results[i] = PrepareError.VdafPrepError
+                failures["leader_ping_pong_message_mismatch"] += 1
+
+        def responses():
+            return [PrepareResp(step.report_ids[i], PrepareStepResult(1) if results[i] is None else
+                                PrepareStepResult(2, error=results[i])) for i in step.stepped]
+
+        if n == 0:
+            step.req.release()
+            if writer is not None:
+                writer.write_job(engine, 0, 0, None, None, [], step._times, initial_write=False, terminal=True)
+            return AggregateInitOutcome(responses(), finished, failures)
+        try:
+            engine.leader_finish_device(step.batch_id, n, d_m.data_ptr() if pm else None, d_p.data_ptr(), d_fv.data_ptr())
+            fv = d_fv.cpu().numpy()[:n]
+        except BaseException:
+            leader_abandon_wire(engine, step)
+            raise
+    step.req.release()
+    accept = np.zeros(n, np.uint8)
+    seg = np.zeros(n, np.uint32)
+    row_seg = [0] * n
+    for i, row in enumerate(step._row_of):
+        row_seg[row] = int(segments[i]) if segments else 0
+    for k, i in enumerate(step.stepped):
+        if int(dec.results[k]) != RESP_CONTINUED:
+            continue
+        row = step._row_of[i]
+        if fv[row] != FINISHED:
+            results[i] = PrepareError.VdafPrepError
+            failures[VERDICT_LABELS[int(fv[row])]] += 1
+            continue
+        results[i] = None
+        accept[row] = 1
+        seg[row] = row_seg[row]
+        finished[i] = True
+    if writer is None:
+        with engine.resident(step.batch_id):
+            engine.accumulate(n, accept, seg, batch_id=step.batch_id)
+    else:
+        idx, seg_ids = _dense(row_seg)
+        try:
+            collected = writer.write_job(engine, step.batch_id, n, accept, idx, seg_ids, step._times,
+                                         initial_write=False, terminal=True)
+        finally:
+            engine.release(step.batch_id)
+        for i, row in enumerate(step._row_of):
+            if finished[i] and row_seg[row] in collected:
+                finished[i] = False
+                results[i] = PrepareError.BatchCollected
+    return AggregateInitOutcome(responses(), finished, failures)
+
+
 # ----------------------------------------------------------------------------- HPKE + prepare
 
 

@@ -3,10 +3,14 @@
 // jx_wire.hip). A decode is three phases with the host reading the small WireState between them, because each
 // phase's sizes are the one before's results: the header (is there a request, how long is its first message), the
 // index (how many messages), the records with the duplicate check and the scans (how many packed bytes).
+// The leader's end of the same exchange: jx_init_req_encode* writes the request body from the arrays the leader holds
+// (one round trip: the body's length is a result), and jx_init_resp_decode walks the response on the host, matches it
+// against the ids the request sent, and queues one upload and one kernel that fill the rows the leader's finish reads.
 #include <cstring>
 #include <new>
 #include <random>
 #include <string>
+#include <vector>
 
 #include "jx_engine_internal.h"
 #include "jx_wire.h"
@@ -18,6 +22,9 @@ static_assert(sizeof(jx_wire_record) == sizeof(WireRec), "jx_wire_record is Wire
 static_assert(JX_WIRE_MALFORMED == WIRE_MALFORMED && JX_WIRE_WRONG_QUERY_TYPE == WIRE_WRONG_QUERY_TYPE &&
                   JX_WIRE_DUPLICATE_ID == WIRE_DUPLICATE_ID && JX_WIRE_NO_ERROR == WIRE_ERR_NONE,
               "the header's code points are the rule's");
+static_assert(JX_RESP_CONTINUED == RESP_CONTINUED && JX_RESP_REJECTED == RESP_REJECTED && JX_RESP_FINISHED == RESP_FINISHED &&
+                  JX_RESP_MESSAGE_MISMATCH == RESP_MESSAGE_MISMATCH && JX_QUERY_FIXED_SIZE == WIRE_QUERY_FIXED_SIZE,
+              "the response's results are the rule's");
 
 struct jx_init_req {
   jx_engine* e = nullptr;
@@ -35,6 +42,19 @@ struct jx_init_req {
   uint8_t *ids = nullptr, *key_index = nullptr, *wire_status = nullptr, *ps = nullptr, *lps = nullptr, *encs = nullptr,
           *payloads = nullptr;
   uint32_t* route = nullptr;
+};
+
+// The leader's encoded request: which reports it sent, in order, for the response to be matched against.
+struct jx_leader_req {
+  jx_engine* e = nullptr;
+  uint64_t n = 0, n_sent = 0, body_len = 0;
+  Slab dev;  // sent_index u32[n] | sent_ids [n x 16]
+  uint32_t* d_sent_index = nullptr;
+  uint8_t* d_sent_ids = nullptr;
+  void* host = nullptr;  // pinned: the same two arrays
+  const uint32_t* sent_index = nullptr;
+  const uint8_t* sent_ids = nullptr;
+  PinnedBuf up;  // a response decode's one upload: the body, then where each row's prep message lies
 };
 
 namespace {
@@ -328,6 +348,164 @@ int32_t encode_core(jx_engine* e, jx_init_req* r, const void* d_verdicts, const 
   return JX_OK;
 }
 
+// ---- the leader's end
+
+void leader_req_free(jx_leader_req* r) {
+  if (!r) return;
+  jx_engine* e = r->e;
+  if (r->up.ev) (void)hipEventSynchronize(r->up.ev);  // the last decode's upload has read the pinned buffer
+  r->up.destroy();
+  if (r->dev.p) arena_put(e->arena, r->dev, e->stream);
+  if (r->host) (void)hipHostFree(r->host);
+  delete r;
+}
+
+struct LeaderReqGuard {
+  jx_leader_req* r;
+  ~LeaderReqGuard() { leader_req_free(r); }
+  jx_leader_req* give() {
+    jx_leader_req* x = r;
+    r = nullptr;
+    return x;
+  }
+};
+
+// what both forms of the request encode take; the bulk pointers are device pointers by the time req_encode_core runs
+struct ReqIn {
+  uint64_t n;
+  const uint8_t *ids, *ps, *encs, *payloads, *lps, *verdicts;
+  const uint64_t* times;
+  const uint8_t* config_ids;
+  const uint64_t *enc_offsets, *payload_offsets;
+  uint64_t lps_stride;
+  const uint8_t *exclude, *agg_param;
+  uint64_t agg_param_len;
+  uint32_t query_type;
+  const uint8_t* batch_id;
+};
+
+// everything that can be refused from the host arrays alone; the bound assumes every report is sent
+int32_t req_check(jx_engine* e, const ReqIn& in, uint64_t* bound) {
+  const Cfg& c = e->cfg;
+  if (in.query_type != JX_QUERY_TIME_INTERVAL && in.query_type != JX_QUERY_FIXED_SIZE) return JX_E_INVALID;
+  if (in.query_type == JX_QUERY_FIXED_SIZE && !in.batch_id) return JX_E_INVALID;
+  if (in.agg_param_len > 0xFFFFFFFFull || (in.agg_param_len && !in.agg_param)) return JX_E_INVALID;
+  if (in.n >= 0x7FFFFFFFull) return fail(e, JX_E_UNSUPPORTED, "init req encode: more than 2^31 - 2 reports in one request");
+  if (in.n && (!in.ids || !in.times || !in.config_ids || !in.payload_offsets || !in.encs || !in.lps || !in.verdicts ||
+               (c.ps_bytes && !in.ps)))
+    return JX_E_INVALID;
+  uint64_t vec = 0;
+  for (uint64_t i = 0; i < in.n; i++) {
+    if ((in.enc_offsets && in.enc_offsets[i + 1] < in.enc_offsets[i]) || in.payload_offsets[i + 1] < in.payload_offsets[i])
+      return fail(e, JX_E_INVALID, "init req encode: offsets must not decrease");
+    const uint64_t el = in.enc_offsets ? in.enc_offsets[i + 1] - in.enc_offsets[i] : 32;
+    const uint64_t pl = in.payload_offsets[i + 1] - in.payload_offsets[i];
+    const uint32_t bad = wire_req_field_check(el, pl);
+    if (bad == WIRE_REQ_LONG_KEY) return fail(e, JX_E_INVALID, "init req encode: an encapsulated key of 2^16 bytes or more");
+    if (bad) return fail(e, JX_E_INVALID, "init req encode: a payload of 2^32 bytes or more");
+    vec += wire_init_len(c.ps_bytes, el, pl, c.lps_bytes);
+  }
+  if (in.n && in.payload_offsets[in.n] - in.payload_offsets[0] && !in.payloads) return JX_E_INVALID;
+  *bound = wire_req_header_len(in.agg_param_len, in.query_type) + vec;
+  return JX_OK;
+}
+
+// the engine mutex is held; in's bulk pointers are on the device; d_out holds `capacity` bytes
+int32_t req_encode_core(jx_engine* e, const ReqIn& in, uint8_t* d_out, uint64_t capacity, uint64_t* out_len,
+                        jx_leader_req** out_req, bool may_wait) {
+  const Cfg& c = e->cfg;
+  const uint64_t n = in.n;
+  LeaderReqGuard g{new (std::nothrow) jx_leader_req};
+  if (!g.r) return fail(e, JX_E_NOMEM, "init req encode: out of host memory");
+  jx_leader_req* r = g.r;
+  r->e = e;
+  r->n = n;
+  WireReqArgs a{};
+  uint64_t *d_times = nullptr, *d_eoff = nullptr, *d_poff = nullptr;
+  uint8_t *d_cfg = nullptr, *d_excl = nullptr, *d_param = nullptr, *d_bid = nullptr;
+  auto lay = [&](void* base) {
+    Carver cv(base);
+    cv.take(d_times, n * 8);
+    cv.take(d_eoff, (n + 1) * 8);
+    cv.take(d_poff, (n + 1) * 8);
+    cv.take(d_cfg, n);
+    cv.take(d_excl, n);
+    cv.take(d_param, in.agg_param_len);
+    cv.take(d_bid, 32);
+    cv.take(a.msg_len, n * 8);
+    cv.take(a.send, n);
+    cv.take(a.offsets, (n + 1) * 8);
+    cv.take(a.rank, (n + 1) * 8);
+    cv.take(a.totals, sizeof(WireReqTotals));
+    return cv.bytes();
+  };
+  Scratch mem;
+  if (const int32_t rc = scratch_get(e, lay(nullptr), mem, may_wait)) return rc;
+  lay(mem.p());
+  auto layh = [&](void* base) {
+    Carver cv(base);
+    cv.take(r->d_sent_index, n * 4);
+    cv.take(r->d_sent_ids, n * 16);
+    return cv.bytes();
+  };
+  const size_t handle_bytes = layh(nullptr);
+  if (const int32_t rc = slab_get(e, handle_bytes, r->dev, "init req encode")) return rc;
+  layh(r->dev.p);
+  if (n) {
+    HIPCHK(e, hipMemcpyAsync(d_times, in.times, n * 8, hipMemcpyHostToDevice, e->stream));
+    if (in.enc_offsets) HIPCHK(e, hipMemcpyAsync(d_eoff, in.enc_offsets, (n + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(d_poff, in.payload_offsets, (n + 1) * 8, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(d_cfg, in.config_ids, n, hipMemcpyHostToDevice, e->stream));
+    if (in.exclude) HIPCHK(e, hipMemcpyAsync(d_excl, in.exclude, n, hipMemcpyHostToDevice, e->stream));
+  }
+  if (in.agg_param_len)
+    HIPCHK(e, hipMemcpyAsync(d_param, in.agg_param, in.agg_param_len, hipMemcpyHostToDevice, e->stream));
+  if (in.query_type == JX_QUERY_FIXED_SIZE)
+    HIPCHK(e, hipMemcpyAsync(d_bid, in.batch_id, 32, hipMemcpyHostToDevice, e->stream));
+  a.n = n;
+  a.ids = in.ids;
+  a.ps = in.ps;
+  a.encs = in.encs;
+  a.payloads = in.payloads;
+  a.lps = in.lps;
+  a.verdicts = in.verdicts;
+  a.times = d_times;
+  a.config_ids = d_cfg;
+  a.enc_offsets = in.enc_offsets ? d_eoff : nullptr;
+  a.payload_offsets = d_poff;
+  a.exclude = in.exclude ? d_excl : nullptr;
+  a.ps_bytes = c.ps_bytes;
+  a.lps_bytes = c.lps_bytes;
+  a.lps_stride = in.lps_stride;
+  a.agg_param = d_param;
+  a.batch_id = d_bid;
+  a.agg_param_len = (uint32_t)in.agg_param_len;
+  a.query_type = in.query_type;
+  a.header_len = wire_req_header_len(in.agg_param_len, in.query_type);
+  a.sent_index = r->d_sent_index;
+  a.sent_ids = r->d_sent_ids;
+  a.out = d_out;
+  HIPCHK(e, launch_wire_req_sizes(a, e->stream));
+  WireReqTotals t{};
+  HIPCHK(e, hipMemcpyAsync(&t, a.totals, sizeof t, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (t.vec_bytes > 0xFFFFFFFFull) return fail(e, JX_E_UNSUPPORTED, "init req encode: the PrepareInits exceed a u32 byte length");
+  const uint64_t total = a.header_len + t.vec_bytes;
+  if (capacity < total) return fail(e, JX_E_INVALID, "init req encode: the output buffer is shorter than the request body");
+  HIPCHK(e, launch_wire_req_pack(a, t.n_sent, (uint32_t)t.vec_bytes, e->stream));
+  HIPCHK(e, hipHostMalloc(&r->host, handle_bytes, hipHostMallocDefault));
+  HIPCHK(e, hipMemcpyAsync(r->host, r->dev.p, handle_bytes, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  const uint8_t *hb = (const uint8_t*)r->host, *db = (const uint8_t*)r->dev.p;
+  r->sent_index = (const uint32_t*)(hb + ((const uint8_t*)r->d_sent_index - db));
+  r->sent_ids = hb + (r->d_sent_ids - db);
+  r->n_sent = t.n_sent;
+  r->body_len = total;
+  *out_len = total;
+  *out_req = g.give();
+  return JX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -404,6 +582,185 @@ void jx_init_req_release(jx_init_req* r) {
   std::lock_guard<FairMutex> lk(r->e->mu);
   (void)hipSetDevice(r->e->device);
   req_free(r);
+}
+
+int32_t jx_init_req_encode_bound(const jx_engine* e, uint64_t n, const uint64_t* enc_offsets, const uint64_t* payload_offsets,
+                                 uint64_t agg_param_len, uint32_t query_type, uint64_t* out_bound) {
+  if (!e || !out_bound || (n && !payload_offsets)) return JX_E_INVALID;
+  const uint32_t st = wire_req_total(n, e->cfg.ps_bytes, e->cfg.lps_bytes, enc_offsets, payload_offsets, nullptr,
+                                     agg_param_len, query_type, out_bound);
+  if (st == WIRE_REQ_LONG_VECTOR) return JX_E_UNSUPPORTED;
+  return st == WIRE_REQ_OK ? JX_OK : JX_E_INVALID;
+}
+
+int32_t jx_init_req_encode_device(jx_engine* e, uint64_t n, const void* d_report_ids, const uint64_t* times,
+                                  const void* d_public_shares, const uint8_t* config_ids, const void* d_encs,
+                                  const uint64_t* enc_offsets, const void* d_payloads, const uint64_t* payload_offsets,
+                                  const void* d_prep_shares, uint64_t prep_share_stride, const void* d_verdicts,
+                                  const uint8_t* exclude, const uint8_t* agg_param, uint64_t agg_param_len,
+                                  uint32_t query_type, const uint8_t* batch_id, void* d_out, uint64_t capacity,
+                                  uint64_t* out_len, jx_leader_req** out_req) {
+  if (!e || !d_out || !out_len || !out_req) return JX_E_INVALID;
+  *out_req = nullptr;
+  LOCK(e);
+  if (prep_share_stride == 0) prep_share_stride = e->cfg.lps_bytes;
+  if (prep_share_stride < e->cfg.lps_bytes) return JX_E_INVALID;
+  const ReqIn in{n, (const uint8_t*)d_report_ids, (const uint8_t*)d_public_shares, (const uint8_t*)d_encs,
+                 (const uint8_t*)d_payloads, (const uint8_t*)d_prep_shares, (const uint8_t*)d_verdicts, times, config_ids,
+                 enc_offsets, payload_offsets, prep_share_stride, exclude, agg_param, agg_param_len, query_type, batch_id};
+  uint64_t bound = 0;
+  if (const int32_t rc = req_check(e, in, &bound)) return rc;
+  HIPCHK(e, hipSetDevice(e->device));
+  return req_encode_core(e, in, (uint8_t*)d_out, capacity, out_len, out_req, true);
+}
+
+int32_t jx_init_req_encode(jx_engine* e, uint64_t n, const uint8_t* report_ids, const uint64_t* times,
+                           const uint8_t* public_shares, const uint8_t* config_ids, const uint8_t* encs,
+                           const uint64_t* enc_offsets, const uint8_t* payloads, const uint64_t* payload_offsets,
+                           const uint8_t* prep_shares, uint64_t prep_share_stride, const uint8_t* verdicts,
+                           const uint8_t* exclude, const uint8_t* agg_param, uint64_t agg_param_len, uint32_t query_type,
+                           const uint8_t* batch_id, uint8_t* out, uint64_t capacity, uint64_t* out_len,
+                           jx_leader_req** out_req) {
+  if (!e || !out || !out_len || !out_req) return JX_E_INVALID;
+  *out_req = nullptr;
+  LOCK(e);
+  const Cfg& c = e->cfg;
+  if (prep_share_stride == 0) prep_share_stride = c.lps_bytes;
+  if (prep_share_stride < c.lps_bytes) return JX_E_INVALID;
+  ReqIn in{n, report_ids, public_shares, encs, payloads, prep_shares, verdicts, times, config_ids,
+           enc_offsets, payload_offsets, prep_share_stride, exclude, agg_param, agg_param_len, query_type, batch_id};
+  uint64_t bound = 0;
+  if (const int32_t rc = req_check(e, in, &bound)) return rc;
+  HIPCHK(e, hipSetDevice(e->device));
+  const uint64_t e0 = n && enc_offsets ? enc_offsets[0] : 0, e1 = n ? (enc_offsets ? enc_offsets[n] : 32 * n) : 0;
+  const uint64_t p0 = n ? payload_offsets[0] : 0, p1 = n ? payload_offsets[n] : 0;
+  uint8_t *d_ids = nullptr, *d_ps = nullptr, *d_encs = nullptr, *d_pay = nullptr, *d_lps = nullptr, *d_v = nullptr,
+          *d_body = nullptr;
+  auto lay = [&](void* base) {
+    Carver cv(base);
+    cv.take(d_ids, n * 16);
+    cv.take(d_ps, n * c.ps_bytes);
+    cv.take(d_encs, e1 - e0);
+    cv.take(d_pay, p1 - p0);
+    cv.take(d_lps, n * prep_share_stride);
+    cv.take(d_v, n);
+    cv.take(d_body, bound);
+    return cv.bytes();
+  };
+  Scratch mem;  // the call holds nothing else yet: it may wait for the arena
+  if (const int32_t rc = scratch_get(e, lay(nullptr), mem, true)) return rc;
+  lay(mem.p());
+  if (n) {
+    HIPCHK(e, hipMemcpyAsync(d_ids, report_ids, n * 16, hipMemcpyHostToDevice, e->stream));
+    if (c.ps_bytes) HIPCHK(e, hipMemcpyAsync(d_ps, public_shares, n * c.ps_bytes, hipMemcpyHostToDevice, e->stream));
+    if (e1 > e0) HIPCHK(e, hipMemcpyAsync(d_encs, encs + e0, e1 - e0, hipMemcpyHostToDevice, e->stream));
+    if (p1 > p0) HIPCHK(e, hipMemcpyAsync(d_pay, payloads + p0, p1 - p0, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(d_lps, prep_shares, (n - 1) * prep_share_stride + c.lps_bytes, hipMemcpyHostToDevice, e->stream));
+    HIPCHK(e, hipMemcpyAsync(d_v, verdicts, n, hipMemcpyHostToDevice, e->stream));
+  }
+  in.ids = d_ids;
+  in.ps = d_ps;
+  in.encs = d_encs - e0;  // the kernels index from the offset arrays' zero
+  in.payloads = d_pay - p0;
+  in.lps = d_lps;
+  in.verdicts = d_v;
+  uint64_t len = 0;
+  jx_leader_req* r = nullptr;
+  if (const int32_t rc = req_encode_core(e, in, d_body, bound, &len, &r, false)) return rc;
+  LeaderReqGuard g{r};
+  if (capacity < len) return fail(e, JX_E_INVALID, "init req encode: the output buffer is shorter than the request body");
+  HIPCHK(e, hipMemcpyAsync(out, d_body, len, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  *out_len = len;
+  *out_req = g.give();
+  return JX_OK;
+}
+
+int32_t jx_leader_req_info(const jx_leader_req* r, jx_leader_req_info_t* out) {
+  if (!r || !out) return JX_E_INVALID;
+  out->n = r->n;
+  out->n_sent = r->n_sent;
+  out->body_len = r->body_len;
+  return JX_OK;
+}
+
+int32_t jx_leader_req_sent(const jx_leader_req* r, const uint32_t** sent_index, const void** d_sent_index) {
+  if (!r) return JX_E_INVALID;
+  if (sent_index) *sent_index = r->sent_index;
+  if (d_sent_index) *d_sent_index = r->d_sent_index;
+  return JX_OK;
+}
+
+int32_t jx_init_resp_decode(jx_engine* e, jx_leader_req* r, const uint8_t* body, uint64_t len, void* d_out_prep_msgs,
+                            uint64_t prep_msg_stride, void* d_out_peer_verdicts, uint8_t* out_result, uint8_t* out_error,
+                            jx_init_resp_info_t* info) {
+  if (!e || !r || r->e != e || !info || (!body && len)) return JX_E_INVALID;
+  LOCK(e);
+  const Cfg& c = e->cfg;
+  const uint32_t PM = c.jr_len ? c.seed : 0;
+  const uint64_t n = r->n, ns = r->n_sent;
+  if (prep_msg_stride == 0) prep_msg_stride = PM;
+  if (prep_msg_stride < PM) return JX_E_INVALID;
+  if (n && (!d_out_peer_verdicts || (PM && !d_out_prep_msgs))) return JX_E_INVALID;
+  if (ns && (!out_result || !out_error)) return JX_E_INVALID;
+  *info = jx_init_resp_info_t{};
+  std::vector<WireRespRec> recs(ns ? ns : 1);
+  const WireWalk w = wire_resp_walk(body, len, recs.data(), ns);
+  info->n = w.n;
+  if (w.status != WIRE_OK) {
+    info->status = JX_WIRE_MALFORMED;
+    info->error_offset = w.err_off;
+    info->n = 0;
+    return JX_OK;
+  }
+  // "missing, duplicate, out-of-order, or unexpected prepare steps": the first position that differs
+  const uint64_t both = w.n < ns ? w.n : ns;
+  uint64_t bad = both;
+  for (uint64_t k = 0; k < both; k++)
+    if (memcmp(body + recs[k].off, r->sent_ids + 16 * k, 16) != 0) {
+      bad = k;
+      break;
+    }
+  if (bad < both || w.n != ns) {
+    info->status = JX_WIRE_RESP_MISMATCH;
+    info->mismatch_index = bad;
+    return JX_OK;
+  }
+  if (n == 0) return JX_OK;
+  HIPCHK(e, hipSetDevice(e->device));
+  const uint64_t rows_at = (len + 7) / 8 * 8;
+  void* hp = nullptr;
+  HIPCHK(e, r->up.reserve(rows_at + n * 8, &hp));
+  if (len) memcpy(hp, body, len);
+  uint64_t* pm_off = (uint64_t*)((uint8_t*)hp + rows_at);
+  for (uint64_t i = 0; i < n; i++) pm_off[i] = WIRE_RESP_NO_MESSAGE;
+  for (uint64_t k = 0; k < ns; k++) {
+    const uint8_t res = wire_resp_classify(recs[k], PM);
+    out_result[k] = res;
+    out_error[k] = res == RESP_CONTINUED ? (uint8_t)WIRE_ERR_NONE : res == RESP_REJECTED ? recs[k].error : (uint8_t)WIRE_ERR_VDAF_PREP;
+    if (res == RESP_CONTINUED) pm_off[r->sent_index[k]] = recs[k].pm_off;
+  }
+  Scratch mem;
+  if (const int32_t rc = scratch_get(e, rows_at + n * 8, mem, true)) return rc;
+  HIPCHK(e, hipMemcpyAsync(mem.p(), hp, rows_at + n * 8, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, r->up.mark(e->stream));
+  WireRespArgs a{};
+  a.n = n;
+  a.body = mem.p();
+  a.pm_off = (const uint64_t*)(mem.p() + rows_at);
+  a.pm_bytes = PM;
+  a.pm_stride = prep_msg_stride;
+  a.prep_msgs = (uint8_t*)d_out_prep_msgs;
+  a.peer_verdicts = (uint8_t*)d_out_peer_verdicts;
+  HIPCHK(e, launch_wire_resp_scatter(a, e->stream));
+  return JX_OK;
+}
+
+void jx_leader_req_release(jx_leader_req* r) {
+  if (!r) return;
+  std::lock_guard<FairMutex> lk(r->e->mu);
+  (void)hipSetDevice(r->e->device);
+  leader_req_free(r);
 }
 
 }  // extern "C"

@@ -334,6 +334,201 @@ inline WireWalk wire_walk(const uint8_t* body, const WireHeader& h, WireRec* rec
   return w;
 }
 
+// ---- the leader's end of the exchange: the request written, the response read.
+//
+// A PrepareInit the leader writes is id[16] || time u64 || u32 PS || public share || config id || u16 + encapsulated
+// key || u32 + payload || u32 M || 00 || u32 LPS || prep share, with M = 5 + LPS: 44 fixed bytes around four fields.
+constexpr uint32_t WIRE_INIT_FIXED = 44;
+JX_HD uint64_t wire_init_len(uint64_t PS, uint64_t enc_len, uint64_t pay_len, uint64_t LPS) {
+  return WIRE_INIT_FIXED + PS + enc_len + pay_len + LPS;
+}
+JX_HD uint64_t wire_req_header_len(uint64_t agg_param_len, uint32_t query_type) {
+  return 4 + agg_param_len + (query_type == WIRE_QUERY_FIXED_SIZE ? 33 : 1) + 4;
+}
+// where the four fields of a PrepareInit start, from the message's first byte
+struct WireInitLayout {
+  uint64_t ps_off, enc_off, pay_off, sh_off, len;
+};
+JX_HD WireInitLayout wire_init_layout(uint64_t PS, uint64_t enc_len, uint64_t pay_len, uint64_t LPS) {
+  WireInitLayout l;
+  l.ps_off = 28;
+  l.enc_off = l.ps_off + PS + 3;
+  l.pay_off = l.enc_off + enc_len + 4;
+  l.sh_off = l.pay_off + pay_len + 9;
+  l.len = l.sh_off + LPS;
+  return l;
+}
+// Fixed byte k < 44 of a PrepareInit: its value, and in *at where it lies from the message's first byte. The kernel
+// gives one k to a lane, the host writer loops over them.
+JX_HD uint8_t wire_init_fixed_byte(uint32_t k, const uint8_t* id, uint64_t time, uint32_t PS, uint8_t config_id,
+                                   uint32_t enc_len, uint32_t pay_len, uint32_t LPS, uint64_t* at) {
+  *at = (uint64_t)k + (k >= 28 ? PS : 0) + (k >= 31 ? enc_len : 0) + (k >= 35 ? (uint64_t)pay_len : 0);
+  if (k < 16) return id[k];
+  if (k < 24) return (uint8_t)(time >> (8 * (23 - k)));
+  if (k < 28) return (uint8_t)(PS >> (8 * (27 - k)));
+  if (k == 28) return config_id;
+  if (k < 31) return (uint8_t)(enc_len >> (8 * (30 - k)));
+  if (k < 35) return (uint8_t)(pay_len >> (8 * (34 - k)));
+  if (k < 39) return (uint8_t)((5 + LPS) >> (8 * (38 - k)));
+  if (k == 39) return 0;  // PingPongMessage::Initialize
+  return (uint8_t)(LPS >> (8 * (43 - k)));
+}
+JX_HD void wire_put_prepare_init_head(uint8_t* p, const uint8_t* id, uint64_t time, uint32_t PS, uint8_t config_id,
+                                      uint32_t enc_len, uint32_t pay_len, uint32_t LPS) {
+  for (uint32_t k = 0; k < WIRE_INIT_FIXED; k++) {
+    uint64_t at;
+    const uint8_t v = wire_init_fixed_byte(k, id, time, PS, config_id, enc_len, pay_len, LPS, &at);
+    p[at] = v;
+  }
+}
+// The request header at out: u32 + aggregation parameter || query type [|| batch id] || u32 vec_len. Returns its length.
+JX_HD uint64_t wire_put_req_header(uint8_t* out, const uint8_t* agg_param, uint32_t agg_param_len, uint32_t query_type,
+                                   const uint8_t* batch_id, uint32_t vec_len) {
+  wire_put32(out, agg_param_len);
+  uint64_t p = 4;
+  for (uint32_t i = 0; i < agg_param_len; i++) out[p++] = agg_param[i];
+  out[p++] = (uint8_t)query_type;
+  if (query_type == WIRE_QUERY_FIXED_SIZE)
+    for (int i = 0; i < 32; i++) out[p++] = batch_id[i];
+  wire_put32(out + p, vec_len);
+  return p + 4;
+}
+// What a request refuses before a byte is written: a field whose length has no place in its prefix, a vector whose
+// byte length does not fit a u32. All sums in 64 bits.
+enum : uint32_t { WIRE_REQ_OK = 0, WIRE_REQ_LONG_KEY = 1, WIRE_REQ_LONG_PAYLOAD = 2, WIRE_REQ_LONG_VECTOR = 3 };
+JX_HD uint32_t wire_req_field_check(uint64_t enc_len, uint64_t pay_len) {
+  if (enc_len >= (1ull << 16)) return WIRE_REQ_LONG_KEY;
+  if (pay_len >= (1ull << 32)) return WIRE_REQ_LONG_PAYLOAD;
+  return WIRE_REQ_OK;
+}
+// The body's length for the reports with send[i] != 0 (send nullable: all), from the offset arrays alone (enc_offsets
+// nullable: 32 bytes each). *total is valid when WIRE_REQ_OK is returned.
+inline uint32_t wire_req_total(uint64_t n, uint64_t PS, uint64_t LPS, const uint64_t* enc_offsets,
+                               const uint64_t* payload_offsets, const uint8_t* send, uint64_t agg_param_len,
+                               uint32_t query_type, uint64_t* total) {
+  uint64_t vec = 0;
+  for (uint64_t i = 0; i < n; i++) {
+    const uint64_t el = enc_offsets ? enc_offsets[i + 1] - enc_offsets[i] : 32;
+    const uint64_t pl = payload_offsets[i + 1] - payload_offsets[i];
+    if (const uint32_t bad = wire_req_field_check(el, pl)) return bad;
+    if (send && !send[i]) continue;
+    vec += wire_init_len(PS, el, pl, LPS);  // < 2^33 each: no wrap below 2^31 reports
+    if (vec > 0xFFFFFFFFull) return WIRE_REQ_LONG_VECTOR;
+  }
+  *total = wire_req_header_len(agg_param_len, query_type) + vec;
+  return WIRE_REQ_OK;
+}
+
+// One PrepareResp of an AggregationJobResp body (messages/src/lib.rs:2270-2333, :2361-2368): id[16] || tag, then
+// Continue (0): u32 M + exactly one PingPongMessage; Finished (1): nothing; Reject (2): a PrepareError code point <= 9.
+struct WireRespRec {
+  uint64_t off, len;   // the whole PrepareResp
+  uint64_t pm_off;     // Continue: the prep message of a Continue / Finish ping-pong message (else where it would start)
+  uint32_t pm_len, sh_len;
+  uint8_t tag, pp_type, error, pad_[5];
+};
+static_assert(sizeof(WireRespRec) == 40, "WireRespRec is plain bytes");
+constexpr uint32_t WIRE_MAX_PREPARE_ERROR = 9;
+
+// False: it does not parse, *err_off is the read that failed (an unknown tag, error code or ping-pong type: that byte;
+// bytes left over inside the message: the first of them).
+JX_HD bool wire_parse_prepare_resp(const uint8_t* body, uint64_t lim, uint64_t off, WireRespRec& r, uint64_t* err_off) {
+  WireCur c{body, off, lim, true};
+  r = WireRespRec{};
+  r.off = off;
+  if (wire_need(c, 16)) c.pos += 16;
+  const uint64_t tag_at = c.pos;
+  r.tag = (uint8_t)wire_u8(c);
+  if (!c.ok) {
+    *err_off = c.pos;
+    return false;
+  }
+  if (r.tag > 2) {
+    *err_off = tag_at;
+    return false;
+  }
+  if (r.tag == 1) {
+    r.len = c.pos - off;
+    return true;
+  }
+  if (r.tag == 2) {
+    const uint64_t e_at = c.pos;
+    r.error = (uint8_t)wire_u8(c);
+    if (!c.ok || r.error > WIRE_MAX_PREPARE_ERROR) {
+      *err_off = e_at;
+      return false;
+    }
+    r.len = c.pos - off;
+    return true;
+  }
+  uint64_t msg_off;
+  uint32_t msg_len;
+  wire_opaque(c, 4, msg_off, msg_len);
+  if (!c.ok) {
+    *err_off = c.pos;
+    return false;
+  }
+  r.len = c.pos - off;
+  WireCur m{body, msg_off, msg_off + msg_len, true};
+  const uint64_t type_at = m.pos;
+  r.pp_type = (uint8_t)wire_u8(m);
+  if (m.ok && r.pp_type > 2) {
+    *err_off = type_at;
+    return false;
+  }
+  r.pm_off = m.pos;
+  uint64_t sh_off;
+  if (r.pp_type >= 1) wire_opaque(m, 4, r.pm_off, r.pm_len);
+  if (r.pp_type <= 1) wire_opaque(m, 4, sh_off, r.sh_len);
+  if (!m.ok || m.pos != m.lim) {
+    *err_off = m.pos;
+    return false;
+  }
+  return true;
+}
+
+// The sequential walk of a response body: the u32 byte length of the PrepareResps, which must end where the body
+// ends, then the messages to the end. recs (nullable) takes up to cap records; n counts them all.
+inline WireWalk wire_resp_walk(const uint8_t* body, uint64_t len, WireRespRec* recs, uint64_t cap) {
+  WireWalk w{WIRE_OK, 0, 0};
+  WireCur c{body, 0, len, true};
+  uint64_t start;
+  uint32_t vl;
+  wire_opaque(c, 4, start, vl);
+  if (!c.ok) {
+    w.status = WIRE_MALFORMED;
+    w.err_off = c.pos;
+    return w;
+  }
+  const uint64_t end = start + vl;
+  if (end != len) {  // bytes after the vector
+    w.status = WIRE_MALFORMED;
+    w.err_off = end;
+    return w;
+  }
+  uint64_t off = start;
+  while (off < end) {
+    WireRespRec r;
+    if (!wire_parse_prepare_resp(body, end, off, r, &w.err_off)) {
+      w.status = WIRE_MALFORMED;
+      return w;
+    }
+    if (recs && w.n < cap) recs[w.n] = r;
+    w.n++;
+    off += r.len;
+  }
+  return w;
+}
+
+// What a one-round leader makes of a PrepareResp (aggregation_job_driver.rs:584-663). PM: its prep-message length.
+enum : uint8_t { RESP_CONTINUED = 0, RESP_REJECTED = 1, RESP_FINISHED = 2, RESP_MESSAGE_MISMATCH = 3 };
+JX_HD uint8_t wire_resp_classify(const WireRespRec& r, uint32_t PM) {
+  if (r.tag == 2) return RESP_REJECTED;  // the helper's PrepareError: r.error
+  if (r.tag == 1) return RESP_FINISHED;  // finish_mismatch: a one-round leader still waits for a message
+  return r.pp_type == 2 && r.pm_len == PM ? RESP_CONTINUED : RESP_MESSAGE_MISMATCH;
+}
+constexpr uint64_t WIRE_RESP_NO_MESSAGE = ~0ull;  // a row of the leader batch without a continued response
+
 // ---- what the kernels of jx_wire.hip and the engine (jx_engine_wire.cpp) share
 constexpr uint32_t WIRE_NO_DUPLICATE = 0xFFFFFFFFu;
 
@@ -379,7 +574,47 @@ struct WireEncodeArgs {
   uint8_t* out;
 };
 
+// The leader's request encode. The host arrays of the call (times .. exclude) are device copies here.
+struct WireReqTotals {
+  uint64_t vec_bytes;  // the PrepareInits of the reports that are sent
+  uint64_t n_sent;
+};
+struct WireReqArgs {
+  uint64_t n;
+  const uint8_t *ids, *ps, *encs, *payloads, *lps, *verdicts;
+  const uint64_t* times;
+  const uint8_t* config_ids;
+  const uint64_t *enc_offsets, *payload_offsets;  // enc_offsets nullable: 32 bytes each
+  const uint8_t* exclude;                         // nullable
+  uint32_t ps_bytes, lps_bytes;
+  uint64_t lps_stride;
+  const uint8_t *agg_param, *batch_id;  // device copies: agg_param_len bytes, 32 bytes (FixedSize)
+  uint32_t agg_param_len, query_type;
+  uint64_t header_len;
+  uint64_t* msg_len;           // [n]: the PrepareInit's length, 0 when the report is not sent
+  uint8_t* send;               // [n]
+  uint64_t *offsets, *rank;    // [n + 1]: exclusive scans of msg_len and of send
+  uint32_t* sent_index;        // [n]: sent_index[rank[i]] = i for the reports sent
+  uint8_t* sent_ids;           // [n x 16]: the id of sent report k
+  WireReqTotals* totals;
+  uint8_t* out;
+};
+
+// The leader's response decode: what the host walk found, per row of the leader batch.
+struct WireRespArgs {
+  uint64_t n;
+  const uint8_t* body;
+  const uint64_t* pm_off;  // [n]: where row i's prep message lies in body, WIRE_RESP_NO_MESSAGE when it has none
+  uint32_t pm_bytes;
+  uint64_t pm_stride;
+  uint8_t *prep_msgs, *peer_verdicts;
+};
+
 #if defined(__HIPCC__) || defined(__HIP__)
+// select + the two scans + the compaction list; the host reads a.totals, then packs n_sent reports
+hipError_t launch_wire_req_sizes(const WireReqArgs& a, hipStream_t s);
+hipError_t launch_wire_req_pack(const WireReqArgs& a, uint64_t n_sent, uint32_t vec_bytes, hipStream_t s);
+hipError_t launch_wire_resp_scatter(const WireRespArgs& a, hipStream_t s);
 hipError_t launch_wire_header(const uint8_t* body, uint64_t len, uint32_t query_type, WireState* st, hipStream_t s);
 // the fast pass over `cands` candidates (fast: not yet run for this body) and the fallback loop; offs / cap: where the
 // starts of the messages the fallback accepts go (null: only count them)

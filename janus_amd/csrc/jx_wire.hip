@@ -11,6 +11,11 @@
 //
 // Encode: one thread per report decides its outcome (wire_outcome) and length, one workgroup scans the lengths, one
 // thread per report writes its PrepareResp.
+//
+// The leader's end: the request body is written by wire_req_select_kernel (which reports are sent, how long each is),
+// wire_req_scan_kernel (one workgroup: both exclusive scans and the compaction list) and wire_req_pack_kernel (one wave
+// per sent report); the response body is walked on the host (jx_engine_wire.cpp) and wire_resp_scatter_kernel writes
+// every row's prep message and peer verdict from what the walk found.
 #include <hip/hip_runtime.h>
 
 #include "../../include/jx_prio3.h"
@@ -262,9 +267,94 @@ __global__ __launch_bounds__(256) void wire_resp_pack_kernel(WireEncodeArgs a) {
   for (uint32_t k = 0; k < S; k++) p[26 + k] = m[k];
 }
 
+// ---- the leader's request: which reports are sent and how long each is, the scans, one wave per sent report
+__global__ __launch_bounds__(256) void wire_req_select_kernel(WireReqArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  const bool send = a.verdicts[i] == JX_FINISHED && !(a.exclude && a.exclude[i]);
+  const uint64_t el = a.enc_offsets ? a.enc_offsets[i + 1] - a.enc_offsets[i] : 32;
+  const uint64_t pl = a.payload_offsets[i + 1] - a.payload_offsets[i];
+  a.send[i] = send;
+  a.msg_len[i] = send ? wire_init_len(a.ps_bytes, el, pl, a.lps_bytes) : 0;
+}
+
+__global__ __launch_bounds__(1024) void wire_req_scan_kernel(WireReqArgs a) {
+  block_exclusive_scan(a.n, [&](uint64_t i) { return a.msg_len[i]; }, a.offsets);
+  block_exclusive_scan(a.n, [&](uint64_t i) { return (uint64_t)a.send[i]; }, a.rank);
+  // the compaction list: thread t reads back the ranks of i = t, t + 1024, .., which it stored itself
+  for (uint64_t i = threadIdx.x; i < a.n; i += 1024)
+    if (a.send[i]) a.sent_index[a.rank[i]] = (uint32_t)i;
+  if (threadIdx.x == 0) {
+    a.totals->vec_bytes = a.offsets[a.n];
+    a.totals->n_sent = a.rank[a.n];
+  }
+}
+
+// Wave k writes sent report k = report sent_index[k] at header_len + offsets[i]: the 44 fixed bytes one per lane, the
+// four fields with wave_copy. Every destination offset is arbitrary mod 16. Thread 0 of the grid writes the header.
+__global__ __launch_bounds__(256) void wire_req_pack_kernel(WireReqArgs a, uint64_t n_sent, uint32_t vec_bytes) {
+  if (blockIdx.x == 0 && threadIdx.x == 0)
+    (void)wire_put_req_header(a.out, a.agg_param, a.agg_param_len, a.query_type, a.batch_id, vec_bytes);
+  const uint64_t k = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const uint32_t lane = threadIdx.x & 63u;
+  if (k >= n_sent) return;
+  const uint64_t i = a.sent_index[k];
+  const uint64_t eo = a.enc_offsets ? a.enc_offsets[i] : 32 * i;
+  const uint32_t el = a.enc_offsets ? (uint32_t)(a.enc_offsets[i + 1] - eo) : 32u;
+  const uint64_t po = a.payload_offsets[i];
+  const uint32_t pl = (uint32_t)(a.payload_offsets[i + 1] - po);  // the host refused a field its prefix cannot hold
+  const WireInitLayout l = wire_init_layout(a.ps_bytes, el, pl, a.lps_bytes);
+  uint8_t* p = a.out + a.header_len + a.offsets[i];
+  const uint8_t* id = a.ids + 16 * i;
+  if (lane < WIRE_INIT_FIXED) {
+    uint64_t at;
+    const uint8_t v = wire_init_fixed_byte(lane, id, a.times[i], a.ps_bytes, a.config_ids[i], el, pl, a.lps_bytes, &at);
+    p[at] = v;
+  }
+  if (lane < 16) a.sent_ids[16 * k + lane] = id[lane];
+  if (a.ps_bytes) wave_copy(p + l.ps_off, a.ps + i * a.ps_bytes, a.ps_bytes, lane);
+  wave_copy(p + l.enc_off, a.encs + eo, el, lane);
+  wave_copy(p + l.pay_off, a.payloads + po, pl, lane);
+  wave_copy(p + l.sh_off, a.lps + i * a.lps_stride, a.lps_bytes, lane);
+}
+
+// ---- the leader's response: one thread per row of the leader batch. A row without a continued response (never
+// sent, rejected, Finished, a message of another kind or length) gets a non-zero peer verdict and a zero prep message,
+// so the finish can never mark it finished; each row is written by one thread, so no write meets another.
+__global__ __launch_bounds__(256) void wire_resp_scatter_kernel(WireRespArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n) return;
+  const uint64_t off = a.pm_off[i];
+  const bool continued = off != WIRE_RESP_NO_MESSAGE;
+  a.peer_verdicts[i] = continued ? 0 : 1;
+  uint8_t* row = a.prep_msgs + i * a.pm_stride;
+  for (uint32_t b = 0; b < a.pm_bytes; b++) row[b] = continued ? a.body[off + b] : (uint8_t)0;
+}
+
 inline uint32_t blocks(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
 
 }  // namespace
+
+hipError_t launch_wire_req_sizes(const WireReqArgs& a, hipStream_t s) {
+  if (a.n) {
+    hipLaunchKernelGGL(wire_req_select_kernel, dim3(blocks(a.n, 256)), dim3(256), 0, s, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(wire_req_scan_kernel, dim3(1), dim3(1024), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t launch_wire_req_pack(const WireReqArgs& a, uint64_t n_sent, uint32_t vec_bytes, hipStream_t s) {
+  hipLaunchKernelGGL(wire_req_pack_kernel, dim3(blocks(n_sent ? n_sent : 1, 4)), dim3(256), 0, s, a, n_sent, vec_bytes);
+  return hipGetLastError();
+}
+
+hipError_t launch_wire_resp_scatter(const WireRespArgs& a, hipStream_t s) {
+  if (a.n == 0) return hipSuccess;
+  hipLaunchKernelGGL(wire_resp_scatter_kernel, dim3(blocks(a.n, 256)), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
 
 hipError_t launch_wire_header(const uint8_t* body, uint64_t len, uint32_t query_type, WireState* st, hipStream_t s) {
   hipLaunchKernelGGL(wire_header_kernel, dim3(1), dim3(1), 0, s, body, len, query_type, st);

@@ -248,6 +248,62 @@ class InitReq:
         self.release()
 
 
+WIRE_RESP_MISMATCH = 4         # JX_WIRE_RESP_MISMATCH: the response's PrepareResps are not the sent reports in order
+RESP_CONTINUED, RESP_REJECTED, RESP_FINISHED, RESP_MESSAGE_MISMATCH = 0, 1, 2, 3  # JX_RESP_*
+
+
+class LeaderReq:
+    """An encoded AggregationJobInitializeReq (jx_leader_req): `body` (bytes; the device form copies it from its
+    device buffer `d_body`, a torch uint8 tensor, when first asked), `body_len`, `n` (rows of the leader batch),
+    `n_sent` and `sent_index` (numpy uint32[n_sent]: sent report k is row sent_index[k]; `d_sent_index` is the same
+    list on the device). Holds device memory until release() (or the end of a `with`), which must come before the
+    engine's close()."""
+
+    def __init__(self, engine: "HelperEngine", handle, body: bytes | None = None, d_body=None):
+        self._engine, self._h = engine, handle
+        L = engine._L
+        info = _lib.JxLeaderReqInfo()
+        check(L.jx_leader_req_info(handle, ctypes.byref(info)), engine._h, "jx_leader_req_info")
+        self.n, self.n_sent, self.body_len = int(info.n), int(info.n_sent), int(info.body_len)
+        hp, dp = ctypes.c_void_p(), ctypes.c_void_p()
+        check(L.jx_leader_req_sent(handle, ctypes.byref(hp), ctypes.byref(dp)), engine._h, "jx_leader_req_sent")
+        self.d_sent_index = dp.value
+        if self.n_sent:
+            buf = (ctypes.c_uint8 * (4 * self.n_sent)).from_address(hp.value)
+            self.sent_index = np.frombuffer(buf, dtype=np.uint32, count=self.n_sent).copy()
+        else:
+            self.sent_index = np.zeros(0, np.uint32)
+        self._body, self.d_body = body, d_body
+
+    @property
+    def body(self) -> bytes:
+        if self._body is None:
+            self._body = self.d_body[:self.body_len].cpu().numpy().tobytes()
+        return self._body
+
+    def release(self):
+        if self._h:
+            self._engine._L.jx_leader_req_release(self._h)
+            self._h = None
+            self.d_sent_index = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.release()
+
+
+@dataclass
+class InitRespDecode:
+    status: int                # WIRE_OK, WIRE_MALFORMED or WIRE_RESP_MISMATCH
+    results: np.ndarray        # uint8[n_sent]: RESP_* per response (meaningful when status is WIRE_OK)
+    errors: np.ndarray         # uint8[n_sent]: the PrepareError code point, WIRE_NO_ERROR where continued
+    error_offset: int = 0      # WIRE_MALFORMED: the read that failed
+    mismatch_index: int = 0    # WIRE_RESP_MISMATCH: the first position that differs
+    n: int = 0                 # PrepareResps in the body
+
+
 class HelperEngine:
     """One engine per (Prio3 instance, verify key, GPU). Serves the helper role (the north-star
     path) and the leader role of the same ping-pong exchange."""
@@ -931,6 +987,119 @@ class HelperEngine:
                                              _ptr(he), _ptr(rp), _ptr(out), cap, ctypes.byref(ln), _ptr(fin))
             check(st, self._h, "jx_init_resp_encode")
         return out[:ln.value].tobytes(), fin[:n].astype(bool)
+
+    # ------------------------------------------------------------------ the leader's end of the wire
+    def _req_host_arrays(self, n: int, times, config_ids, enc_offsets, payload_offsets, exclude, agg_param, query_type,
+                         batch_id):
+        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
+        cf = np.ascontiguousarray(np.asarray(config_ids, dtype=np.uint8).reshape(n)) if n else np.zeros(1, np.uint8)
+        off = np.ascontiguousarray(np.asarray(payload_offsets, dtype=np.uint64).reshape(n + 1))
+        eoff = None if enc_offsets is None else np.ascontiguousarray(np.asarray(enc_offsets, dtype=np.uint64).reshape(n + 1))
+        ex = None if exclude is None or not n else np.ascontiguousarray(np.asarray(exclude).astype(np.uint8).reshape(n))
+        par = np.frombuffer(bytes(agg_param) or b"\0", np.uint8)
+        if query_type == 2 and (batch_id is None or len(batch_id) != 32):
+            raise ValueError("FixedSize carries a 32-byte batch id")
+        bid = None if batch_id is None else np.frombuffer(bytes(batch_id), np.uint8)
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        return (tm.ctypes.data_as(u64p), _ptr(cf), eoff.ctypes.data_as(u64p) if eoff is not None else None,
+                off.ctypes.data_as(u64p), _ptr(ex), _ptr(par), len(agg_param), query_type, _ptr(bid)), (tm, cf, off, eoff, ex, par, bid)
+
+    def init_req_bound(self, n: int, payload_offsets, agg_param_len: int, query_type: int, enc_offsets=None) -> int:
+        """The length of the request body if every report were sent (jx_init_req_encode_bound)."""
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        off = np.ascontiguousarray(np.asarray(payload_offsets, dtype=np.uint64).reshape(n + 1))
+        eoff = None if enc_offsets is None else np.ascontiguousarray(np.asarray(enc_offsets, dtype=np.uint64).reshape(n + 1))
+        out = ctypes.c_uint64()
+        check(self._L.jx_init_req_encode_bound(self._h, n, eoff.ctypes.data_as(u64p) if eoff is not None else None,
+                                               off.ctypes.data_as(u64p), agg_param_len, query_type, ctypes.byref(out)),
+              self._h, "jx_init_req_encode_bound")
+        return out.value
+
+    def _leader_req(self, h, body=None, d_body=None) -> LeaderReq:
+        req = LeaderReq(self, h, body, d_body)
+        with self._lock:
+            if not hasattr(self, "_init_reqs"):
+                self._init_reqs = weakref.WeakSet()
+            self._init_reqs.add(req)
+        return req
+
+    def encode_init_req(self, n: int, d_report_ids: int, times, d_public_shares: int | None, config_ids, d_encs: int,
+                        d_payloads: int, payload_offsets, d_prep_shares: int, d_verdicts: int, agg_param: bytes = b"",
+                        query_type: int = 1, batch_id: bytes | None = None, enc_offsets=None, exclude=None,
+                        prep_share_stride: int = 0, d_out: int | None = None, capacity: int = 0, stream=None) -> LeaderReq:
+        """The AggregationJobInitializeReq body of a leader job, written on the GPU (jx_init_req_encode_device) from
+        the arrays the leader holds: device pointers for the report ids, public shares, encapsulated keys and payloads
+        (packed; enc_offsets None: n x 32 bytes), the prep shares and verdicts leader_init_device wrote; host arrays
+        for times, config_ids, the offset arrays and exclude (a mask of reports not to send). Report i is sent iff its
+        verdict is FINISHED and it is not excluded. Without d_out the body goes to a device buffer of the bound that
+        the returned LeaderReq keeps (d_body); with d_out (a device buffer of `capacity` bytes) it is written there.
+        Ordered against `stream` like the other device-pointer methods; waits for its result."""
+        args, keep = self._req_host_arrays(n, times, config_ids, enc_offsets, payload_offsets, exclude, agg_param,
+                                           query_type, batch_id)
+        d_body = None
+        if d_out is None:
+            import torch
+
+            capacity = self.init_req_bound(n, payload_offsets, len(agg_param), query_type, enc_offsets)
+            d_body = torch.empty(capacity, dtype=torch.uint8, device=torch.device("cuda", self.device))
+            d_out = d_body.data_ptr()
+        ln, h = ctypes.c_uint64(), ctypes.c_void_p()
+        tm, cf, eoff, off, ex, par, plen, q, bid = args
+        with self._ordered(stream):
+            st = self._L.jx_init_req_encode_device(self._h, n, d_report_ids, tm, d_public_shares, cf, d_encs, eoff,
+                                                   d_payloads, off, d_prep_shares, prep_share_stride, d_verdicts, ex,
+                                                   par, plen, q, bid, d_out, capacity, ctypes.byref(ln), ctypes.byref(h))
+            check(st, self._h, "jx_init_req_encode_device")
+        del keep
+        if d_body is None and ln.value:  # the caller's buffer, as torch sees it
+            import torch
+
+            d_body = torch.as_tensor(_DeviceBytes(d_out, ln.value), device=torch.device("cuda", self.device))
+        return self._leader_req(h, None, d_body)
+
+    def encode_init_req_host(self, report_ids, times, public_shares, config_ids, encs, payloads, payload_offsets,
+                             prep_shares, verdicts, agg_param: bytes = b"", query_type: int = 1,
+                             batch_id: bytes | None = None, enc_offsets=None, exclude=None) -> LeaderReq:
+        """The same from host arrays (jx_init_req_encode): encs and payloads are the packed byte arrays the offset
+        arrays index, prep_shares rows of prep_share_len bytes. The body is returned in host memory."""
+        if isinstance(report_ids, (bytes, bytearray)):
+            report_ids = np.frombuffer(report_ids, np.uint8)
+        n = int(np.asarray(report_ids).size // 16)
+        ids = _u8(report_ids, n, 16, "report_ids") if n else np.zeros((1, 16), np.uint8)
+        ps = _u8(public_shares, n, self.public_share_len, "public_shares")
+        lps = _u8(prep_shares, n, self.prep_share_len, "prep_shares")
+        vd = np.ascontiguousarray(np.asarray(verdicts, dtype=np.uint8).reshape(n)) if n else np.zeros(1, np.uint8)
+        en = np.ascontiguousarray(np.frombuffer(bytes(encs) or b"\0", np.uint8))
+        pay = np.ascontiguousarray(np.frombuffer(bytes(payloads) or b"\0", np.uint8))
+        args, keep = self._req_host_arrays(n, times, config_ids, enc_offsets, payload_offsets, exclude, agg_param,
+                                           query_type, batch_id)
+        tm, cf, eoff, off, ex, par, plen, q, bid = args
+        cap = self.init_req_bound(n, payload_offsets, len(agg_param), query_type, enc_offsets)
+        out = np.zeros(cap, np.uint8)
+        ln, h = ctypes.c_uint64(), ctypes.c_void_p()
+        st = self._L.jx_init_req_encode(self._h, n, _ptr(ids), tm, _ptr(ps) if self.public_share_len else None, cf,
+                                        _ptr(en), eoff, _ptr(pay), off, _ptr(lps), 0, _ptr(vd), ex, par, plen, q, bid,
+                                        _ptr(out), cap, ctypes.byref(ln), ctypes.byref(h))
+        check(st, self._h, "jx_init_req_encode")
+        del keep
+        return self._leader_req(h, out[:ln.value].tobytes())
+
+    def decode_init_resp(self, req: LeaderReq, body: bytes, d_out_prep_msgs: int | None, d_out_peer_verdicts: int | None,
+                         prep_msg_stride: int = 0, stream=None) -> InitRespDecode:
+        """The helper's AggregationJobResp body for an encoded request (jx_init_resp_decode): the body is walked and
+        matched against the sent reports on the host; for an accepted one the prep messages and peer verdicts of all
+        req.n rows are queued into the device arrays leader_finish_device reads. Raises nothing for a refused
+        response (see the status); a refused response writes nothing."""
+        b = np.frombuffer(bytes(body) or b"\0", np.uint8)
+        res = np.full(max(req.n_sent, 1), 0xFF, np.uint8)
+        err = np.full(max(req.n_sent, 1), 0xFF, np.uint8)
+        info = _lib.JxInitRespInfo()
+        with self._ordered(stream):
+            st = self._L.jx_init_resp_decode(self._h, req._h, _ptr(b), len(body), d_out_prep_msgs, prep_msg_stride,
+                                             d_out_peer_verdicts, _ptr(res), _ptr(err), ctypes.byref(info))
+            check(st, self._h, "jx_init_resp_decode")
+        return InitRespDecode(int(info.status), res[:req.n_sent], err[:req.n_sent], int(info.error_offset),
+                              int(info.mismatch_index), int(info.n))
 
     # ------------------------------------------------------------------ aggregation state
     def aggregate_share(self, segment: int = 0) -> tuple[bytes, int, bytes]:
