@@ -14,6 +14,10 @@
  *   /root/reference/aggregator/src/aggregator/aggregate_share.rs:55-96.
  * This ABI replaces that loop body with one call per batch. HPKE-open, plaintext
  * decode, replay / collected-batch checks and the datastore stay on the host.
+ * Further entry points cover the rest of a report's path on the device: sealed input shares opened inside the
+ * prepare calls, the leader's upload open, the client's shard and seal, the aggregate-init request and response as
+ * wire bytes at both ends, and the upload message itself: jx_report_encode* writes the client's Report bodies,
+ * jx_upload_decode* cuts the leader's uploads into the arrays the upload open and the request encode read.
  *
  * Conventions:
  *  - Every function returns int32 status: 0 = OK, < 0 = engine error (JX_E_*).
@@ -641,6 +645,100 @@ int32_t jx_init_resp_decode(jx_engine* e, jx_leader_req* r, const uint8_t* body,
                             jx_init_resp_info_t* info);
 void jx_leader_req_release(jx_leader_req* r);
 
+/* ---- The upload message on the device: the DAP Report a client sends the leader (messages/src/lib.rs:1353-1432),
+ *   id[16] || time u64 BE || u32 + public share || config id u8 || u16 + encapsulated key || u32 + payload ||
+ *   config id u8 || u16 + encapsulated key || u32 + payload     (the leader's ciphertext, then the helper's),
+ * written from the rows jx_client_seal_* left on the device and cut into the arrays jx_leader_upload_open_device and
+ * jx_init_req_encode_device read, so that a report's 100+ KB never cross the host one report at a time.
+ *
+ * jx_report_encode* (the client) writes n Report bodies back to back into out (capacity bytes) from report ids
+ * [n x 16], times[n] (a HOST array in both forms, as in the seal), public-share rows [n x PS] (NULL when PS is 0),
+ * leader and helper encapsulated-key rows [n x leader_enc_len] / [n x helper_enc_len], the two ciphertext row arrays
+ * of jx_client_seal_sizes' lengths, one config id per recipient and the seal's status (nullable). Report i lies at
+ * out + offsets[i], offsets[n] is the total (also *out_len); a report whose status is non-zero takes no room
+ * (offsets[i + 1] == offsets[i]). The offsets go to d_out_offsets (device, n + 1, nullable) and out_offsets (host,
+ * n + 1, nullable). An encapsulated key of 2^16 bytes or more, or bodies longer than `capacity`, are JX_E_INVALID
+ * before a byte is written; jx_report_encode_bound gives the length if every report takes room. The calls wait for
+ * their result: the length is part of it.
+ *
+ * jx_upload_decode* (the leader) takes n upload bodies back to back (len bytes) with the HOST array body_offsets
+ * [n + 1]: every upload is an HTTP body of its own, so the boundaries are known. Per upload, first failing check first:
+ * the parse (Report::get_decoded: every field inside the body, nothing left over), the handler's three time checks in
+ * its order (aggregator.rs:1544-1573; both sums saturate at 2^64 - 1, which decides as the unbounded sum does), the
+ * public share's length against the engine's PS (the reference's DecodeFailure, :1580-1593). There is no duplicate-id
+ * check: the reference's upload has none (the report writer's unique constraint does it). key_first / key_second map
+ * the LEADER ciphertext's config id to keypair slots, as in jx_init_req_decode.
+ * The handle gives, for all n: report id, time, upload_status and row_of (JX_UPLOAD_NO_ROW when not accepted; id and
+ * time are zeros when the body has fewer than 24 bytes); and for the m accepted reports, dense and in order, exactly
+ * what jx_leader_upload_open_device and jx_init_req_encode_device take: index[m] (accepted report k is upload
+ * index[k]), ids, times, public-share rows, key_index[m x 2], the leader's encapsulated keys and payloads packed with
+ * their offset arrays [m + 1], the helper's config_ids[m], encapsulated keys and payloads packed with theirs. The host
+ * pointers of jx_upload_req_arrays are one pinned copy made by the decode. After the call the bodies are no longer
+ * read. Decreasing body_offsets or an offset past len: JX_E_INVALID; n >= 2^31 - 1: JX_E_UNSUPPORTED; both with
+ * nothing queued. The device form's inputs are ordered by the Conventions; the call waits for its own results (m is
+ * one). A handle holds arena memory until jx_upload_req_release, which must come before jx_engine_destroy. */
+#define JX_UPLOAD_OK 0
+#define JX_UPLOAD_MALFORMED 1         /* the reference answers that upload with invalidMessage */
+#define JX_UPLOAD_TOO_EARLY 2         /* time > now + tolerable_clock_skew */
+#define JX_UPLOAD_TASK_EXPIRED 3      /* time > task_expiration */
+#define JX_UPLOAD_EXPIRED 4           /* now > time + report_expiry_age */
+#define JX_UPLOAD_ODD_PUBLIC_SHARE 5  /* the public share is not PS bytes */
+#define JX_UPLOAD_NO_ROW 0xFFFFFFFFu
+typedef struct jx_upload_req jx_upload_req;
+typedef struct jx_upload_checks {
+  uint64_t now, tolerable_clock_skew;
+  uint32_t has_task_expiration;
+  uint64_t task_expiration;
+  uint32_t has_report_expiry_age;
+  uint64_t report_expiry_age;
+} jx_upload_checks;
+typedef struct jx_upload_req_info_t {
+  uint64_t n, m; /* uploads; accepted */
+  uint64_t leader_enc_bytes, leader_payload_bytes, helper_enc_bytes, helper_payload_bytes;
+  uint64_t status_count[6]; /* uploads by JX_UPLOAD_* */
+} jx_upload_req_info_t;
+typedef struct jx_upload_req_arrays_t {
+  /* on the device; the m accepted reports */
+  const void *d_index, *d_report_ids, *d_times, *d_public_shares, *d_key_index, *d_leader_encs, *d_leader_enc_offsets,
+      *d_leader_payloads, *d_leader_payload_offsets, *d_helper_config_ids, *d_helper_encs, *d_helper_enc_offsets,
+      *d_helper_payloads, *d_helper_payload_offsets;
+  /* on the device; all n uploads */
+  const void *d_all_report_ids, *d_all_times, *d_upload_status, *d_row_of;
+  /* the pinned host copy */
+  const uint32_t* index;
+  const uint64_t* times;
+  const uint8_t* key_index;
+  const uint64_t *leader_enc_offsets, *leader_payload_offsets, *helper_enc_offsets, *helper_payload_offsets;
+  const uint8_t* helper_config_ids;
+  const uint8_t* all_report_ids;
+  const uint64_t* all_times;
+  const uint8_t* upload_status;
+  const uint32_t* row_of;
+} jx_upload_req_arrays_t;
+int32_t jx_report_encode_bound(const jx_engine* e, uint64_t n, uint32_t leader_enc_len, uint32_t helper_enc_len,
+                               uint64_t* out_bound);
+int32_t jx_report_encode_device(jx_engine* e, uint64_t n, const void* d_report_ids, const uint64_t* times,
+                                const void* d_public_shares, const void* d_leader_encs, uint32_t leader_enc_len,
+                                const void* d_leader_cts, const void* d_helper_encs, uint32_t helper_enc_len,
+                                const void* d_helper_cts, uint8_t leader_config_id, uint8_t helper_config_id,
+                                const void* d_seal_status, void* d_out, uint64_t capacity, void* d_out_offsets,
+                                uint64_t* out_offsets, uint64_t* out_len);
+int32_t jx_report_encode(jx_engine* e, uint64_t n, const uint8_t* report_ids, const uint64_t* times,
+                         const uint8_t* public_shares, const uint8_t* leader_encs, uint32_t leader_enc_len,
+                         const uint8_t* leader_cts, const uint8_t* helper_encs, uint32_t helper_enc_len,
+                         const uint8_t* helper_cts, uint8_t leader_config_id, uint8_t helper_config_id,
+                         const uint8_t* seal_status, uint8_t* out, uint64_t capacity, uint64_t* out_offsets,
+                         uint64_t* out_len);
+int32_t jx_upload_decode_device(jx_engine* e, const void* d_bodies, uint64_t len, uint64_t n, const uint64_t* body_offsets,
+                                const jx_upload_checks* checks, const uint8_t key_first[256],
+                                const uint8_t key_second[256], jx_upload_req** out);
+int32_t jx_upload_decode(jx_engine* e, const uint8_t* bodies, uint64_t len, uint64_t n, const uint64_t* body_offsets,
+                         const jx_upload_checks* checks, const uint8_t key_first[256], const uint8_t key_second[256],
+                         jx_upload_req** out);
+int32_t jx_upload_req_info(const jx_upload_req* r, jx_upload_req_info_t* out);
+int32_t jx_upload_req_arrays(const jx_upload_req* r, jx_upload_req_arrays_t* out);
+void jx_upload_req_release(jx_upload_req* r);
+
 /* Accumulate the output shares of the resident batch `batch_id` (helper, or leader after finish) into
  * the engine's running batch aggregations (the engine as one shard, §8e): report i is added iff
  * verdict == FINISHED and accept_mask[i] != 0 (accept_mask nullable = all), into aggregation
@@ -758,7 +856,9 @@ int32_t jx_engine_timing_read(jx_engine* e, float ms[4], uint64_t launches[4]);
  *   option 9: run the deferred accumulations now;
  *   option 10: reports per launch of jx_client_shard_batch / _device: 0 automatic (what 4 GiB of scratch hold, at
  *             least 64), else that many;
- *   option 11: reports per launch of jx_client_seal_batch / _device: 0 automatic (2^20), else that many. */
+ *   option 11: reports per launch of jx_client_seal_batch / _device: 0 automatic (2^20), else that many;
+ *   option 12: waves per report of the gather of jx_upload_decode* and the pack of jx_report_encode*: 0 automatic
+ *             (one, or more when few reports with long fields would leave the device idle), else 1..64. */
 int32_t jx_engine_debug(jx_engine* e, int32_t option, int64_t value);
 
 const char* jx_status_str(int32_t status);

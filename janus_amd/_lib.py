@@ -32,6 +32,8 @@ EXPORTED_SYMBOLS = (
     "jx_init_resp_encode_device", "jx_init_resp_encode", "jx_init_req_release",
     "jx_init_req_encode_bound", "jx_init_req_encode_device", "jx_init_req_encode", "jx_leader_req_info",
     "jx_leader_req_sent", "jx_init_resp_decode", "jx_leader_req_release",
+    "jx_report_encode_bound", "jx_report_encode_device", "jx_report_encode", "jx_upload_decode_device", "jx_upload_decode",
+    "jx_upload_req_info", "jx_upload_req_arrays", "jx_upload_req_release",
 )
 
 _lib = None
@@ -82,6 +84,27 @@ class JxLeaderReqInfo(ctypes.Structure):
 class JxInitRespInfo(ctypes.Structure):
     _fields_ = [("status", ctypes.c_uint32), ("pad_", ctypes.c_uint32)]
     _fields_ += [(name, ctypes.c_uint64) for name in ("error_offset", "mismatch_index", "n")]
+
+
+class JxUploadChecks(ctypes.Structure):
+    _fields_ = [("now", ctypes.c_uint64), ("tolerable_clock_skew", ctypes.c_uint64),
+                ("has_task_expiration", ctypes.c_uint32), ("task_expiration", ctypes.c_uint64),
+                ("has_report_expiry_age", ctypes.c_uint32), ("report_expiry_age", ctypes.c_uint64)]
+
+
+class JxUploadReqInfo(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_uint64) for name in (
+        "n", "m", "leader_enc_bytes", "leader_payload_bytes", "helper_enc_bytes", "helper_payload_bytes")]
+    _fields_ += [("status_count", ctypes.c_uint64 * 6)]
+
+
+class JxUploadReqArrays(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_void_p) for name in (
+        "d_index", "d_report_ids", "d_times", "d_public_shares", "d_key_index", "d_leader_encs", "d_leader_enc_offsets",
+        "d_leader_payloads", "d_leader_payload_offsets", "d_helper_config_ids", "d_helper_encs", "d_helper_enc_offsets",
+        "d_helper_payloads", "d_helper_payload_offsets", "d_all_report_ids", "d_all_times", "d_upload_status", "d_row_of",
+        "index", "times", "key_index", "leader_enc_offsets", "leader_payload_offsets", "helper_enc_offsets",
+        "helper_payload_offsets", "helper_config_ids", "all_report_ids", "all_times", "upload_status", "row_of")]
 
 
 class EngineError(RuntimeError):
@@ -175,6 +198,16 @@ def load():
         "jx_leader_req_sent": (i32, [vp, P(vp), P(vp)]),
         "jx_init_resp_decode": (i32, [vp, vp, u8p, u64, vp, u64, vp, u8p, u8p, P(JxInitRespInfo)]),
         "jx_leader_req_release": (None, [vp]),
+        "jx_report_encode_bound": (i32, [vp, u64, u32, u32, P(u64)]),
+        "jx_report_encode_device": (i32, [vp, u64, vp, P(u64), vp, vp, u32, vp, vp, u32, vp, ctypes.c_uint8, ctypes.c_uint8,
+                                          vp, vp, u64, vp, P(u64), P(u64)]),
+        "jx_report_encode": (i32, [vp, u64, u8p, P(u64), u8p, u8p, u32, u8p, u8p, u32, u8p, ctypes.c_uint8, ctypes.c_uint8,
+                                   u8p, u8p, u64, P(u64), P(u64)]),
+        "jx_upload_decode_device": (i32, [vp, vp, u64, u64, P(u64), P(JxUploadChecks), u8p, u8p, P(vp)]),
+        "jx_upload_decode": (i32, [vp, u8p, u64, u64, P(u64), P(JxUploadChecks), u8p, u8p, P(vp)]),
+        "jx_upload_req_info": (i32, [vp, P(JxUploadReqInfo)]),
+        "jx_upload_req_arrays": (i32, [vp, P(JxUploadReqArrays)]),
+        "jx_upload_req_release": (None, [vp]),
         "jx_engine_sync": (i32, [vp]),
         "jx_engine_stream": (i32, [vp, P(vp)]),
         "jx_engine_wait_stream": (i32, [vp, vp]),

@@ -942,3 +942,171 @@ def handle_upload(engine: HelperEngine, task: UploadTask, reports: list, now: in
             out.counters["upload_decode_failure"] += 1
             reject(i, ReportRejectionReason.DecodeFailure)
     return out
+
+
+@dataclass
+class UploadWireOutcome:
+    """handle_upload_wire's result, as arrays: nothing here is a Python object per report until results() is called.
+    status: uint8[n], engine.UPLOAD_* per upload; row_of: uint32[n], the upload's row of `rows` (UPLOAD_NO_ROW: none);
+    open_status: uint8[m], OPEN_OK or an OPEN_STATUS key per row; rows: torch uint8[m, lis_stride] on the device, the
+    leader input shares leader_init_device reads in place (zeros where the open failed; None when m is 0); counters as
+    UploadOutcome's; helper_shares: (config_ids uint8[m], d_encs, enc_offsets uint64[m + 1], d_payloads,
+    payload_offsets uint64[m + 1]), the helper's ciphertexts of the m rows with device pointers and host offsets, as
+    engine.encode_init_req takes them. `req` is the engine's UploadReq: it owns the device memory of helper_shares and
+    the ids, times and public shares of the rows (req.d, req.times), so release() (or the end of a `with`) comes after
+    their last use."""
+
+    task_id: bytes
+    req: object
+    status: np.ndarray
+    row_of: np.ndarray
+    open_status: np.ndarray
+    rows: object = None
+    lis_stride: int = 0
+    counters: Counter = field(default_factory=Counter)
+    helper_shares: tuple = ()
+    _ext: object = None      # torch uint8 on the device: row k's extension bytes at the leader payload's offset
+    _ext_len: object = None  # torch int32[m]
+    _unknown_config: dict = field(default_factory=dict)  # upload index -> leader config id, where no keypair has it
+
+    def results(self) -> list:
+        """The object path's list (UploadOutcome.results): per upload a StoredReport or a ReportRejection; None for an
+        upload that does not parse, which the reference answers with invalidMessage before any handler runs. Copies
+        the helper ciphertexts, public shares and extensions to the host."""
+        from .engine import (OPEN_OK, UPLOAD_EXPIRED, UPLOAD_MALFORMED, UPLOAD_ODD_PUBLIC_SHARE, UPLOAD_OK,
+                             UPLOAD_TASK_EXPIRED, UPLOAD_TOO_EARLY)
+        req = self.req
+        n, m = req.n, req.m
+        reason = {UPLOAD_TOO_EARLY: ReportRejectionReason.TooEarly, UPLOAD_TASK_EXPIRED: ReportRejectionReason.TaskExpired,
+                  UPLOAD_EXPIRED: ReportRejectionReason.Expired, UPLOAD_ODD_PUBLIC_SHARE: ReportRejectionReason.DecodeFailure}
+        host = lambda name: req.device_bytes(name).cpu().numpy().tobytes()  # noqa: E731
+        ps, encs, pays = host("public_shares"), host("helper_encs"), host("helper_payloads")
+        PS = len(ps) // m if m else 0
+        ext = self._ext.cpu().numpy() if m else None
+        ext_len = self._ext_len.cpu().numpy() if m else None
+        eo, po, lpo = req.helper_enc_offsets, req.helper_payload_offsets, req.leader_payload_offsets
+        out: list = [None] * n
+        for i in range(n):
+            st, rid, t = int(self.status[i]), req.report_ids[i].tobytes(), int(req.all_times[i])
+            if st == UPLOAD_MALFORMED:
+                continue
+            if st != UPLOAD_OK:
+                out[i] = ReportRejection(self.task_id, rid, t, reason[st])
+                continue
+            k = int(self.row_of[i])
+            op = int(self.open_status[k])
+            if op == OPEN_OK:
+                e = ext[int(lpo[k]):int(lpo[k]) + int(ext_len[k])].tobytes()
+                exts = PlaintextInputShare.decode(len(e).to_bytes(2, "big") + e + bytes(4)).extensions
+                ct = HpkeCiphertext(int(req.helper_config_ids[k]), encs[int(eo[k]):int(eo[k + 1])], pays[int(po[k]):int(po[k + 1])])
+                out[i] = StoredReport(self.task_id, ReportMetadata(rid, t), ps[PS * k:PS * k + PS], exts, k, ct)
+            elif op == 7:  # JX_OPEN_UNKNOWN_CONFIG
+                out[i] = ReportRejection(self.task_id, rid, t, ReportRejectionReason.OutdatedHpkeConfig, self._unknown_config.get(i))
+            elif op == 1:  # JX_OPEN_HPKE_DECRYPT_ERROR
+                out[i] = ReportRejection(self.task_id, rid, t, ReportRejectionReason.DecryptFailure)
+            else:
+                out[i] = ReportRejection(self.task_id, rid, t, ReportRejectionReason.DecodeFailure)
+        return out
+
+    def release(self):
+        self.rows = self._ext = self._ext_len = None
+        self.helper_shares = ()
+        self.req.release()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.release()
+
+
+def handle_upload_wire(engine: HelperEngine, task: UploadTask, bodies, body_offsets, now: int, global_keypairs=None,
+                       lis_stride: int = 0) -> UploadWireOutcome:
+    """handle_upload from the upload bodies as wire bytes: n encoded Reports back to back (`bodies`: bytes, or a torch
+    uint8 tensor on the engine's device, as client.prepare_report_bodies returns it) with body_offsets[n + 1]. One
+    engine.decode_uploads parses every body, makes the three time checks and the public-share check and lays the
+    accepted reports out on the device; one jx_leader_upload_open_device over the handle's arrays opens and validates
+    their leader shares. The key slots are handle_upload's: per config id the task's keypair first, then the global one
+    of the same id; the two tables cover every config id the task and the global keys hold, so more than
+    JX_ENC_MAX_KEYPAIRS distinct keypairs among them is a ValueError here, where handle_upload counts only those a batch
+    uses. Nothing per report runs in Python; UploadWireOutcome.results() gives the object path's list for callers that
+    want it. The helper's ciphertexts never leave the device: outcome.helper_shares feeds
+    engine.encode_init_req."""
+    import ctypes
+
+    import torch
+
+    from ._lib import check
+    from .engine import KEY_NONE, UPLOAD_ODD_PUBLIC_SHARE, _ptr
+
+    globals_ = dict(global_keypairs or {})
+    keypairs: list = []
+    slot: dict[int, int] = {}
+
+    def key_slot(k) -> int:
+        if id(k) not in slot:
+            slot[id(k)] = len(keypairs)
+            keypairs.append(k)
+        return slot[id(k)]
+
+    key_first, key_second = np.full(256, KEY_NONE, np.uint8), np.full(256, KEY_NONE, np.uint8)
+    for cfg in sorted(set(task.hpke_keys) | set(globals_)):
+        task_k, glob_k = task.hpke_keys.get(cfg), globals_.get(cfg)
+        first, second = (task_k, glob_k) if task_k is not None else (glob_k, None)
+        if first is not None:
+            key_first[cfg] = key_slot(first)
+            if second is not None:
+                key_second[cfg] = key_slot(second)
+    if len(keypairs) > 8:
+        raise ValueError("more than JX_ENC_MAX_KEYPAIRS distinct keypairs for one upload batch")
+    on_device = hasattr(bodies, "data_ptr")
+    req = engine.decode_uploads(bodies, body_offsets, now, key_first, key_second, task.tolerable_clock_skew,
+                                task.task_expiration, task.report_expiry_age, length=int(bodies.numel()) if on_device else None)
+    out = UploadWireOutcome(task.task_id, req, req.status, req.row_of, np.zeros(0, np.uint8))
+    out.counters["upload_decode_failure"] += req.status_count[UPLOAD_ODD_PUBLIC_SHARE]
+    if not out.counters["upload_decode_failure"]:
+        del out.counters["upload_decode_failure"]
+    m = req.m
+    if m == 0:
+        return out
+    v = engine.vdaf
+    stride = lis_stride or v.leader_input_share_len
+    dev = torch.device("cuda", engine.device)
+    task_b = np.frombuffer(task.task_id, np.uint8).copy()
+    hs = (ctypes.c_void_p * max(1, len(keypairs)))(*[k.handle for k in keypairs])
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    a = req.d
+    with torch.cuda.device(dev):
+        d_rows = torch.zeros(m * stride + 16, dtype=torch.uint8, device=dev)
+        skew = (-d_rows.data_ptr()) % 16
+        rows = d_rows[skew:skew + m * stride].view(m, stride)
+        d_ext = torch.zeros(max(req.leader_payload_bytes, 1), dtype=torch.uint8, device=dev)
+        d_len = torch.zeros(m, dtype=torch.int32, device=dev)
+        d_st = torch.zeros(m, dtype=torch.uint8, device=dev)
+        with engine._ordered(None):
+            st = engine._L.jx_leader_upload_open_device(
+                engine._h, m, a.d_report_ids, req.times.ctypes.data_as(u64p), a.d_public_shares, _ptr(task_b), hs,
+                len(keypairs), _ptr(np.ascontiguousarray(req.key_index)), a.d_leader_encs,
+                req.leader_enc_offsets.ctypes.data_as(u64p), a.d_leader_payloads,
+                req.leader_payload_offsets.ctypes.data_as(u64p), rows.data_ptr(), lis_stride, d_ext.data_ptr(),
+                d_len.data_ptr(), d_st.data_ptr())
+            check(st, engine._h, "jx_leader_upload_open_device")
+        out.open_status = d_st.cpu().numpy()
+    out.rows, out.lis_stride, out._ext, out._ext_len = rows, stride, d_ext, d_len
+    counts = np.bincount(out.open_status, minlength=8)
+    if counts[1]:
+        out.counters["upload_decrypt_failure"] += int(counts[1])
+    if counts[2] + counts[6]:
+        out.counters["upload_decode_failure"] += int(counts[2] + counts[6])
+    out.helper_shares = (req.helper_config_ids, a.d_helper_encs, req.helper_enc_offsets, a.d_helper_payloads,
+                         req.helper_payload_offsets)
+    if counts[7]:  # OutdatedHpkeConfig names the config id: one byte per such upload, right after its public share
+        k = np.nonzero(out.open_status == 7)[0]
+        i = req.index[k].astype(np.int64)
+        at = np.asarray(body_offsets, np.uint64)[i].astype(np.int64) + 28 + v.public_share_len
+        if on_device:
+            ids = bodies[torch.from_numpy(at).to(bodies.device)].cpu().numpy()
+        else:
+            ids = np.frombuffer(bytes(bodies), np.uint8)[at]
+        out._unknown_config = dict(zip(i.tolist(), ids.tolist()))
+    return out

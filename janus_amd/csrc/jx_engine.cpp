@@ -813,6 +813,11 @@ int32_t jx_engine_debug(jx_engine* e, int32_t option, int64_t value) {
     e->seal_chunk = (uint64_t)value;
     return JX_OK;
   }
+  if (option == 12) {  // waves per report of the upload gather and the report pack: 0 automatic, 1..64
+    if (value < 0 || value > 64) return JX_E_INVALID;
+    e->upload_parts = (uint32_t)value;
+    return JX_OK;
+  }
   if (option == 7) {  // tests: the device coalescer's gathers wait (up to their window) for this many jobs
     if (value < 0 || value > (int64_t)MAX_JOBS_PER_LAUNCH) return JX_E_INVALID;
     if (!e->coal) return fail(e, JX_E_STATE, "debug option 7: coalescing is off");

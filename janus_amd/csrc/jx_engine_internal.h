@@ -1,6 +1,6 @@
 // jx_engine_internal.h — engine internals shared by the engine's host sources: jx_engine.cpp (staging, resident
 // batches, the K1 -> K3 sequencing, the ABI's lifetime and plumbing calls), the call families jx_engine_cfg.cpp,
-// _prep.cpp, _acc.cpp, _fused.cpp, _upload.cpp, _shard.cpp, _seal.cpp and _wire.cpp, jx_arena.cpp (the per-device memory arena) and
+// _prep.cpp, _acc.cpp, _fused.cpp, _upload.cpp, _shard.cpp, _seal.cpp, _wire.cpp and _wire_upload.cpp, jx_arena.cpp (the per-device memory arena) and
 // jx_coalesce.cpp (the per-device job coalescer). Not part of the ABI: include/jx_prio3.h is.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -333,6 +333,7 @@ struct jx_engine {
   uint64_t wire_key[2] = {0, 0};
   bool wire_key_set = false;
   uint64_t shard_chunk = 0;      // reports per launch of jx_client_shard_* (debug option 10; 0: by the scratch budget)
+  uint32_t upload_parts = 0;     // waves per report of jx_upload_decode* / jx_report_encode* (debug option 12; 0: automatic)
   // timing
   bool timing = false;
   std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> pending;

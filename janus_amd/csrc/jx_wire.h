@@ -630,4 +630,198 @@ hipError_t launch_wire_encode_sizes(const WireEncodeArgs& a, hipStream_t s);
 hipError_t launch_wire_encode_pack(const WireEncodeArgs& a, hipStream_t s);
 #endif
 
+// ---- the upload: the Report a client sends the leader (messages/src/lib.rs:1353-1432) is id[16] || time u64 ||
+// u32 + public share || config id || u16 + encapsulated key || u32 + payload || config id || u16 + encapsulated key ||
+// u32 + payload (the leader's ciphertext, then the helper's): 42 fixed bytes around five fields. Every upload is an
+// HTTP body of its own, so where a Report starts and ends is known: there is no index to build.
+constexpr uint32_t WIRE_REPORT_FIXED = 42;
+// per-upload status (upload_status[n]), first failing check first
+enum : uint8_t {
+  UPLOAD_OK = 0, UPLOAD_MALFORMED = 1, UPLOAD_TOO_EARLY = 2, UPLOAD_TASK_EXPIRED = 3, UPLOAD_EXPIRED = 4,
+  UPLOAD_ODD_PUBLIC_SHARE = 5
+};
+constexpr uint32_t UPLOAD_NO_ROW = 0xFFFFFFFFu;  // row_of[i] of a report that is not accepted
+
+// One Report of the uploads: absolute byte offsets and lengths of its five fields. The report id is at off, the
+// time at off + 16. key0 / key1: the keypair slots of the leader ciphertext's config id (the decode fills them).
+struct WireReportRec {
+  uint64_t off, len;  // the whole Report
+  uint64_t ps_off, lenc_off, lpay_off, henc_off, hpay_off;
+  uint32_t ps_len, lenc_len, lpay_len, henc_len, hpay_len;
+  uint8_t leader_config_id, helper_config_id, key0, key1;
+};
+static_assert(sizeof(WireReportRec) == 80, "WireReportRec is plain bytes");
+
+// The Report in body[off, lim) (off <= lim): every field inside, nothing left over, as Report::get_decoded. False: it
+// does not parse, *err_off is the read that failed (bytes left over: the first of them).
+JX_HD bool wire_parse_report(const uint8_t* body, uint64_t lim, uint64_t off, WireReportRec& r, uint64_t* err_off) {
+  WireCur c{body, off, lim, true};
+  r = WireReportRec{};
+  r.off = off;
+  if (wire_need(c, 24)) c.pos += 24;  // report id, time
+  wire_opaque(c, 4, r.ps_off, r.ps_len);
+  r.leader_config_id = (uint8_t)wire_u8(c);
+  wire_opaque(c, 2, r.lenc_off, r.lenc_len);
+  wire_opaque(c, 4, r.lpay_off, r.lpay_len);
+  r.helper_config_id = (uint8_t)wire_u8(c);
+  wire_opaque(c, 2, r.henc_off, r.henc_len);
+  wire_opaque(c, 4, r.hpay_off, r.hpay_len);
+  if (!c.ok || c.pos != lim) {
+    *err_off = c.pos;
+    return false;
+  }
+  r.len = c.pos - off;
+  return true;
+}
+
+JX_HD uint64_t wire_report_len(uint64_t PS, uint64_t lenc_len, uint64_t lpay_len, uint64_t henc_len, uint64_t hpay_len) {
+  return WIRE_REPORT_FIXED + PS + lenc_len + lpay_len + henc_len + hpay_len;
+}
+// where the five fields of a Report start, from its first byte
+struct WireReportLayout {
+  uint64_t ps_off, lenc_off, lpay_off, henc_off, hpay_off, len;
+};
+JX_HD WireReportLayout wire_report_layout(uint64_t PS, uint64_t lenc_len, uint64_t lpay_len, uint64_t henc_len,
+                                          uint64_t hpay_len) {
+  WireReportLayout l;
+  l.ps_off = 28;
+  l.lenc_off = l.ps_off + PS + 3;
+  l.lpay_off = l.lenc_off + lenc_len + 4;
+  l.henc_off = l.lpay_off + lpay_len + 3;
+  l.hpay_off = l.henc_off + henc_len + 4;
+  l.len = l.hpay_off + hpay_len;
+  return l;
+}
+// Fixed byte k < 42 of a Report: its value, and in *at where it lies from the Report's first byte. The kernel gives
+// one k to a lane, a host writer loops over them.
+JX_HD uint8_t wire_report_fixed_byte(uint32_t k, const uint8_t* id, uint64_t time, uint32_t PS, uint8_t leader_config_id,
+                                     uint32_t lenc_len, uint32_t lpay_len, uint8_t helper_config_id, uint32_t henc_len,
+                                     uint32_t hpay_len, uint64_t* at) {
+  *at = (uint64_t)k + (k >= 28 ? PS : 0) + (k >= 31 ? lenc_len : 0) + (k >= 35 ? (uint64_t)lpay_len : 0) +
+        (k >= 38 ? henc_len : 0);
+  if (k < 16) return id[k];
+  if (k < 24) return (uint8_t)(time >> (8 * (23 - k)));
+  if (k < 28) return (uint8_t)(PS >> (8 * (27 - k)));
+  if (k == 28) return leader_config_id;
+  if (k < 31) return (uint8_t)(lenc_len >> (8 * (30 - k)));
+  if (k < 35) return (uint8_t)(lpay_len >> (8 * (34 - k)));
+  if (k == 35) return helper_config_id;
+  if (k < 38) return (uint8_t)(henc_len >> (8 * (37 - k)));
+  return (uint8_t)(hpay_len >> (8 * (41 - k)));
+}
+
+// The upload handler's three time checks in its order (aggregator/src/aggregator.rs:1544-1573): TooEarly, time >
+// now + skew; TaskExpired, time > *task_expiration; Expired, now > time + *report_expiry_age (either pointer null: the
+// task has no such limit). Both sums saturate at 2^64 - 1, which decides as the unbounded sum does: no u64 exceeds a
+// sum that overflowed.
+JX_HD uint64_t wire_sat_add(uint64_t a, uint64_t b) {
+  const uint64_t s = a + b;
+  return s < a ? ~0ull : s;
+}
+JX_HD uint8_t wire_upload_check_limits(uint64_t time, uint64_t now, uint64_t skew, bool has_task_expiration,
+                                       uint64_t task_expiration, bool has_report_expiry_age, uint64_t report_expiry_age) {
+  if (time > wire_sat_add(now, skew)) return UPLOAD_TOO_EARLY;
+  if (has_task_expiration && time > task_expiration) return UPLOAD_TASK_EXPIRED;
+  if (has_report_expiry_age && now > wire_sat_add(time, report_expiry_age)) return UPLOAD_EXPIRED;
+  return UPLOAD_OK;
+}
+JX_HD uint8_t wire_upload_check(uint64_t time, uint64_t now, uint64_t skew, const uint64_t* task_expiration,
+                                const uint64_t* report_expiry_age) {
+  return wire_upload_check_limits(time, now, skew, task_expiration != nullptr, task_expiration ? *task_expiration : 0,
+                                  report_expiry_age != nullptr, report_expiry_age ? *report_expiry_age : 0);
+}
+
+// What the parse kernel decides for upload i of body, which lies in [lo, hi): its record, id, time and status. A
+// report that is not accepted keeps zero lengths in its record, so the scans count nothing for it. An upload of fewer
+// than 24 bytes has a zero id and time. ps_bytes: the engine's public-share length; key_first / key_second: [256].
+struct WireUploadChecks {
+  uint64_t now, skew, task_expiration, report_expiry_age;
+  uint32_t has_task_expiration, has_report_expiry_age;
+};
+JX_HD uint8_t wire_upload_parse(const uint8_t* body, uint64_t lo, uint64_t hi, uint32_t ps_bytes,
+                                const WireUploadChecks& ck, const uint8_t* key_first, const uint8_t* key_second,
+                                WireReportRec& r, uint8_t id[16], uint64_t* time) {
+  uint64_t eo;
+  const bool parsed = wire_parse_report(body, hi, lo, r, &eo);
+  const bool head = hi - lo >= 24;
+  for (int k = 0; k < 16; k++) id[k] = head ? body[lo + k] : (uint8_t)0;
+  *time = head ? wire_be64(body + lo + 16) : 0;
+  uint8_t st = UPLOAD_MALFORMED;
+  if (parsed) {
+    st = wire_upload_check_limits(*time, ck.now, ck.skew, ck.has_task_expiration != 0, ck.task_expiration,
+                                  ck.has_report_expiry_age != 0, ck.report_expiry_age);
+    if (st == UPLOAD_OK && r.ps_len != ps_bytes) st = UPLOAD_ODD_PUBLIC_SHARE;
+  }
+  if (st != UPLOAD_OK) {
+    r.ps_len = r.lenc_len = r.lpay_len = r.henc_len = r.hpay_len = 0;
+    r.key0 = r.key1 = 0xFF;
+  } else {
+    r.key0 = key_first[r.leader_config_id];
+    r.key1 = key_second[r.leader_config_id];
+  }
+  return st;
+}
+
+// A long field copied by `parts` waves: wave `part` takes bytes [*lo, *lo + *cnt) of its len. The slices have one
+// length, a multiple of 16, so they neither overlap nor leave a gap (the last may be short or empty).
+JX_HD void wire_part_span(uint64_t len, uint32_t part, uint32_t parts, uint64_t* lo, uint64_t* cnt) {
+  const uint64_t chunk = ((len + parts - 1) / parts + 15) & ~15ull;
+  uint64_t at = (uint64_t)part * chunk;
+  if (at > len) at = len;
+  *lo = at;
+  *cnt = len - at < chunk ? len - at : chunk;
+}
+
+// ---- what the kernels of jx_wire_upload.hip and the engine (jx_engine_wire_upload.cpp) share
+struct WireUploadTotals {
+  uint64_t m;                                    // accepted reports
+  uint64_t lenc_bytes, lpay_bytes, henc_bytes, hpay_bytes;  // their four packed fields
+};
+struct WireUploadArgs {
+  uint64_t n;
+  const uint8_t* body;
+  const uint64_t* body_offsets;  // [n + 1], a device copy
+  uint32_t ps_bytes;
+  WireUploadChecks checks;
+  const uint8_t *key_first, *key_second;  // [256] each
+  // for all n
+  WireReportRec* recs;
+  uint8_t *ids_all, *status;
+  uint64_t* times_all;
+  uint32_t* row_of;
+  uint64_t *rank, *scan[4];  // [n + 1] each: exclusive scans of the accept flags and of the four lengths
+  WireUploadTotals* totals;
+  // for the m accepted, dense and in order
+  uint32_t* index;
+  uint8_t *ids, *ps, *key_index, *config_ids;
+  uint64_t* times;
+  uint64_t* offs[4];  // [m + 1] each: leader enc, leader payload, helper enc, helper payload
+  uint8_t* packed[4];
+};
+
+// The client's encode: the rows jx_client_seal_* wrote, every report of the same length.
+struct WireReportTotals {
+  uint64_t bytes, m;  // the bodies together; the reports that take room
+};
+struct WireReportArgs {
+  uint64_t n;
+  const uint8_t *ids, *ps, *lencs, *lcts, *hencs, *hcts;
+  const uint64_t* times;    // a device copy
+  const uint8_t* status;    // nullable: a non-zero entry takes no room
+  uint32_t ps_bytes, lenc_len, lct_len, henc_len, hct_len;
+  uint8_t leader_config_id, helper_config_id;
+  uint64_t *offsets, *rank;  // [n + 1]
+  uint32_t* index;           // [n]: index[rank[i]] = i for the reports that take room
+  WireReportTotals* totals;
+  uint8_t* out;
+};
+
+#if defined(__HIPCC__) || defined(__HIP__)
+// parse + the scans with the compaction; the host reads a.totals, then gathers m reports with `parts` waves each
+hipError_t launch_wire_upload_sizes(const WireUploadArgs& a, hipStream_t s);
+hipError_t launch_wire_upload_gather(const WireUploadArgs& a, uint64_t m, uint32_t parts, hipStream_t s);
+hipError_t launch_wire_report_sizes(const WireReportArgs& a, hipStream_t s);
+hipError_t launch_wire_report_pack(const WireReportArgs& a, uint64_t m, uint32_t parts, hipStream_t s);
+#endif
+
 }  // namespace jx

@@ -20,6 +20,7 @@
 
 #include "../../include/jx_prio3.h"
 #include "jx_wire.h"
+#include "jx_wire_dev.h"  // block_exclusive_scan, wave_copy
 
 namespace jx {
 namespace {
@@ -148,34 +149,6 @@ __global__ void wire_dup_read_kernel(const uint32_t* result, WireState* st) {
   st->dup = *result;
 }
 
-// ---- exclusive scan by one workgroup of 1024: out[i] = sum of load(j) for j < i, out[n] the total
-template <class F>
-__device__ void block_exclusive_scan(uint64_t n, F load, uint64_t* out) {
-  __shared__ uint64_t wsum[16];
-  const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-  uint64_t carry = 0;
-  for (uint64_t base = 0; base < n; base += 1024) {
-    const uint64_t i = base + t;
-    const uint64_t v = i < n ? load(i) : 0;
-    uint64_t x = v;
-    for (int d = 1; d < 64; d <<= 1) {
-      const uint64_t y = __shfl_up((unsigned long long)x, d);
-      if (lane >= (uint32_t)d) x += y;
-    }
-    if (lane == 63) wsum[w] = x;
-    __syncthreads();
-    uint64_t pre = 0, total = 0;
-    for (uint32_t k = 0; k < 16; k++) {
-      if (k < w) pre += wsum[k];
-      total += wsum[k];
-    }
-    if (i < n) out[i] = carry + pre + x - v;
-    carry += total;
-    __syncthreads();
-  }
-  if (t == 0) out[n] = carry;
-}
-
 __global__ __launch_bounds__(1024) void wire_scan_kernel(const WireRec* recs, uint64_t n, uint64_t* enc_offsets,
                                                          uint64_t* payload_offsets, WireState* st) {
   block_exclusive_scan(n, [&](uint64_t i) { return (uint64_t)recs[i].enc_len; }, enc_offsets);
@@ -184,24 +157,6 @@ __global__ __launch_bounds__(1024) void wire_scan_kernel(const WireRec* recs, ui
     st->enc_total = enc_offsets[n];
     st->pay_total = payload_offsets[n];
   }
-}
-
-// len bytes from src (any alignment) to dst by one wave: bytes up to dst's 16-byte boundary, 16 bytes per lane, the tail
-__device__ void wave_copy(uint8_t* dst, const uint8_t* src, uint64_t len, uint32_t lane) {
-  uint64_t head = (16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15;
-  if (head > len) head = len;
-  if (lane < head) dst[lane] = src[lane];
-  dst += head;
-  src += head;
-  len -= head;
-  const uint64_t nv = len / 16;
-  for (uint64_t v = lane; v < nv; v += 64) {
-    uint4 x;
-    __builtin_memcpy(&x, src + 16 * v, 16);
-    *reinterpret_cast<uint4*>(dst + 16 * v) = x;
-  }
-  const uint64_t t0 = nv * 16;
-  if (lane < len - t0) dst[t0 + lane] = src[t0 + lane];
 }
 
 __global__ __launch_bounds__(256) void wire_gather_kernel(WireDecodeArgs a) {

@@ -304,6 +304,94 @@ class InitRespDecode:
     n: int = 0                 # PrepareResps in the body
 
 
+# JX_UPLOAD_*: upload_status of jx_upload_decode
+UPLOAD_OK, UPLOAD_MALFORMED, UPLOAD_TOO_EARLY, UPLOAD_TASK_EXPIRED, UPLOAD_EXPIRED, UPLOAD_ODD_PUBLIC_SHARE = range(6)
+UPLOAD_NO_ROW = 0xFFFFFFFF     # row_of[i] of an upload that is not accepted
+
+
+class UploadReq:
+    """A batch of decoded upload bodies (jx_upload_req). For all n uploads, numpy views of the pinned host copy:
+    status (UPLOAD_*), row_of (UPLOAD_NO_ROW where not accepted), report_ids (n x 16) and all_times. For the m accepted
+    reports, dense and in order: index (accepted report k is upload index[k]), times, key_index (m x 2),
+    leader_enc_offsets / leader_payload_offsets / helper_enc_offsets / helper_payload_offsets (m + 1 each) and
+    helper_config_ids; `d` holds the device pointers (a _lib.JxUploadReqArrays), in the form leader_upload_open's device
+    call and encode_init_req take. Holds device memory until release() (or the end of a `with`), which must come before
+    the engine's close()."""
+
+    _VIEWS = ("status", "row_of", "report_ids", "all_times", "index", "times", "key_index", "leader_enc_offsets",
+              "leader_payload_offsets", "helper_enc_offsets", "helper_payload_offsets", "helper_config_ids")
+
+    def __init__(self, engine: "HelperEngine", handle):
+        self._engine, self._h = engine, handle
+        L = engine._L
+        info = _lib.JxUploadReqInfo()
+        check(L.jx_upload_req_info(handle, ctypes.byref(info)), engine._h, "jx_upload_req_info")
+        self.n, self.m = int(info.n), int(info.m)
+        self.leader_enc_bytes, self.leader_payload_bytes = int(info.leader_enc_bytes), int(info.leader_payload_bytes)
+        self.helper_enc_bytes, self.helper_payload_bytes = int(info.helper_enc_bytes), int(info.helper_payload_bytes)
+        self.status_count = [int(x) for x in info.status_count]
+        n, m = self.n, self.m
+        self.d = None
+        if n:
+            a = _lib.JxUploadReqArrays()
+            check(L.jx_upload_req_arrays(handle, ctypes.byref(a)), engine._h, "jx_upload_req_arrays")
+            self.d = a
+
+            def view(ptr, dtype, count):
+                if count == 0:
+                    return np.zeros(0, dtype)
+                buf = (ctypes.c_uint8 * (np.dtype(dtype).itemsize * count)).from_address(ptr)
+                return np.frombuffer(buf, dtype=dtype, count=count)
+
+            self.status = view(a.upload_status, np.uint8, n)
+            self.row_of = view(a.row_of, np.uint32, n)
+            self.report_ids = view(a.all_report_ids, np.uint8, 16 * n).reshape(n, 16)
+            self.all_times = view(a.all_times, np.uint64, n)
+            self.index = view(a.index, np.uint32, m)
+            self.times = view(a.times, np.uint64, m)
+            self.key_index = view(a.key_index, np.uint8, 2 * m).reshape(m, 2)
+            self.leader_enc_offsets = view(a.leader_enc_offsets, np.uint64, m + 1)
+            self.leader_payload_offsets = view(a.leader_payload_offsets, np.uint64, m + 1)
+            self.helper_enc_offsets = view(a.helper_enc_offsets, np.uint64, m + 1)
+            self.helper_payload_offsets = view(a.helper_payload_offsets, np.uint64, m + 1)
+            self.helper_config_ids = view(a.helper_config_ids, np.uint8, m)
+        else:
+            self.status, self.row_of = np.zeros(0, np.uint8), np.zeros(0, np.uint32)
+            self.report_ids, self.all_times = np.zeros((0, 16), np.uint8), np.zeros(0, np.uint64)
+            self.index, self.times, self.key_index = np.zeros(0, np.uint32), np.zeros(0, np.uint64), np.zeros((0, 2), np.uint8)
+            self.leader_enc_offsets = self.leader_payload_offsets = np.zeros(1, np.uint64)
+            self.helper_enc_offsets = self.helper_payload_offsets = np.zeros(1, np.uint64)
+            self.helper_config_ids = np.zeros(0, np.uint8)
+
+    def device_bytes(self, name: str):
+        """One of the device arrays of the accepted reports (report_ids, public_shares, leader_encs, leader_payloads,
+        helper_encs, helper_payloads) as a torch uint8 tensor over the handle's memory."""
+        import torch
+
+        e, m = self._engine, self.m
+        size = {"report_ids": 16 * m, "public_shares": m * e.public_share_len, "leader_encs": self.leader_enc_bytes,
+                "leader_payloads": self.leader_payload_bytes, "helper_encs": self.helper_enc_bytes,
+                "helper_payloads": self.helper_payload_bytes}[name]
+        ptr = getattr(self.d, "d_" + name) if self.d is not None else None
+        if not size or not ptr:
+            return torch.zeros(0, dtype=torch.uint8, device=torch.device("cuda", e.device))
+        return torch.as_tensor(_DeviceBytes(ptr, size), device=torch.device("cuda", e.device))
+
+    def release(self):
+        if self._h:
+            for name in self._VIEWS:  # the views' memory goes with the handle
+                setattr(self, name, None)
+            self.d = None
+            self._engine._L.jx_upload_req_release(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.release()
+
+
 class HelperEngine:
     """One engine per (Prio3 instance, verify key, GPU). Serves the helper role (the north-star
     path) and the leader role of the same ping-pong exchange."""
@@ -1100,6 +1188,111 @@ class HelperEngine:
             check(st, self._h, "jx_init_resp_decode")
         return InitRespDecode(int(info.status), res[:req.n_sent], err[:req.n_sent], int(info.error_offset),
                               int(info.mismatch_index), int(info.n))
+
+    # ------------------------------------------------------------------ the upload message
+    def report_bound(self, n: int, leader_enc_len: int = 32, helper_enc_len: int = 32) -> int:
+        """The length of n Report bodies if every report takes room (jx_report_encode_bound)."""
+        out = ctypes.c_uint64()
+        check(self._L.jx_report_encode_bound(self._h, n, leader_enc_len, helper_enc_len, ctypes.byref(out)), self._h,
+              "jx_report_encode_bound")
+        return out.value
+
+    def encode_reports(self, n: int, d_report_ids: int, times, d_public_shares: int | None, d_leader_encs: int,
+                       d_leader_cts: int, d_helper_encs: int, d_helper_cts: int, leader_config_id: int,
+                       helper_config_id: int, d_seal_status: int | None = None, leader_enc_len: int = 32,
+                       helper_enc_len: int = 32, d_out: int | None = None, capacity: int = 0, stream=None):
+        """The DAP Report bodies of n sealed reports, written back to back on the GPU (jx_report_encode_device) from
+        the arrays seal_reports_device wrote: device pointers for the report ids, public-share rows, encapsulated-key
+        rows (leader_enc_len / helper_enc_len bytes each) and ciphertext rows (client_seal_sizes() bytes each), `times`
+        a host array, one config id per recipient. A report whose d_seal_status entry is non-zero takes no room.
+        Returns (bodies, offsets): offsets is numpy uint64[n + 1], report i lies at bodies[offsets[i]:offsets[i + 1]];
+        bodies is a torch uint8 tensor on the device (the caller's d_out of `capacity` bytes when given, else a buffer
+        of report_bound). Ordered against `stream` like the other device-pointer methods; waits for its result."""
+        import torch
+
+        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
+        dev = torch.device("cuda", self.device)
+        keep = None
+        if d_out is None:
+            capacity = self.report_bound(n, leader_enc_len, helper_enc_len)
+            keep = torch.empty(max(capacity, 1), dtype=torch.uint8, device=dev)
+            d_out = keep.data_ptr()
+        offs = np.zeros(n + 1, np.uint64)
+        ln = ctypes.c_uint64()
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        with self._ordered(stream):
+            st = self._L.jx_report_encode_device(self._h, n, d_report_ids, tm.ctypes.data_as(u64p), d_public_shares,
+                                                 d_leader_encs, leader_enc_len, d_leader_cts, d_helper_encs, helper_enc_len,
+                                                 d_helper_cts, leader_config_id, helper_config_id, d_seal_status, d_out,
+                                                 capacity, None, offs.ctypes.data_as(u64p), ctypes.byref(ln))
+            check(st, self._h, "jx_report_encode_device")
+        if keep is not None:
+            bodies = keep[:ln.value]
+        elif ln.value:
+            bodies = torch.as_tensor(_DeviceBytes(d_out, ln.value), device=dev)
+        else:
+            bodies = torch.zeros(0, dtype=torch.uint8, device=dev)
+        return bodies, offs
+
+    def encode_reports_host(self, report_ids, times, public_shares, leader_encs, leader_cts, helper_encs, helper_cts,
+                            leader_config_id: int, helper_config_id: int, seal_status=None):
+        """The same from host arrays (jx_report_encode), as seal_reports returns them: rows of n, the encapsulated
+        keys' lengths taken from the rows. Returns (bodies bytes, offsets numpy uint64[n + 1])."""
+        ids = np.ascontiguousarray(np.asarray(report_ids, dtype=np.uint8)).reshape(-1, 16)
+        n = ids.shape[0]
+        rows = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.uint8)).reshape(max(n, 1), -1)  # noqa: E731
+        le, lc, he, hc = rows(leader_encs), rows(leader_cts), rows(helper_encs), rows(helper_cts)
+        if n and (lc.shape[1], hc.shape[1]) != self.client_seal_sizes():
+            raise ValueError("ciphertext rows of client_seal_sizes() bytes")
+        ps = _u8(public_shares, n, self.public_share_len, "public_shares")
+        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
+        ss = None if seal_status is None else _u8(seal_status, n, 1, "seal_status")
+        le_len, he_len = (le.shape[1], he.shape[1]) if n else (32, 32)
+        cap = self.report_bound(n, le_len, he_len)
+        out, offs, ln = np.zeros(max(cap, 1), np.uint8), np.zeros(n + 1, np.uint64), ctypes.c_uint64()
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        st = self._L.jx_report_encode(self._h, n, _ptr(ids), tm.ctypes.data_as(u64p), _ptr(ps) if self.public_share_len else None,
+                                      _ptr(le), le_len, _ptr(lc), _ptr(he), he_len, _ptr(hc), leader_config_id,
+                                      helper_config_id, _ptr(ss), _ptr(out), cap, offs.ctypes.data_as(u64p), ctypes.byref(ln))
+        check(st, self._h, "jx_report_encode")
+        return out[:ln.value].tobytes(), offs
+
+    def decode_uploads(self, bodies, body_offsets, now: int, key_first, key_second, tolerable_clock_skew: int = 0,
+                       task_expiration: int | None = None, report_expiry_age: int | None = None,
+                       length: int | None = None, stream=None) -> UploadReq:
+        """Decode n upload bodies lying back to back on the GPU (jx_upload_decode / _device). bodies: bytes (copied to
+        the device once) or, with `length`, a device pointer or torch tensor (ordered against `stream`). body_offsets:
+        n + 1, upload i is bodies[body_offsets[i]:body_offsets[i + 1]]. now, tolerable_clock_skew, task_expiration,
+        report_expiry_age: the upload handler's three time checks (None: the task has no such limit). key_first /
+        key_second: 256 keypair indices by the leader ciphertext's HPKE config id (KEY_NONE: none). Per upload the
+        UploadReq says whether it was accepted (status); the accepted reports' fields are its device arrays."""
+        off = np.ascontiguousarray(np.asarray(body_offsets, dtype=np.uint64).reshape(-1))
+        n = off.size - 1
+        if n < 0:
+            raise ValueError("body_offsets holds n + 1 offsets")
+        tab = lambda k: np.frombuffer(bytes(k), np.uint8) if isinstance(k, (bytes, bytearray)) else np.asarray(k, dtype=np.uint8)  # noqa: E731
+        kf, ks = (np.ascontiguousarray(tab(k).reshape(256)) for k in (key_first, key_second))
+        ck = _lib.JxUploadChecks(now, tolerable_clock_skew, task_expiration is not None, task_expiration or 0,
+                                 report_expiry_age is not None, report_expiry_age or 0)
+        h = ctypes.c_void_p()
+        u64p = ctypes.POINTER(ctypes.c_uint64)
+        if length is None:
+            b = np.frombuffer(bytes(bodies) or b"\0", np.uint8)
+            st = self._L.jx_upload_decode(self._h, _ptr(b), len(bodies), n, off.ctypes.data_as(u64p), ctypes.byref(ck),
+                                          _ptr(kf), _ptr(ks), ctypes.byref(h))
+            check(st, self._h, "jx_upload_decode")
+        else:
+            ptr = int(bodies.data_ptr()) if hasattr(bodies, "data_ptr") else int(bodies)
+            with self._ordered(stream):
+                st = self._L.jx_upload_decode_device(self._h, ptr, length, n, off.ctypes.data_as(u64p), ctypes.byref(ck),
+                                                     _ptr(kf), _ptr(ks), ctypes.byref(h))
+                check(st, self._h, "jx_upload_decode_device")
+        req = UploadReq(self, h)
+        with self._lock:
+            if not hasattr(self, "_init_reqs"):
+                self._init_reqs = weakref.WeakSet()
+            self._init_reqs.add(req)
+        return req
 
     # ------------------------------------------------------------------ aggregation state
     def aggregate_share(self, segment: int = 0) -> tuple[bytes, int, bytes]:
