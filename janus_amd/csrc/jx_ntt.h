@@ -23,6 +23,15 @@
 
 namespace jx {
 
+#if defined(__HIPCC__) || defined(__HIP__)
+// the device's sync(): what one lane of the wave wrote to LDS is visible to the others; no workgroup barrier
+__device__ __forceinline__ void wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+#endif
+
 // Table of one transform size P (f128 entries, Montgomery form):
 //   [0, P/2)    alpha^k                      forward twiddles
 //   [P/2, P)    alpha^-k                     inverse twiddles

@@ -2,8 +2,9 @@
 // jx_kernels.hip inline it: an encoding >= p is skipped and the stream moves on (VDAF-08 §6.2.1 next_vec).
 // A rejection is a 2^-32 event per Field64 element and a 2^-59 one per Field128 element, so this header also
 // builds for the host, where tests/csrc/hosttest.cpp runs it on hand-built Keccak states
-// (tests/test_device_math_host.py). The exact ">= p" predicates on f128 / word pairs, ge_p128 / ge_p64, are in
-// jx_field.h; the one on an explicit element as loaded (uint4), ge_exact, is here.
+// (tests/test_device_math_host.py). xof_stream128, at the end, is the sampler of Prio3.shard's streams
+// (jx_shard.hip). The exact ">= p" predicates on f128 / word pairs, ge_p128 / ge_p64, are in jx_field.h; the one
+// on an explicit element as loaded (uint4), ge_exact, is here.
 #pragma once
 #include <stdint.h>
 
@@ -113,6 +114,32 @@ JX_DEV f128 bx_sample128(ByteXof& x) {
   for (;;) {
     f128 v = bx_elem128(x);
     if (!ge_p128(v)) return v;
+  }
+}
+
+// XOF.next_vec for Field128: emit(k, v) for the first n accepted 16-byte chunks of the stream whose first block
+// is in S. 21 chunks span two blocks (the eleventh straddles them), so every state index is static.
+template <class Emit>
+JX_DEVI void xof_stream128(uint32_t* S, uint32_t n, Emit emit) {
+  uint32_t k = 0;
+  auto take = [&](uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) __attribute__((always_inline)) {
+    const f128 v = w4_to_f(w0, w1, w2, w3);
+    if (k < n && !ge_p128(v)) {
+      emit(k, v);
+      k++;
+    }
+  };
+#pragma unroll 1
+  while (k < n) {
+#pragma unroll
+    for (int ci = 0; ci < 10; ci++) take(S[4 * ci], S[4 * ci + 1], S[4 * ci + 2], S[4 * ci + 3]);
+    if (k >= n) break;
+    const uint32_t c0 = S[40], c1 = S[41];
+    keccak_p12(S);
+    take(c0, c1, S[0], S[1]);
+#pragma unroll
+    for (int ci = 0; ci < 10; ci++) take(S[2 + 4 * ci], S[3 + 4 * ci], S[4 + 4 * ci], S[5 + 4 * ci]);
+    if (k < n) keccak_p12(S);
   }
 }
 

@@ -39,12 +39,6 @@ __device__ __forceinline__ void st16(uint8_t* p, const uint32_t w[4], bool keep)
   for (int i = 0; i < 4; i++) q[i] = keep ? w[i] : 0u;
 }
 
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 // bit idx of the encoded measurement (flp_encode): Sum and SumVec entries little-endian, Histogram one-hot
 __device__ __forceinline__ uint32_t meas_bit(const ShardArgs& a, const uint64_t* m, uint64_t idx) {
   if (a.algo == ALGO_HISTOGRAM) return m[0] == idx;
@@ -64,32 +58,6 @@ __device__ __forceinline__ void xof_start(uint32_t* S, uint32_t dst_id, uint32_t
   if (NB > 1) blk_put_byte(m, pos + 1, b1);
   blk_pad(m, pos + NB);
   sponge_oneblock(S, m);
-}
-
-// XOF.next_vec for Field128: emit(k, v) for the first n accepted 16-byte chunks of the stream whose first block
-// is in S. 21 chunks span two blocks (the eleventh straddles them), so every state index is static.
-template <class Emit>
-__device__ __forceinline__ void xof_stream128(uint32_t* S, uint32_t n, Emit emit) {
-  uint32_t k = 0;
-  auto take = [&](uint32_t w0, uint32_t w1, uint32_t w2, uint32_t w3) __attribute__((always_inline)) {
-    const f128 v = w4_to_f(w0, w1, w2, w3);
-    if (k < n && !ge_p128(v)) {
-      emit(k, v);
-      k++;
-    }
-  };
-#pragma unroll 1
-  while (k < n) {
-#pragma unroll
-    for (int ci = 0; ci < 10; ci++) take(S[4 * ci], S[4 * ci + 1], S[4 * ci + 2], S[4 * ci + 3]);
-    if (k >= n) break;
-    const uint32_t c0 = S[40], c1 = S[41];
-    keccak_p12(S);
-    take(c0, c1, S[0], S[1]);
-#pragma unroll
-    for (int ci = 0; ci < 10; ci++) take(S[2 + 4 * ci], S[3 + 4 * ci], S[4 + 4 * ci], S[5 + 4 * ci]);
-    if (k < n) keccak_p12(S);
-  }
 }
 
 }  // namespace

@@ -8,6 +8,9 @@
 // an operation of variable length carries an offset and a length into one shared `aux` buffer and checks both
 // against its size. dt_run takes HOST pointers: it allocates exactly n records and the aux bytes, copies in,
 // launches whole waves with a guarded tail, synchronises, copies back, frees, and returns the HIP error code.
+//
+// A second launch shape, for the code that runs across a wave (jx_ntt.h with nl = 64): one wave per case over 64 KiB
+// of dynamic LDS, the exchanges behind the prove kernel's wave_sync (the DT_WOP operations).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
@@ -17,6 +20,7 @@
 #include "../../janus_amd/csrc/jx_sha256.h"
 #include "../../janus_amd/csrc/jx_sha512.h"
 #include "../../janus_amd/csrc/jx_sample.h"
+#include "../../janus_amd/csrc/jx_ntt.h"
 #include "../../janus_amd/csrc/jx_hpke.h"
 #include "../../janus_amd/csrc/jx_sha_aes.h"
 #include "../../janus_amd/csrc/jx_chapoly.h"
@@ -66,7 +70,7 @@ struct Ctx {
 #define DT_OP(name, in_bytes, out_bytes, needs_t0)                             \
   struct op_##name {                                                           \
     static constexpr uint32_t IN = in_bytes, OUT = out_bytes;                  \
-    static constexpr bool T0 = needs_t0;                                       \
+    static constexpr bool T0 = needs_t0, WAVE = false;                         \
     static __device__ void run(const uint8_t* in, uint8_t* out, const Ctx& c); \
   };                                                                           \
   __device__ void op_##name::run(const uint8_t* in, uint8_t* out, const Ctx& c)
@@ -215,6 +219,14 @@ DT_OP(bx_sample, 208, 400, false) {
   wr32(out + 200, end);
   wr32(out + 204, 0);
 }
+// u32 n (<= 48), pad, state[25] -> u32 emit calls (| 2^31: out of order), pad, 48 elements (0xA5 past n)
+DT_OP(xof_stream, 208, 776, false) {
+  uint64_t s[25];
+  for (int i = 0; i < 25; i++) s[i] = rd64(in + 8 + 8 * i);
+  const uint32_t n = rd32(in);
+  wr32(out, n <= 48 ? t_xof_stream128(s, n, out + 8) : 0xDEADu);
+  wr32(out + 4, 0);
+}
 // a, b, c, pad -> xor3, maj3
 DT_OP(bitop, 16, 8, false) {
   wr32(out, xor3(rd32(in), rd32(in + 4), rd32(in + 8)));
@@ -310,6 +322,84 @@ DT_OP(ghash, 40, 16, false) {
 // u32 otf, pad, key[16], block[16] -> AES-128 of the block by the T-table code, the table in LDS
 DT_OP(aes_t, 40, 16, true) { t_aes128_t((int)rd32(in), c.t0, in + 8, in + 24, out); }
 
+// ---- wave-per-case operations: a workgroup of one wave runs one case over DT_WAVE_LDS bytes of dynamic LDS, as a
+// wave of shard_prove_kernel runs jx_ntt.h: lane = threadIdx.x, nl = 64, sync = wave_sync. Every branch on the
+// record is uniform over the wave. A refused record leaves its output as the harness filled it.
+constexpr uint32_t DT_WAVE_LDS = 65536, DT_WAVE_ELEMS = DT_WAVE_LDS / 16;
+
+#define DT_WOP(name, in_bytes, out_bytes)                                                                 \
+  struct op_##name {                                                                                      \
+    static constexpr uint32_t IN = in_bytes, OUT = out_bytes;                                             \
+    static constexpr bool T0 = false, WAVE = true;                                                        \
+    static __device__ void run(const uint8_t* in, uint8_t* out, const Ctx& c, f128* lds, uint32_t lane);  \
+  };                                                                                                      \
+  __device__ void op_##name::run(const uint8_t* in, uint8_t* out, const Ctx& c, f128* lds, uint32_t lane)
+
+// logP (1..10), npairs, table offset, data offset (elements of aux): the table is ntt_build_table's (dt_ntt_table)
+struct NttCase {
+  uint32_t logP, npairs, P;
+  const f128* tab;
+  const uint8_t* data;
+  bool ok;
+};
+__device__ inline NttCase ntt_case(const uint8_t* in, const Ctx& c, uint32_t wires, uint32_t lds_per_P) {
+  NttCase n = {rd32(in), rd32(in + 4), 0, nullptr, nullptr, false};
+  const uint32_t tab_off = rd32(in + 8), data_off = rd32(in + 12);
+  if (n.logP < 1 || n.logP > 10 || n.npairs < 1 || n.npairs > 16) return n;
+  n.P = 1u << n.logP;
+  n.ok = lds_per_P * n.P <= DT_WAVE_ELEMS && in_aux(16ull * tab_off, 16ull * ntt_table_len(n.P), c.aux_len) &&
+         in_aux(16ull * data_off, 16ull * wires * n.npairs * n.P, c.aux_len);
+  n.tab = reinterpret_cast<const f128*>(c.aux + 16ull * tab_off);  // aux is 16-byte aligned
+  n.data = c.aux + 16ull * data_off;
+  return n;
+}
+// ntt_odd_points on one wire of P values -> its P odd-point values (npairs must be 1)
+DT_WOP(ntt_odd, 16, 16 * 1024) {
+  const NttCase n = ntt_case(in, c, 1, 1);
+  if (!n.ok || n.npairs != 1) return;
+  const auto sync = [] { wave_sync(); };
+  f128* const A = lds;
+  for (uint32_t k = lane; k < n.P; k += 64) A[k] = ld(n.data + 16ull * k);
+  sync();
+  ntt_odd_points(A, n.P, n.tab, lane, 64u, sync);
+  for (uint32_t k = lane; k < n.P; k += 64) st(out + 16ull * k, A[k]);
+}
+// The prove kernel's accumulation over npairs wire pairs (pair i: P values of wire 2i, then P of wire 2i + 1) and
+// ntt_gpoly_finish, the wave's LDS laid out A, B, E, O as there -> the 2P coefficients of the gadget polynomial
+DT_WOP(ntt_gpoly, 16, 16 * 2048) {
+  const NttCase n = ntt_case(in, c, 2, 4);
+  if (!n.ok) return;
+  const uint32_t P = n.P;
+  const auto sync = [] { wave_sync(); };
+  f128 *const A = lds, *const B = A + P, *const E = B + P, *const O = E + P;
+  for (uint32_t k = lane; k < P; k += 64) E[k] = O[k] = make128(0, 0);
+  for (uint32_t i = 0; i < n.npairs; i++) {
+    for (uint32_t k = lane; k < P; k += 64) {
+      const f128 va = ld(n.data + 16ull * (2ull * i * P + k)), vb = ld(n.data + 16ull * ((2ull * i + 1) * P + k));
+      A[k] = va;
+      B[k] = vb;
+      E[k] = add128(E[k], mont128(va, vb));
+    }
+    sync();
+    ntt_odd_points(A, P, n.tab, lane, 64u, sync);
+    ntt_odd_points(B, P, n.tab, lane, 64u, sync);
+    for (uint32_t k = lane; k < P; k += 64) O[k] = add128(O[k], mont128(A[k], B[k]));
+    sync();
+  }
+  ntt_gpoly_finish(E, O, P, n.logP, n.tab, lane, 64u, sync, [&](uint32_t j, f128 g) { st(out + 16ull * j, g); });
+}
+
+template <class Op>
+__global__ void __launch_bounds__(DT_BLOCK) dt_wave_kernel(uint32_t n, const uint8_t* in, uint8_t* out,
+                                                           const uint8_t* aux, uint32_t aux_len) {
+  extern __shared__ uint4 dt_lds[];
+  const uint32_t i = blockIdx.x;
+  if (i >= n) return;
+  const Ctx c = {aux, aux_len, nullptr};
+  if constexpr (Op::WAVE)
+    Op::run(in + (uint64_t)i * Op::IN, out + (uint64_t)i * Op::OUT, c, reinterpret_cast<f128*>(dt_lds), threadIdx.x);
+}
+
 template <class Op>
 __global__ void __launch_bounds__(DT_BLOCK) dt_kernel(uint32_t n, const uint8_t* in, uint8_t* out, const uint8_t* aux,
                                                       uint32_t aux_len) {
@@ -321,7 +411,7 @@ __global__ void __launch_bounds__(DT_BLOCK) dt_kernel(uint32_t n, const uint8_t*
   const uint32_t i = blockIdx.x * DT_BLOCK + threadIdx.x;
   if (i >= n) return;  // the last wave runs partly masked
   const Ctx c = {aux, aux_len, t0};
-  Op::run(in + (uint64_t)i * Op::IN, out + (uint64_t)i * Op::OUT, c);
+  if constexpr (!Op::WAVE) Op::run(in + (uint64_t)i * Op::IN, out + (uint64_t)i * Op::OUT, c);
 }
 
 template <class Op>
@@ -338,7 +428,10 @@ int dt_launch(uint32_t n, const void* in, uint32_t in_stride, void* out, uint32_
   if (e == hipSuccess) e = hipMemset(d_out, 0xA5, out_bytes);
   if (e == hipSuccess && aux_len) e = hipMemcpy(d_aux, aux, aux_len, hipMemcpyHostToDevice);
   if (e == hipSuccess) {
-    dt_kernel<Op><<<(n + DT_BLOCK - 1) / DT_BLOCK, DT_BLOCK>>>(n, d_in, d_out, d_aux, aux_len);
+    if constexpr (Op::WAVE)
+      dt_wave_kernel<Op><<<n, DT_BLOCK, DT_WAVE_LDS>>>(n, d_in, d_out, d_aux, aux_len);
+    else
+      dt_kernel<Op><<<(n + DT_BLOCK - 1) / DT_BLOCK, DT_BLOCK>>>(n, d_in, d_out, d_aux, aux_len);
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -353,8 +446,9 @@ int dt_launch(uint32_t n, const void* in, uint32_t in_stride, void* out, uint32_
 
 #define DT_OPS(X)                                                                                                    \
   X(f128) X(red192) X(mont_lazy) X(ge128) X(ge_screen) X(trunc) X(truncw) X(wacc_cols) X(wide_dot) X(cd26) X(cl_mac) X(f64)    \
-  X(wacc64_dot) X(red192_p64) X(ge64) X(sample64) X(sample2) X(bx_sample) X(bitop) X(keccak) X(hash) X(shift16)     \
-  X(fe) X(fe_limbs) X(x25519) X(p256_fe) X(p256_valid) X(p256_mul) X(pl_mul) X(poly1305) X(ghash) X(aes_t)
+  X(wacc64_dot) X(red192_p64) X(ge64) X(sample64) X(sample2) X(bx_sample) X(xof_stream) X(bitop) X(keccak) X(hash) X(shift16)     \
+  X(fe) X(fe_limbs) X(x25519) X(p256_fe) X(p256_valid) X(p256_mul) X(pl_mul) X(poly1305) X(ghash) X(aes_t)   \
+  X(ntt_odd) X(ntt_gpoly)
 
 extern "C" {
 // the hash of this file and every header it includes that the build passed in (tests recompute it: stale = rebuild)
@@ -370,6 +464,18 @@ int dt_run(const char* name, uint32_t n, const void* in, uint32_t in_stride, voi
   DT_OPS(DT_DISPATCH)
 #undef DT_DISPATCH
   return -1;
+}
+// ntt_build_table(logP), 1 <= logP <= 10, as the kernels read it (Montgomery form): out[16 (3 2^logP + 1)], host
+// code, no launch. The wave-per-case transforms take it through aux.
+int dt_ntt_table(uint32_t logP, uint8_t* out) {
+  if (logP < 1 || logP > 10) return -3;
+  f128 tab[3 * 1024 + 1];
+  ntt_build_table(logP, tab);
+  for (uint32_t i = 0; i < ntt_table_len(1u << logP); i++) {
+    memcpy(out + 16 * i, &tab[i].lo, 8);
+    memcpy(out + 16 * i + 8, &tab[i].hi, 8);
+  }
+  return 0;
 }
 // the record sizes of an operation; 0 for a known name
 int dt_sizes(const char* name, uint32_t* in_bytes, uint32_t* out_bytes) {

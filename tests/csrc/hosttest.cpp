@@ -113,4 +113,6 @@ void ht_sample64(int n, uint64_t st64[25], uint64_t* out) { t_sample64(n, st64, 
 void ht_sample2_f128(uint64_t st64[25], uint32_t cnt, int slow, uint8_t out[32], uint32_t* flags) { t_sample2_f128(st64, cnt, slow, out, flags); }
 // n elements from the byte stream that starts at byte `pos` of the block in st64; returns the final position
 uint32_t ht_bx_sample128(uint64_t st64[25], uint32_t pos, int n, uint8_t* out) { return t_bx_sample128(st64, pos, n, out); }
+// xof_stream128: n elements into out[16 n]; returns the number of emit calls, | 2^31 if their k was not 0, 1, 2, ...
+uint32_t ht_xof_stream128(const uint64_t st64[25], uint32_t n, uint8_t* out) { return t_xof_stream128(st64, n, out); }
 }

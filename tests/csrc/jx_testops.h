@@ -301,6 +301,18 @@ JXT uint32_t t_bx_sample128(uint64_t st64[25], uint32_t pos, int n, uint8_t* out
   st_from_words(x.s, st64);
   return x.pos;
 }
+// xof_stream128 for n elements on a Keccak state whose first block is ready: value k of emit(k, v) to out[16 k]
+// (k < n only). Returns the number of emit calls when call i came with k == i, else that number | 2^31.
+JXT uint32_t t_xof_stream128(const uint64_t st64[25], uint32_t n, uint8_t* out) {
+  uint32_t s[50], calls = 0, disorder = 0;
+  st_to_words(st64, s);
+  xof_stream128(s, n, [&](uint32_t k, f128 v) {
+    if (k != calls) disorder = 0x80000000u;
+    if (k < n) st(out + 16 * k, v);
+    calls++;
+  });
+  return calls | disorder;
+}
 #endif  // JX_TESTOPS_SAMPLE
 
 #ifdef JX_TESTOPS_P256

@@ -273,6 +273,252 @@ def bx_sample_cases():
     return out
 
 
+# ---------------------------------------------------------------------------- Keccak-p[1600] backwards
+def _keccak_round_constants():
+    out, r = [], 1
+    for _ in range(24):
+        rc = 0
+        for j in range(7):
+            r = ((r << 1) ^ ((r >> 7) * 0x71)) & 0xFF
+            if r & 2:
+                rc |= 1 << ((1 << j) - 1)
+        out.append(rc)
+    return out
+
+
+def _keccak_rho_offsets():
+    r, (x, y) = [0] * 25, (1, 0)
+    for t in range(24):
+        r[x + 5 * y] = ((t + 1) * (t + 2) // 2) % 64
+        x, y = y, (2 * x + 3 * y) % 5
+    return r
+
+
+_KRC, _KRHO = _keccak_round_constants(), _keccak_rho_offsets()
+
+
+def _theta_parity_map(c):
+    """theta on the column parities (320 bits, column x at bits 64 x ..): C'[x] = C[x] ^ C[x-1] ^ rotl(C[x+1], 1)."""
+    cs = [(c >> (64 * x)) & M64 for x in range(5)]
+    rot1 = lambda v: ((v << 1) | (v >> 63)) & M64  # noqa: E731
+    return sum((cs[x] ^ cs[(x - 1) % 5] ^ rot1(cs[(x + 1) % 5])) << (64 * x) for x in range(5))
+
+
+def _theta_parity_inverse():
+    """The inverse of _theta_parity_map as 320 columns (the image of every unit vector), by Gauss-Jordan over GF(2)."""
+    n = 320
+    cols = [_theta_parity_map(1 << j) for j in range(n)]
+    rows = [(1 << (n + i)) | sum(((cols[j] >> i) & 1) << j for j in range(n)) for i in range(n)]  # [M | I]
+    for j in range(n):
+        piv = next(i for i in range(j, n) if (rows[i] >> j) & 1)
+        rows[j], rows[piv] = rows[piv], rows[j]
+        for i in range(n):
+            if i != j and (rows[i] >> j) & 1:
+                rows[i] ^= rows[j]
+    inv_rows = [r >> n for r in rows]
+    return [sum(((inv_rows[i] >> j) & 1) << i for i in range(n)) for j in range(n)]
+
+
+_THETA_INV = []
+
+
+def keccak_p1600_inverse(state, rounds):
+    """The inverse of Keccak-p[1600, rounds] (the last `rounds` rounds of Keccak-f, FIPS 202 §3.3) on 25 lanes,
+    lane (x, y) at index x + 5 y: per round iota, chi, pi, rho and theta undone in that order."""
+    if not _THETA_INV:
+        _THETA_INV.extend(_theta_parity_inverse())
+    a = list(state)
+    for ir in reversed(range(24 - rounds, 24)):
+        a[0] ^= _KRC[ir]
+        b = list(a)
+        for y in range(5):  # chi^-1: a_x = b_x ^ ~b_(x+1) & (b_(x+2) ^ ~b_(x+3) & b_(x+4))
+            r = b[5 * y:5 * y + 5]
+            for x in range(5):
+                a[x + 5 * y] = r[x] ^ (~r[(x + 1) % 5] & M64 & (r[(x + 2) % 5] ^ (~r[(x + 3) % 5] & M64 & r[(x + 4) % 5])))
+        b = list(a)
+        for x in range(5):  # pi and rho: B[y, 2x + 3y] = rotl(A[x, y], rho[x, y])
+            for y in range(5):
+                v, s = b[y + 5 * ((2 * x + 3 * y) % 5)], _KRHO[x + 5 * y]
+                a[x + 5 * y] = ((v >> s) | (v << (64 - s))) & M64 if s else v
+        cp = 0
+        for x in range(5):
+            cp |= (a[x] ^ a[x + 5] ^ a[x + 10] ^ a[x + 15] ^ a[x + 20]) << (64 * x)
+        c, j = 0, 0
+        while cp:  # the parities before theta
+            if cp & 1:
+                c ^= _THETA_INV[j]
+            cp >>= 1
+            j += 1
+        cs = [(c >> (64 * x)) & M64 for x in range(5)]
+        for x in range(5):
+            v = cs[(x + 1) % 5]
+            d = cs[(x - 1) % 5] ^ (((v << 1) | (v >> 63)) & M64)
+            for y in range(5):
+                a[x + 5 * y] ^= d
+    return a
+
+
+# ---------------------------------------------------------------------------- xof_stream128
+def stream_chunks(st, count):
+    """The first `count` 16-byte chunks of the byte stream whose first block is in st (rejected ones included)."""
+    out, buf, st = [], b"", list(st)
+    while len(out) < count:
+        buf += b"".join(x.to_bytes(8, "little") for x in st[:21])
+        while len(buf) >= 16 and len(out) < count:
+            out.append(int.from_bytes(buf[:16], "little"))
+            buf = buf[16:]
+        st = O.keccak_p1600(st, 12)
+    return out
+
+
+def xof_stream_state(rnd, n, placed):
+    """A state from which xof_stream128 of n elements meets exactly the chunks of `placed` ({stream position: value}
+    with position 21 pair + c) as placed, every value >= p rejected, and no other rejection. The chunks of one
+    case lie in one block: c < 10 in block 2 pair, c > 10 in block 2 pair + 1 (with c = 10, the straddling chunk,
+    whose high half is that block's lane 0 and whose low half is whatever the block before holds, so its value
+    must be given as None and it is rejected). That block is filled in and the state permuted backwards to the
+    stream's first block; the blocks this leaves uncontrolled are checked to hold no encoding >= p."""
+    blocks = {2 * (q // 21) + (q % 21 >= 10) for q in placed} or {0}
+    assert len(blocks) == 1, "the placed chunks must lie in one block"
+    blk = blocks.pop()
+    st = [rnd.randrange(2**64) for _ in range(25)]
+    for i in range(21):
+        st[i] &= 2**63 - 1  # nothing >= p at either alignment
+    for q, v in placed.items():
+        c = q % 21
+        if c < 10:
+            st[2 * c], st[2 * c + 1] = v & M64, v >> 64
+        elif c == 10:
+            assert v is None
+            st[0] = M64
+        else:
+            st[2 * (c - 11) + 1], st[2 * (c - 11) + 2] = v & M64, v >> 64
+    for _ in range(blk):
+        st = keccak_p1600_inverse(st, 12)
+    rejected = sorted(q for q, v in placed.items() if v is None or v >= P128)
+    chunks = stream_chunks(st, n + len(rejected) + 1)
+    assert [q for q, v in enumerate(chunks[:n + len(rejected)]) if v >= P128] == rejected, (n, placed)
+    for q, v in placed.items():
+        assert q >= len(chunks) or (chunks[q] == v if v is not None else chunks[q] >> 64 == M64)
+    return st
+
+
+def xof_stream_cases():
+    """(label, n, state) per case for xof_stream128, n <= 48. The reference is _model_take(state, 16, n, P128)."""
+    rnd = random.Random(80)
+    g = lambda i: GE128[i % len(GE128)]  # noqa: E731
+    val = lambda q, i: None if q % 21 == 10 else g(i)  # noqa: E731
+    cases = [(f"no rejection, n={n}", n, {}) for n in (1, 9, 10, 11, 20, 21, 22, 31, 32, 42, 43)]
+    cases += [(f"rejection at {q}", 22, {q: val(q, q)}) for q in range(21)]       # every position of the first pair
+    cases += [(f"rejection at {q} in the second pair", 40, {q: val(q, q)}) for q in (21 + 3, 21 + 10, 21 + 13)]
+    # neighbours rejected together on either side of the first permutation. Position 9 lies in the block before
+    # the permutation and 10, 11 in the one after it: values >= p on both sides of one permutation would take a
+    # search of about 2^59 states, so 9 goes with 8 and 10 with 11.
+    cases += [("rejections at 8 and 9", 22, {8: g(1), 9: g(2)}), ("rejections at 10 and 11", 22, {10: None, 11: g(3)}),
+              ("rejections at 10, 11 and 12", 22, {10: None, 11: g(4), 12: g(0)}),
+              ("rejections at 19 and 20", 22, {19: g(1), 20: g(2)})]
+    # the last chunk needed is rejected, so that one more permutation is required
+    cases += [("rejection in the last chunk needed, n=10", 10, {9: g(0)}),
+              ("rejection in the last chunk needed, n=11", 11, {10: None}),
+              ("rejection in the last chunk needed, n=21", 21, {20: g(1)})]
+    for i in range(len(GE128)):  # every rejected encoding, before and after the permutation
+        cases += [(f"GE128[{i}] at 3", 12, {3: g(i)}), (f"GE128[{i}] at 14", 22, {14: g(i)})]
+    cases += [("p - 1 is taken at 0", 1, {0: P128 - 1}), ("p - 1 is taken at 9", 10, {9: P128 - 1}),
+              ("p - 1 is taken at 12 and 20", 21, {12: P128 - 1, 20: P128 - 1})]
+    return [(label, n, xof_stream_state(rnd, n, placed)) for label, n, placed in cases]
+
+
+# ---------------------------------------------------------------------------- the prover's transforms (jx_ntt.h)
+GEN128 = pow(7, (P128 - 1) >> 66, P128)  # order 2^66
+
+
+def root(log_order):
+    return pow(GEN128, 1 << (66 - log_order), P128)
+
+
+def rev(i, bits):
+    return int(format(i, f"0{bits}b")[::-1], 2) if bits else 0
+
+
+def dft(x, w):
+    n = len(x)
+    return [sum(x[j] * pow(w, j * m, P128) for j in range(n)) % P128 for m in range(n)]
+
+
+def horner(coef, x):
+    r = 0
+    for c in reversed(coef):
+        r = (r * x + c) % P128
+    return r
+
+
+def rand_vals(rng, n):
+    edge = [0, 1, P128 - 1]
+    return [rng.choice(edge) if rng.random() < 0.1 else rng.randrange(P128) for _ in range(n)]
+
+
+def interpolate(vals, log_p):
+    """Coefficients of the polynomial of degree < P with w(alpha^k) = vals[k], by the fast transform in Python."""
+    n = 1 << log_p
+    a = list(vals)
+    winv = pow(root(log_p), P128 - 2, P128) if log_p else 1
+    ln = n
+    while ln >= 2:
+        half, wl = ln // 2, pow(winv, n // ln, P128)
+        for s in range(0, n, ln):
+            ww = 1
+            for k in range(half):
+                u, v = a[s + k], a[s + k + half]
+                a[s + k] = (u + v) % P128
+                a[s + k + half] = (u - v) * ww % P128
+                ww = ww * wl % P128
+        ln //= 2
+    ninv = pow(n, P128 - 2, P128)
+    return [a[rev(j, log_p)] * ninv % P128 for j in range(n)]
+
+
+def evaluate(coef, log_n):
+    """The values at root(log_n)^m, m < 2^log_n, of the polynomial with the coefficients coef (at most 2^log_n):
+    the forward fast transform, by the even / odd split."""
+    def split(a, w):
+        if len(a) == 1:
+            return a
+        e, o = split(a[0::2], w * w % P128), split(a[1::2], w * w % P128)
+        half, out, t = len(a) // 2, [0] * len(a), 1
+        for k in range(half):
+            v = t * o[k] % P128
+            out[k], out[k + half] = (e[k] + v) % P128, (e[k] - v) % P128
+            t = t * w % P128
+        return out
+    n = 1 << log_n
+    return split(list(coef) + [0] * (n - len(coef)), root(log_n))
+
+
+def odd_point_values(vals, log_p):
+    """w(beta^(2k+1)), k < P, of the wire polynomial with w(alpha^k) = vals[k] (beta^2 = alpha): ntt_odd_points."""
+    return evaluate(interpolate(vals, log_p), log_p + 1)[1::2]
+
+
+def gadget_poly(wires, log_p):
+    """The 2P coefficients of sum_i wire_2i wire_2i+1 of the interpolated wires, through the size-2P transform."""
+    vals = [evaluate(interpolate(w, log_p), log_p + 1) for w in wires]
+    prod = [sum(vals[2 * i][m] * vals[2 * i + 1][m] for i in range(len(wires) // 2)) % P128 for m in range(2 << log_p)]
+    return interpolate(prod, log_p + 1)
+
+
+def ntt_wave_cases():
+    """(log_p, npairs, wires) for the 64-lane transforms: every size 2..1024 with one pair, and with three pairs
+    up to P = 256 (the prove kernel's four-wave size), the wire values random with 0, 1 and p - 1 mixed in."""
+    out = []
+    for log_p in range(1, 11):
+        for npairs in (1, 3):
+            if npairs == 3 and log_p > 8:
+                continue
+            rng = random.Random(900 + 10 * log_p + npairs)
+            out.append((log_p, npairs, [rand_vals(rng, 1 << log_p) for _ in range(2 * npairs)]))
+    return out
+
+
 # ---------------------------------------------------------------------------- 26-bit coefficient limbs
 def coef_limb_values():
     rnd = random.Random(26)

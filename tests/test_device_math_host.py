@@ -61,6 +61,8 @@ def ht():
     L.ht_sample2_f128.argtypes = [vp, ctypes.c_uint32, ctypes.c_int, vp, vp]
     L.ht_bx_sample128.argtypes = [vp, ctypes.c_uint32, ctypes.c_int, vp]
     L.ht_bx_sample128.restype = ctypes.c_uint32
+    L.ht_xof_stream128.argtypes = [vp, ctypes.c_uint32, vp]
+    L.ht_xof_stream128.restype = ctypes.c_uint32
     return L
 
 
@@ -399,3 +401,34 @@ def test_bx_sample128_rejection_before_a_block_boundary(ht):
     buf, out = _u64s(st), ctypes.create_string_buffer(16 * 12)
     assert ht.ht_bx_sample128(buf, 0, 12, out) == pos_after
     assert [int.from_bytes(out.raw[16 * i:16 * i + 16], "little") for i in range(12)] == want
+
+
+def test_keccak_p1600_inverse_round_trip():
+    """math_vectors.keccak_p1600_inverse, which builds the xof_stream128 states, against the oracle's permutation,
+    in both directions."""
+    rnd = random.Random(1600)
+    states = [[0] * 25, [M64] * 25] + [[rnd.getrandbits(64) for _ in range(25)] for _ in range(20)]
+    for st in states:
+        assert V.keccak_p1600_inverse(O.keccak_p1600(st, 12), 12) == st
+        assert O.keccak_p1600(V.keccak_p1600_inverse(st, 12), 12) == st
+    st = states[2]  # two blocks back, as the states of the second block pair are built; other round counts
+    back2 = V.keccak_p1600_inverse(V.keccak_p1600_inverse(st, 12), 12)
+    assert back2 != st and O.keccak_p1600(O.keccak_p1600(back2, 12), 12) == st
+    for rounds in (1, 2, 24):
+        assert V.keccak_p1600_inverse(O.keccak_p1600(st, rounds), rounds) == st
+
+
+def test_xof_stream128_rejects_at_every_position(ht):
+    """xof_stream128 (jx_sample.h), the sampler of Prio3.shard's Field128 streams, on states built backwards through
+    the permutation so that a rejected encoding sits at a chosen chunk of the first, second or third block:
+    emit is called for k = 0 .. n - 1 once each and in order, with the byte-stream model's values."""
+    cases = V.xof_stream_cases()
+    assert len(cases) == 55 and max(n for _, n, _ in cases) <= 48
+    for label, n, st in cases:
+        want, _, _ = _model_take(st, 16, n, P128)
+        buf, out = _u64s(st), ctypes.create_string_buffer(b"\xa5" * (16 * 49), 16 * 49)
+        calls = ht.ht_xof_stream128(buf, n, out)
+        assert calls == n, (label, hex(calls))
+        assert [int.from_bytes(out.raw[16 * i:16 * i + 16], "little") for i in range(n)] == want, label
+        assert out.raw[16 * n:] == b"\xa5" * (16 * (49 - n)), label
+        assert list(buf) == st  # the operation works on a copy

@@ -6,7 +6,9 @@ functions use other instructions (mac_c: a v_mad_u64_u32 whose carry-out is an S
 v_addc_co_u32; adc32 / sbb32: __builtin_addc / __builtin_subc; xor3 / maj3: v_bitop3; alignbit; wacc_mac's asm
 barrier), and the whole-kernel GPU tests feed them pseudo-random operands only. Here every launch shuffles edge and
 random cases together with a fixed seed, so that the lanes of one wave carry differently, and has a case count that
-is no multiple of 64, so that the last wave runs partly masked.
+is no multiple of 64, so that the last wave runs partly masked. The prover's transforms (jx_ntt.h) exchange data
+between the lanes of a wave through LDS, which no host build can show: they run in the harness's second launch
+shape, one wave per case, with every output element compared.
 
 The limit of this file: the harness kernels (tests/csrc/devtest.hip) are not the product kernels, so register
 allocation and instruction scheduling differ. What is identical is every __forceinline__ body of the headers and
@@ -49,6 +51,7 @@ class DevTest:
         lib.dt_run.argtypes = [ctypes.c_char_p, u32, vp, u32, vp, u32, vp, u32]
         lib.dt_sizes.argtypes = [ctypes.c_char_p, vp, vp]
         lib.dt_source_hash.restype = ctypes.c_char_p
+        lib.dt_ntt_table.argtypes = [u32, vp]
 
     def run(self, op: str, records, aux: bytes = b""):
         """records: one bytes object per case. Returns the output record of every case, in the order given. The
@@ -343,6 +346,69 @@ def test_samplers(dev):
     for (want, st_after, pos_after), g in zip(wants, got):
         assert words(g[:200], 8) == st_after and li(g[200:204]) == pos_after
         assert words(g[208:], 16)[:len(want)] == want
+
+
+def test_xof_stream128(dev):
+    """xof_stream128, the sampler of Prio3.shard's Field128 streams, on the host test's states (built backwards
+    through the permutation: a rejected encoding at every chunk of the first block pair, in the second pair, in the
+    last chunk needed): emit is called for k = 0 .. n - 1 once each, in order, with the byte-stream model's values."""
+    cases = V.xof_stream_cases()
+    got = dev.run("xof_stream", [u32s(n, 0) + u64s(*st) for _, n, st in cases])
+    for (label, n, st), g in zip(cases, got):
+        want, _, _ = V._model_take(st, 16, n, P128)
+        assert li(g[:4]) == n, (label, hex(li(g[:4])))
+        assert words(g[8:8 + 16 * n], 16) == want, label
+        assert g[8 + 16 * n:] == b"\xa5" * (16 * (48 - n)), label
+
+
+# ---------------------------------------------------------------------------- the prover's transforms, 64 lanes
+def _ntt_aux(dev, cases):
+    """aux for the wave-per-case transforms: the table of every size once, then every case's wires, pair by pair.
+    Returns (aux, {log_p: table offset}, [data offset per case]), offsets in elements."""
+    aux, tab_off, data_off = b"", {}, []
+    for log_p in sorted({c[0] for c in cases}):
+        buf = ctypes.create_string_buffer(16 * (3 * (1 << log_p) + 1))
+        assert dev.lib.dt_ntt_table(log_p, buf) == 0
+        tab_off[log_p] = len(aux) // 16
+        aux += buf.raw
+    for _, _, wires in cases:
+        data_off.append(len(aux) // 16)
+        aux += b"".join(le(v) for w in wires for v in w)
+    return aux, tab_off, data_off
+
+
+def test_ntt_odd_points_across_a_wave(dev):
+    """ntt_odd_points with nl = 64 and the prove kernel's wave_sync, one wave per case over LDS, P = 2 .. 1024:
+    EVERY odd-point value against the Python fast transform (test_ntt_host.py pins that against Horner's rule). A
+    misplaced sync() corrupts a few elements only, so nothing is sampled."""
+    cases = [(log_p, 1, wires[:1]) for log_p, npairs, wires in V.ntt_wave_cases() if npairs == 1]
+    assert [c[0] for c in cases] == list(range(1, 11))
+    aux, tab_off, data_off = _ntt_aux(dev, cases)
+    got = dev.run("ntt_odd", [u32s(log_p, 1, tab_off[log_p], off) for (log_p, _, _), off in zip(cases, data_off)], aux)
+    for (log_p, _, wires), g in zip(cases, got):
+        n = 1 << log_p
+        want = V.odd_point_values(wires[0], log_p)
+        bad = [k for k, (a, b) in enumerate(zip(words(g[:16 * n], 16), want)) if a != b]
+        assert not bad, (log_p, len(bad), bad[:8])
+        assert g[16 * n:] == b"\xa5" * (len(g) - 16 * n)
+
+
+def test_ntt_gadget_polynomial_across_a_wave(dev):
+    """The prove kernel's accumulation over 1 and 3 wire pairs (LDS laid out A, B, E, O) and ntt_gpoly_finish with
+    64 lanes, P = 2 .. 1024 (three pairs up to 256): ALL 2P coefficients against the product of the interpolated
+    wires through the Python transform of size 2P; the top coefficient is zero."""
+    cases = V.ntt_wave_cases()
+    assert {(c[0], c[1]) for c in cases} >= {(10, 1), (8, 3), (6, 1), (6, 3), (1, 1), (1, 3)}
+    aux, tab_off, data_off = _ntt_aux(dev, cases)
+    recs = [u32s(log_p, npairs, tab_off[log_p], off) for (log_p, npairs, _), off in zip(cases, data_off)]
+    got = dev.run("ntt_gpoly", recs, aux)
+    for (log_p, npairs, wires), g in zip(cases, got):
+        n = 1 << log_p
+        want = V.gadget_poly(wires, log_p)
+        assert want[2 * n - 1] == 0
+        bad = [j for j, (a, b) in enumerate(zip(words(g[:32 * n], 16), want)) if a != b]
+        assert not bad, (log_p, npairs, len(bad), bad[:8])
+        assert g[32 * n:] == b"\xa5" * (len(g) - 32 * n)
 
 
 # ---------------------------------------------------------------------------- bit operations and hashes

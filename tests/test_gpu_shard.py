@@ -10,6 +10,7 @@ import os
 import numpy as np
 import pytest
 
+import shard_shapes as SS
 from janus_amd._lib import EngineError
 from janus_amd.engine import SHARD_INVALID_MEASUREMENT, SHARD_MAX_P, HelperEngine
 from janus_amd.vdaf import Prio3
@@ -108,6 +109,51 @@ def test_histogram(shape):
     for i in range(65):  # every index of the small shapes; 0, 255 and a middle one of the large
         meas[i, 0] = (0, v.length - 1, v.length // 2)[i % 3] if v.length > 3 else i % v.length
     _check(v, meas, nonces, rands)
+
+
+def _matrix_inputs(v: Prio3, n):
+    """Report 0 all zeros, report 1 all max (Histogram: the first and the last index), the rest seeded random."""
+    meas, nonces, rands = _inputs(v, n, 7000 + 31 * v.meas_len + v.chunk_length)
+    meas[0] = 0
+    meas[1] = v.length - 1 if v.algo_id == O.HISTOGRAM else (1 << v.bits) - 1
+    return meas, nonces, rands
+
+
+@pytest.mark.parametrize("v", SS.INSTANCES, ids=SS.shape_id)
+def test_shape_matrix(v):
+    """The matrix of shard_shapes.py (its ledger: test_shard_shapes.py): every transform size of both wire paths,
+    every wave layout, every residue of the absorb kernel's tail and every exit of xof_stream128, a full wave and
+    one report more in one call."""
+    _check(v, *_matrix_inputs(v, 65), sizes=(65,))
+
+
+@pytest.mark.parametrize("v", [SS.W2_P512, SS.W4_P256], ids=SS.shape_id)
+def test_multi_wave_layouts_in_a_ragged_launch(v):
+    """The two layouts at the LDS limit (two waves at P = 512 with three slots; four waves at P = 256) through
+    shard_device with a padded row stride, the call cut into launches of 64, 64 and 2 reports."""
+    import torch
+
+    n = 130
+    meas, nonces, rands = _matrix_inputs(v, n)
+    dev = torch.device("cuda", 0)
+    lis_len = v.leader_input_share_len
+    stride = (lis_len + 127) // 128 * 128 + 128
+    d_m = torch.from_numpy(meas.view(np.int64)).to(dev)
+    d_n, d_r = torch.from_numpy(nonces).to(dev), torch.from_numpy(rands).to(dev)
+    u8 = lambda *shape: torch.full(shape, 0xA5, dtype=torch.uint8, device=dev)  # noqa: E731
+    d_ps, d_lis, d_his, d_st = u8(n, v.public_share_len), u8(n, stride), u8(n, v.helper_input_share_len), u8(n)
+    torch.cuda.synchronize()
+    with HelperEngine(v, VK) as eng:
+        eng.debug(10, 64)
+        eng.shard_device(n, d_m.data_ptr(), d_n.data_ptr(), d_r.data_ptr(), d_ps.data_ptr(), d_lis.data_ptr(),
+                         d_his.data_ptr(), d_st.data_ptr(), lis_stride=stride)
+        st, ps, lis, his = (t.cpu().numpy() for t in (d_st, d_ps, d_lis, d_his))
+    assert not st.any()
+    want_ps, want_lis, want_his = _expected(v, meas, nonces, rands)
+    np.testing.assert_array_equal(ps, want_ps)
+    np.testing.assert_array_equal(his, want_his)
+    np.testing.assert_array_equal(lis[:, :lis_len], want_lis)
+    assert not lis[:, lis_len:].any()  # the padding is zeroed
 
 
 def test_rejected_samples():

@@ -6,13 +6,10 @@ import subprocess
 
 import pytest
 
+import math_vectors as V
+from math_vectors import P128, dft, horner, interpolate, rand_vals, rev, root  # shared with the device test
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-P128 = 2**128 - 28 * 2**64 + 1
-GEN = pow(7, (P128 - 1) >> 66, P128)  # order 2^66
-
-
-def root(log_order):
-    return pow(GEN, 1 << (66 - log_order), P128)
 
 
 @pytest.fixture(scope="module")
@@ -38,47 +35,6 @@ def pack(vals):
 
 def unpack(buf, n):
     return [int.from_bytes(buf.raw[16 * i:16 * i + 16], "little") for i in range(n)]
-
-
-def rev(i, bits):
-    return int(format(i, f"0{bits}b")[::-1], 2) if bits else 0
-
-
-def dft(x, w):
-    n = len(x)
-    return [sum(x[j] * pow(w, j * m, P128) for j in range(n)) % P128 for m in range(n)]
-
-
-def horner(coef, x):
-    r = 0
-    for c in reversed(coef):
-        r = (r * x + c) % P128
-    return r
-
-
-def rand_vals(rng, n):
-    edge = [0, 1, P128 - 1]
-    return [rng.choice(edge) if rng.random() < 0.1 else rng.randrange(P128) for _ in range(n)]
-
-
-def interpolate(vals, log_p):
-    """Coefficients of the polynomial of degree < P with w(alpha^k) = vals[k], by the fast transform in Python."""
-    n = 1 << log_p
-    a = list(vals)
-    winv = pow(root(log_p), P128 - 2, P128) if log_p else 1
-    ln = n
-    while ln >= 2:
-        half, wl = ln // 2, pow(winv, n // ln, P128)
-        for s in range(0, n, ln):
-            ww = 1
-            for k in range(half):
-                u, v = a[s + k], a[s + k + half]
-                a[s + k] = (u + v) % P128
-                a[s + k + half] = (u - v) * ww % P128
-                ww = ww * wl % P128
-        ln //= 2
-    ninv = pow(n, P128 - 2, P128)
-    return [a[rev(j, log_p)] * ninv % P128 for j in range(n)]
 
 
 @pytest.mark.parametrize("log_p", range(1, 12))
@@ -160,3 +116,24 @@ def test_gadget_poly(nt, log_p, npairs):
     polys = [interpolate(w, log_p) for w in wires]
     want = sum(horner(polys[2 * i], z) * horner(polys[2 * i + 1], z) for i in range(npairs)) % P128
     assert horner(g, z) == want
+
+
+@pytest.mark.parametrize("log_p", [1, 2, 6, 8, 10])
+def test_python_transforms_against_horner(log_p):
+    """The Python fast transforms every element of the device test's outputs is compared with (math_vectors.py):
+    the forward transform, the odd-point values and the gadget polynomial, against Horner's rule at a few points."""
+    rng = random.Random(400 + log_p)
+    n = 1 << log_p
+    wires = [rand_vals(rng, n) for _ in range(4)]
+    coef = [interpolate(w, log_p) for w in wires]
+    alpha, beta = root(log_p), root(log_p + 1)
+    vals, odd = V.evaluate(coef[0], log_p), V.odd_point_values(wires[0], log_p)
+    assert vals == wires[0] and len(odd) == n
+    wide = V.evaluate(coef[0], log_p + 1)
+    for k in [0, n - 1] + rng.sample(range(n), min(n, 6)):
+        assert horner(coef[0], pow(alpha, k, P128)) == vals[k]
+        assert horner(coef[0], pow(beta, 2 * k + 1, P128)) == odd[k] == wide[2 * k + 1]
+    g = V.gadget_poly(wires, log_p)
+    assert len(g) == 2 * n and g[2 * n - 1] == 0
+    for z in [1, beta, P128 - 1] + [rng.randrange(P128) for _ in range(4)]:
+        assert horner(g, z) == sum(horner(coef[2 * i], z) * horner(coef[2 * i + 1], z) for i in range(2)) % P128
