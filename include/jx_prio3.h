@@ -803,6 +803,91 @@ int32_t jx_shard_record_bytes(const jx_engine* e, uint32_t* bytes);
 int32_t jx_shard_record_export_device(jx_engine* e, uint32_t segment, void* d_dst);
 int32_t jx_shard_record_combine_device(jx_engine* e, const void* d_records, uint32_t nrecords, void* d_out);
 
+/* ---- Collection, the protocol's last stage, at all three roles. Only NoDifferentialPrivacy is covered: no noise is
+ * added to a share.
+ *
+ * jx_collect_seal* is the helper's handle_aggregate_share_generic (aggregator/src/aggregator.rs:2766-2965) and the
+ * leader's collection step (collection_job_driver.rs) for njobs collection jobs in one call: per job, merge the shard
+ * records it names (compute_aggregate_share, aggregate_share.rs:55-110: mod-p sum of the shares, sum of the counts, XOR
+ * of the checksums), check the result, and seal the merged share to the collector (hpke::seal under
+ * HpkeApplicationInfo(AggregateShare, Helper or Leader, Collector), associated data the job's encoded
+ * AggregateShareAad). The records are the state of batch_aggregations rows as jx_shard_record_bytes /
+ * jx_shard_record_export_device define them; a row without a share (count 0) is passed as a zero share.
+ *   records          nrecords x jx_shard_record_bytes, back to back
+ *   record_offsets   [njobs + 1], record_index[]: job j's records are records[record_index[k]] for k in
+ *                    [record_offsets[j], record_offsets[j + 1]). Jobs may share records and name them in any order.
+ *   expect_counts    [njobs] and expect_checksums [njobs x 32]: the other aggregator's report count and checksum (the
+ *                    helper: from the AggregateShareReq); both NULL for the leader, which has nothing to compare against
+ *   min_batch_size, max_batch_size   the task's (max 0 = none): task.validate_batch_size (task.rs:365-377)
+ *   aads, aad_offsets [njobs + 1]    the encoded AggregateShareAad of each job, in the layout of jx_hpke_seal_*
+ *   ephemeral_sks    njobs x 32: one X25519 private key per seal, from the caller's CSPRNG (jx_hpke.h)
+ *   sender           a context of jx_hpke_create_sender holding the collector's public key
+ *   out_status [njobs], out_counts [njobs] (u64), out_checksums [njobs x 32], out_encs [njobs x 32],
+ *   out_cts [njobs x (OUT x FB + 16)], out_shares [njobs x OUT x FB] (nullable): the merged share unencrypted, which
+ *                    Janus keeps in its AggregateShareJob so that a repeated request is served without a merge
+ * out_status[j] is decided in Janus's order: JX_COLLECT_BAD_RECORD, an element of a record of the job is >= p (the
+ * datastore's decode fails); JX_COLLECT_INVALID_BATCH_SIZE, the job names no record or its count is below
+ * min_batch_size or above a non-zero max_batch_size; JX_COLLECT_BATCH_MISMATCH, expectations were given and the count or
+ * the checksum differs (aggregator.rs:2927-2939); JX_COLLECT_SEAL_FAILED, X25519(skE, pkR) was all zero (a low-order
+ * collector key); else JX_COLLECT_OK. The count and the checksum of every job are reported (BatchMismatch carries
+ * them); enc, ciphertext and share of a job whose status is not JX_COLLECT_OK are zeros.
+ * Refused before anything is queued, with nothing written: decreasing offsets, a record index >= nrecords, a record
+ * named twice by one job, a context that is no sender context or lives on another device (JX_E_INVALID); a context of
+ * the P-256 KEM (JX_E_UNSUPPORTED). njobs == 0 is JX_OK.
+ * The host form waits for its results. The device form takes the records, the ephemeral keys and every output as
+ * device pointers (8-byte aligned but for the status bytes) and the small arrays (offsets, indices, expectations, aads)
+ * from the host: they are consumed before the call returns, and the kernels stay queued on the engine stream (one merge
+ * launch for all jobs, one decision launch, the long seal's two, one that zeroes the refused jobs' outputs). */
+#define JX_COLLECT_OK 0
+#define JX_COLLECT_INVALID_BATCH_SIZE 1
+#define JX_COLLECT_BATCH_MISMATCH 2
+#define JX_COLLECT_BAD_RECORD 3
+#define JX_COLLECT_SEAL_FAILED 4
+int32_t jx_collect_seal(jx_engine* e, uint64_t njobs, const uint8_t* records, uint64_t nrecords,
+                        const uint64_t* record_offsets, const uint32_t* record_index, const uint64_t* expect_counts,
+                        const uint8_t* expect_checksums, uint64_t min_batch_size, uint64_t max_batch_size,
+                        const uint8_t* aads, const uint64_t* aad_offsets, const uint8_t* ephemeral_sks, jx_hpke* sender,
+                        uint8_t* out_status, uint64_t* out_counts, uint8_t* out_checksums, uint8_t* out_encs,
+                        uint8_t* out_cts, uint8_t* out_shares);
+int32_t jx_collect_seal_device(jx_engine* e, uint64_t njobs, const void* d_records, uint64_t nrecords,
+                               const uint64_t* record_offsets, const uint32_t* record_index,
+                               const uint64_t* expect_counts, const uint8_t* expect_checksums, uint64_t min_batch_size,
+                               uint64_t max_batch_size, const uint8_t* aads, const uint64_t* aad_offsets,
+                               const void* d_ephemeral_sks, jx_hpke* sender, void* d_out_status, void* d_out_counts,
+                               void* d_out_checksums, void* d_out_encs, void* d_out_cts, void* d_out_shares);
+/* jx_collect_open* is the collector (collector/src/lib.rs:573-629) for n collections: open the leader's and the
+ * helper's encrypted aggregate share of each, decode both and add them mod p (Prio3.unshard before the decode of the
+ * result).
+ *   leader_opener, helper_opener   recipient contexts holding the collector's keypair with the
+ *                    (AggregateShare, Leader -> Collector) and (AggregateShare, Helper -> Collector) application infos
+ *   leader_encs, helper_encs       n x jx_hpke_enc_len of the context
+ *   leader_cts / helper_cts with leader_ct_offsets / helper_ct_offsets [n + 1]   the ciphertexts, back to back
+ *   aads, aad_offsets [n + 1]      the encoded AggregateShareAad of each collection, the same for both shares
+ *   out_aggregates [n x OUT x FB]  the aggregate as canonical little-endian elements
+ *   out_status [n]   JX_COLLECT_OPEN_OK; _LEADER / _HELPER: that share did not open; JX_COLLECT_DECODE_LEADER /
+ *                    _HELPER: that share is not OUT x FB bytes, or holds an element >= p (Error::AggregateShareDecode)
+ * The lengths are read from the offsets on the host: a collection with a share of another length than OUT x FB + 16
+ * gets its status there (the leader's share first) and neither of its shares is opened. Of the others the leader's
+ * open failing comes first, then the helper's, then the leader's decode, then the helper's. The row of a collection
+ * whose status is not JX_COLLECT_OPEN_OK is zeros. A sender context, or a context on another device, is JX_E_INVALID
+ * before anything is queued; n == 0 is JX_OK. The device form takes the encapsulated keys, the ciphertexts and the two
+ * outputs as device pointers (out_aggregates 8-byte aligned) and the offsets and aads from the host; it stays queued
+ * on the engine stream (per share the long open's two launches, then the check-and-add and the status launch). */
+#define JX_COLLECT_OPEN_OK 0
+#define JX_COLLECT_OPEN_LEADER 1
+#define JX_COLLECT_OPEN_HELPER 2
+#define JX_COLLECT_DECODE_LEADER 3
+#define JX_COLLECT_DECODE_HELPER 4
+int32_t jx_collect_open(jx_engine* e, jx_hpke* leader_opener, jx_hpke* helper_opener, uint64_t n,
+                        const uint8_t* leader_encs, const uint8_t* leader_cts, const uint64_t* leader_ct_offsets,
+                        const uint8_t* helper_encs, const uint8_t* helper_cts, const uint64_t* helper_ct_offsets,
+                        const uint8_t* aads, const uint64_t* aad_offsets, uint8_t* out_aggregates, uint8_t* out_status);
+int32_t jx_collect_open_device(jx_engine* e, jx_hpke* leader_opener, jx_hpke* helper_opener, uint64_t n,
+                               const void* d_leader_encs, const void* d_leader_cts, const uint64_t* leader_ct_offsets,
+                               const void* d_helper_encs, const void* d_helper_cts, const uint64_t* helper_ct_offsets,
+                               const uint8_t* aads, const uint64_t* aad_offsets, void* d_out_aggregates,
+                               void* d_out_status);
+
 /* Wait for all work on the engine stream. Returns JX_E_INVALID if a combine since the last sync
  * met a non-canonical field element (>= p) in its inputs (the host merge rejects those too). */
 int32_t jx_engine_sync(jx_engine* e);

@@ -34,6 +34,7 @@ EXPORTED_SYMBOLS = (
     "jx_leader_req_sent", "jx_init_resp_decode", "jx_leader_req_release",
     "jx_report_encode_bound", "jx_report_encode_device", "jx_report_encode", "jx_upload_decode_device", "jx_upload_decode",
     "jx_upload_req_info", "jx_upload_req_arrays", "jx_upload_req_release",
+    "jx_collect_seal", "jx_collect_seal_device", "jx_collect_open", "jx_collect_open_device",
 )
 
 _lib = None
@@ -208,6 +209,12 @@ def load():
         "jx_upload_req_info": (i32, [vp, P(JxUploadReqInfo)]),
         "jx_upload_req_arrays": (i32, [vp, P(JxUploadReqArrays)]),
         "jx_upload_req_release": (None, [vp]),
+        "jx_collect_seal": (i32, [vp, u64, u8p, u64, P(u64), P(u32), P(u64), u8p, u64, u64, u8p, P(u64), u8p, vp,
+                                  u8p, P(u64), u8p, u8p, u8p, u8p]),
+        "jx_collect_seal_device": (i32, [vp, u64, vp, u64, P(u64), P(u32), P(u64), u8p, u64, u64, u8p, P(u64), vp, vp,
+                                         vp, vp, vp, vp, vp, vp]),
+        "jx_collect_open": (i32, [vp, vp, vp, u64, u8p, u8p, P(u64), u8p, u8p, P(u64), u8p, P(u64), u8p, u8p]),
+        "jx_collect_open_device": (i32, [vp, vp, vp, u64, vp, vp, P(u64), vp, vp, P(u64), u8p, P(u64), vp, vp]),
         "jx_engine_sync": (i32, [vp]),
         "jx_engine_stream": (i32, [vp, P(vp)]),
         "jx_engine_wait_stream": (i32, [vp, vp]),

@@ -25,10 +25,13 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from .engine import FINISHED, VERDICT_LABELS, HelperEngine
-from .messages import (EXTENSION_TASKPROV, CodecError, HpkeCiphertext, PingPongMessage,  # noqa: F401
-                       PlaintextInputShare, PrepareError, PrepareInit, PrepareResp, PrepareStepResult, ReportMetadata,
-                       ReportShare)
+from .batch_aggregation import AGGREGATING, SCRUBBED, AlreadyCollected, BatchAggregation, Interval, Scrubbed
+from .engine import (COLLECT_BATCH_MISMATCH, COLLECT_INVALID_BATCH_SIZE, COLLECT_OK, FINISHED, VERDICT_LABELS,
+                     HelperEngine)
+from .messages import (EXTENSION_TASKPROV, QUERY_TIME_INTERVAL, AggregateShare, AggregateShareAad,  # noqa: F401
+                       AggregateShareReq, BatchSelector, CodecError, Collection, HpkeCiphertext, PartialBatchSelector,
+                       PingPongMessage, PlaintextInputShare, PrepareError, PrepareInit, PrepareResp, PrepareStepResult,
+                       ReportMetadata, ReportShare)
 
 
 @dataclass
@@ -1110,3 +1113,209 @@ def handle_upload_wire(engine: HelperEngine, task: UploadTask, bodies, body_offs
             ids = np.frombuffer(bytes(bodies), np.uint8)[at]
         out._unknown_config = dict(zip(i.tolist(), ids.tolist()))
     return out
+
+
+# ----------------------------------------------------------------------------- collection (time-interval tasks)
+#
+# The helper's handle_aggregate_share_generic (aggregator/src/aggregator.rs:2766-2965) and the leader's collection step
+# (aggregator/src/aggregator/collection_job_driver.rs), with the merge, the checks and the seal of a collection in one
+# engine call (HelperEngine.collect_seal). Only NoDifferentialPrivacy is covered: no noise is added to a share. A
+# BatchAggregation row's integer batch identifier is its time bucket's number, bucket start // time_precision.
+
+
+class BatchInvalid(ValueError):
+    """The batch interval does not meet the task's time precision (Error::BatchInvalid)."""
+
+
+class AggregateShareRequestRejected(ValueError):
+    """The batch is past its report expiry: eligible for garbage collection (Error::AggregateShareRequestRejected)."""
+
+
+class InvalidBatchSize(ValueError):
+    """task.validate_batch_size refused the batch's report count (Error::InvalidBatchSize)."""
+
+    def __init__(self, task_id: bytes, report_count: int):
+        super().__init__(f"invalid batch size: {report_count} reports")
+        self.task_id, self.report_count = task_id, report_count
+
+
+class BatchMismatch(ValueError):
+    """The two aggregators' report counts or checksums differ (Error::BatchMismatch, aggregator.rs:2927-2939)."""
+
+    def __init__(self, task_id: bytes, own_report_count: int, own_checksum: bytes, peer_report_count: int,
+                 peer_checksum: bytes):
+        super().__init__(f"batch mismatch: own {own_report_count} reports / {own_checksum.hex()}, peer "
+                         f"{peer_report_count} / {peer_checksum.hex()}")
+        self.task_id = task_id
+        self.own_report_count, self.own_checksum = own_report_count, own_checksum
+        self.peer_report_count, self.peer_checksum = peer_report_count, peer_checksum
+
+
+class CollectionFailed(RuntimeError):
+    """A batch-aggregation row that does not decode (an element >= p), or a seal that did not come about."""
+
+
+@dataclass(frozen=True)
+class CollectTask:
+    """What collection reads of an AggregatorTask (aggregator_core/src/task.rs): max_batch_size 0 = none."""
+
+    task_id: bytes
+    time_precision: int
+    min_batch_size: int
+    max_batch_size: int = 0
+    report_expiry_age: int | None = None
+    collector_config_id: int = 0
+
+    def validate_batch_interval(self, iv) -> bool:
+        """TimeInterval::validate_collection_identifier (aggregator_core/src/query_type.rs:270-282)."""
+        p = self.time_precision
+        return iv.duration >= p and iv.start % p == 0 and iv.duration % p == 0
+
+    def batch_identifiers(self, iv) -> list[int]:
+        """batch_identifiers_for_collection_identifier: the interval's time buckets, by number."""
+        return [iv.start // self.time_precision + k for k in range(iv.duration // self.time_precision)]
+
+
+@dataclass(frozen=True)
+class AggregateShareJob:
+    """models.rs AggregateShareJob: the UNENCRYPTED share, so that a repeated request is sealed to the collector key
+    valid then (aggregator.rs:2941-2944)."""
+
+    aggregate_share: bytes
+    report_count: int
+    checksum: bytes
+
+
+def _collection_rows(tx, task: CollectTask, writer, iv):
+    """The rows of every batch identifier of the interval over every shard ord, and the (identifier, ord) pairs that
+    have none (empty_batch_aggregations, aggregator.rs:2968-3008)."""
+    rows, missing = [], []
+    for s in task.batch_identifiers(iv):
+        for ord_ in range(writer.shard_count):
+            row = tx.get((s, ord_))
+            if row is None:
+                missing.append((s, ord_))
+            elif row.state == SCRUBBED:
+                raise Scrubbed("batch aggregation was scrubbed")  # compute_aggregate_share, aggregate_share.rs:69-71
+            else:
+                rows.append(row)
+    return rows, missing
+
+
+def _row_records(engine: HelperEngine, rows) -> bytes:
+    """The rows as shard records (share || count u64 LE || checksum); a row without a share is a zero share."""
+    pt = engine.output_len * engine.field_bytes
+    return b"".join((r.aggregate_share if r.aggregate_share is not None else bytes(pt)) +
+                    r.report_count.to_bytes(8, "little") + r.checksum for r in rows)
+
+
+def _raise_collect_status(task: CollectTask, status: int, count: int, checksum: bytes, peer=None):
+    if status == COLLECT_OK:
+        return
+    if status == COLLECT_INVALID_BATCH_SIZE:
+        raise InvalidBatchSize(task.task_id, count)
+    if status == COLLECT_BATCH_MISMATCH:
+        raise BatchMismatch(task.task_id, count, checksum, peer[0], peer[1])
+    raise CollectionFailed(f"collection failed with status {status}")
+
+
+def _aligned(iv, precision: int):
+    """Interval::align_to_time_precision (core/src/time.rs:319-335): the start down, the duration up, and one more
+    step when the start's move left the end outside."""
+    start = iv.start - iv.start % precision
+    duration = -(-iv.duration // precision) * precision
+    if iv.end > start + duration:
+        duration += precision
+    return Interval(start, duration)
+
+
+def handle_aggregate_share(engine: HelperEngine, writer, task: CollectTask, req_body: bytes, collector_sender,
+                           ephemeral_sk: bytes, now: int, cache: dict, inject_tx_failures: int = 0) -> bytes:
+    """The helper's aggregate-share handler for a time-interval task. collector_sender: an HpkeSealer holding the
+    collector's public key with the (AggregateShare, Helper -> Collector) application info; ephemeral_sk: 32 bytes of
+    the caller's CSPRNG; cache: the AggregateShareJobs served so far, by (batch interval, aggregation parameter).
+    Returns the AggregateShare body."""
+    req = AggregateShareReq.decode(req_body, QUERY_TIME_INTERVAL)
+    iv = req.batch_selector.batch_interval
+    if not task.validate_batch_interval(iv):
+        raise BatchInvalid(f"batch interval {iv} does not fit time precision {task.time_precision}")
+    if task.report_expiry_age is not None and now > iv.end + task.report_expiry_age:
+        raise AggregateShareRequestRejected("aggregate share request too late")
+    aad = AggregateShareAad(task.task_id, req.aggregation_parameter, req.batch_selector).encode()
+    key = ((iv.start, iv.duration), req.aggregation_parameter)
+    peer = (req.report_count, req.checksum)
+    job = cache.get(key)
+    if job is not None:
+        # served before: the stored share is sealed afresh; the comparison runs against this request
+        rec = job.aggregate_share + job.report_count.to_bytes(8, "little") + job.checksum
+        out = engine.collect_seal(rec, [[0]], [aad], ephemeral_sk, collector_sender, 0, 0, expect=[peer])
+        _raise_collect_status(task, int(out.status[0]), job.report_count, job.checksum, peer)
+    else:
+        def closure(tx):
+            rows, missing = _collection_rows(tx, task, writer, iv)
+            out = engine.collect_seal(_row_records(engine, rows), [list(range(len(rows)))], [aad], ephemeral_sk,
+                                      collector_sender, task.min_batch_size, task.max_batch_size, expect=[peer],
+                                      want_shares=True)
+            count, checksum = int(out.counts[0]), out.checksums[0].tobytes()
+            _raise_collect_status(task, int(out.status[0]), count, checksum, peer)
+            for r in rows:
+                tx[(r.batch_identifier, r.ord)] = r.scrubbed()
+            for s, ord_ in missing:
+                tx[(s, ord_)] = BatchAggregation(s, ord_, field_bytes=writer.field_bytes).scrubbed()
+            return out, AggregateShareJob(out.shares[0].tobytes(), count, checksum)
+
+        out, job = writer.datastore.run_tx(closure, inject_tx_failures)
+        cache[key] = job
+    ct = HpkeCiphertext(task.collector_config_id, out.encs[0].tobytes(), out.cts[0].tobytes())
+    return AggregateShare(ct).encode()
+
+
+@dataclass
+class LeaderCollection:
+    """The leader's half of a collection: what goes to the helper, and what waits for its answer."""
+
+    request_body: bytes            # the AggregateShareReq
+    leader_share: HpkeCiphertext   # sealed under (AggregateShare, Leader -> Collector)
+    report_count: int
+    checksum: bytes
+    interval: Interval             # the merged client-timestamp interval, aligned outward to the time precision
+    aggregate_share: bytes         # unencrypted (the leader's AggregateShareJob counterpart)
+
+
+def leader_collect(engine: HelperEngine, writer, task: CollectTask, batch_interval, agg_param: bytes, collector_sender,
+                   ephemeral_sk: bytes, inject_tx_failures: int = 0) -> LeaderCollection:
+    """The leader's collection step, first half: merge its rows of the batch interval (the same engine call, with
+    nothing to compare against), mark them collected, seal its share under the (AggregateShare, Leader -> Collector)
+    info of collector_sender, and write the AggregateShareReq for the helper."""
+    if not task.validate_batch_interval(batch_interval):
+        raise BatchInvalid(f"batch interval {batch_interval} does not fit time precision {task.time_precision}")
+    sel = BatchSelector.time_interval(batch_interval)
+    aad = AggregateShareAad(task.task_id, agg_param, sel).encode()
+
+    def closure(tx):
+        rows, missing = _collection_rows(tx, task, writer, batch_interval)
+        if any(r.state != AGGREGATING for r in rows):
+            raise AlreadyCollected("batch aggregation was already collected")
+        out = engine.collect_seal(_row_records(engine, rows), [list(range(len(rows)))], [aad], ephemeral_sk,
+                                  collector_sender, task.min_batch_size, task.max_batch_size, want_shares=True)
+        count, checksum = int(out.counts[0]), out.checksums[0].tobytes()
+        _raise_collect_status(task, int(out.status[0]), count, checksum)
+        span = Interval.EMPTY
+        for r in rows:
+            span = span.merge(r.client_timestamp_interval)
+            tx[(r.batch_identifier, r.ord)] = r.collected()
+        for s, ord_ in missing:
+            tx[(s, ord_)] = BatchAggregation(s, ord_, field_bytes=writer.field_bytes).collected()
+        return out, count, checksum, _aligned(span, task.time_precision)
+
+    out, count, checksum, span = writer.datastore.run_tx(closure, inject_tx_failures)
+    body = AggregateShareReq(sel, agg_param, count, checksum).encode()
+    ct = HpkeCiphertext(task.collector_config_id, out.encs[0].tobytes(), out.cts[0].tobytes())
+    return LeaderCollection(body, ct, count, checksum, span, out.shares[0].tobytes())
+
+
+def leader_finish_collection(step: LeaderCollection, helper_body: bytes) -> bytes:
+    """Second half: the helper's AggregateShare body in, the Collection body for the collector out."""
+    helper = AggregateShare.decode(helper_body).encrypted_aggregate_share
+    return Collection(PartialBatchSelector.time_interval(), step.report_count, step.interval, step.leader_share,
+                      helper).encode()

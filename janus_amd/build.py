@@ -15,9 +15,9 @@ from concurrent.futures import ThreadPoolExecutor
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = [os.path.join(_HERE, "csrc", f) for f in ("jx_hpke_p256.hip", "jx_hpke_long.hip", "jx_kernels.hip", "jx_hpke_suite.hip", "jx_hpke_seal.hip",
                                                   "jx_hpke_default.hip", "jx_flp.hip", "jx_accumulate.hip",
-                                                  "jx_mp64.hip", "jx_shard.hip", "jx_engine.cpp", "jx_engine_cfg.cpp", "jx_engine_prep.cpp",
+                                                  "jx_mp64.hip", "jx_shard.hip", "jx_collect.hip", "jx_engine.cpp", "jx_engine_cfg.cpp", "jx_engine_prep.cpp",
                                                   "jx_engine_acc.cpp", "jx_engine_fused.cpp", "jx_engine_upload.cpp",
-                                                  "jx_engine_shard.cpp", "jx_engine_seal.cpp", "jx_engine_wire.cpp", "jx_wire.hip",
+                                                  "jx_engine_shard.cpp", "jx_engine_seal.cpp", "jx_engine_collect.cpp", "jx_engine_wire.cpp", "jx_wire.hip",
                                                   "jx_engine_wire_upload.cpp", "jx_wire_upload.hip", "jx_coalesce.cpp",
                                                   "jx_arena.cpp",
                                                   "jx_hpke.hip")]  # the slowest to compile first
@@ -27,7 +27,7 @@ HEADERS = [os.path.join(_HERE, "csrc", f) for f in ("jx_field.h", "jx_keccak.h",
                                                   "jx_hpke_open.h", "jx_k1_plan.h", "jx_fused_plan.h", "jx_ghash_lanes.h",
                                                   "jx_hpke_long.h", "jx_upload.h", "jx_chapoly_lanes.h", "jx_enc_rows.h",
                                                   "jx_ntt.h", "jx_shard.h", "jx_sample.h", "jx_carve.h", "jx_hpke_seal.h",
-                                                  "jx_wire.h", "jx_wire_dev.h")]
+                                                  "jx_wire.h", "jx_wire_dev.h", "jx_collect.h")]
 OUT = os.path.join(_HERE, "lib", "libjanus_prio3.so")
 # jx_mp64.hip: keep the LDS for the AES table (the AMDGPU backend would otherwise move a small private
 # array of the out-of-line helpers into LDS, +16 KiB per workgroup, one workgroup less per CU)

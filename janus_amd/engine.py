@@ -154,6 +154,28 @@ class SealResult:
     status: np.ndarray        # uint8[n]: SEAL_OK, SEAL_SKIPPED or SEAL_ZERO_DH
 
 
+# jx_collect_seal*: JX_COLLECT_* (include/jx_prio3.h), in the order they are decided but for the numbering
+COLLECT_OK, COLLECT_INVALID_BATCH_SIZE, COLLECT_BATCH_MISMATCH, COLLECT_BAD_RECORD, COLLECT_SEAL_FAILED = 0, 1, 2, 3, 4
+# jx_collect_open*: JX_COLLECT_OPEN_* / JX_COLLECT_DECODE_*
+COLLECT_OPEN_OK, COLLECT_OPEN_LEADER, COLLECT_OPEN_HELPER, COLLECT_DECODE_LEADER, COLLECT_DECODE_HELPER = 0, 1, 2, 3, 4
+
+
+@dataclass
+class CollectSeal:
+    status: np.ndarray        # uint8[njobs]: COLLECT_*
+    counts: np.ndarray        # uint64[njobs]: the merged report counts
+    checksums: np.ndarray     # uint8[njobs, 32]: the merged checksums
+    encs: np.ndarray          # uint8[njobs, 32]
+    cts: np.ndarray           # uint8[njobs, OUT * FB + 16]
+    shares: np.ndarray | None  # uint8[njobs, OUT * FB]: the merged shares, unencrypted (want_shares)
+
+
+@dataclass
+class CollectOpen:
+    aggregates: np.ndarray    # uint8[n, OUT * FB]: canonical little-endian elements, zeros where status != 0
+    status: np.ndarray        # uint8[n]: COLLECT_OPEN_* / COLLECT_DECODE_*
+
+
 WIRE_OK, WIRE_MALFORMED, WIRE_WRONG_QUERY_TYPE, WIRE_DUPLICATE_ID = 0, 1, 2, 3  # JX_WIRE_* (request status)
 WIRE_REPORT_ODD_PUBLIC_SHARE, WIRE_REPORT_NOT_INITIALIZE, WIRE_REPORT_ODD_PREP_SHARE = 1, 2, 3  # wire_status
 WIRE_NO_ERROR = 0xFF           # JX_WIRE_NO_ERROR: no host-resolved error for the report
@@ -1333,6 +1355,142 @@ class HelperEngine:
         with self._ordered(stream):
             check(self._L.jx_shard_record_combine_device(self._h, d_records, nrecords, d_out), self._h,
                   "jx_shard_record_combine_device")
+
+    # ------------------------------------------------------------------ collection
+    def _collect_jobs(self, jobs, nrecords: int, expect, aads, njobs_keys: int):
+        """The host arrays jx_collect_seal* takes: the jobs' record lists as a CSR, the expectations, the aads."""
+        njobs = len(jobs)
+        if not (len(aads) == njobs and njobs_keys == njobs) or (expect is not None and len(expect) != njobs):
+            raise ValueError("one aad, one 32-byte ephemeral key and (when given) one expectation per job")
+        off = np.zeros(njobs + 1, np.uint64)
+        off[1:] = np.cumsum([len(j) for j in jobs], dtype=np.uint64)
+        idx = np.ascontiguousarray(np.asarray([r for j in jobs for r in j] or [0], dtype=np.int64))
+        if idx.min() < 0 or idx.max() >= 2**32:
+            raise ValueError("record indices are u32")
+        idx = idx.astype(np.uint32)
+        ao = np.zeros(njobs + 1, np.uint64)
+        ao[1:] = np.cumsum([len(a) for a in aads], dtype=np.uint64)
+        aad = np.frombuffer(b"".join(aads) or b"\0", np.uint8).copy()
+        ec = ecs = None
+        if expect is not None:
+            ec = np.ascontiguousarray(np.asarray([c for c, _ in expect] or [0], dtype=np.uint64))
+            if any(len(cs) != 32 for _, cs in expect):
+                raise ValueError("a checksum is 32 bytes")
+            ecs = np.frombuffer(b"".join(cs for _, cs in expect) or bytes(32), np.uint8).copy()
+        return off, idx, ec, ecs, aad, ao
+
+    def collect_seal(self, records, jobs, aads, ephemeral_sks, sender, min_batch_size: int, max_batch_size: int = 0,
+                     expect=None, want_shares: bool = False) -> CollectSeal:
+        """Merge, check and seal many collection jobs in one call (jx_collect_seal): the helper's
+        handle_aggregate_share_generic and the leader's collection step. records: nrecords x record_bytes() shard records
+        (bytes or array; the state of batch_aggregations rows); jobs[j]: the indices of job j's records; aads[j]: its
+        encoded AggregateShareAad; ephemeral_sks: njobs x 32 bytes from the caller's CSPRNG; sender: an HpkeSealer with
+        the collector's public key and the (AggregateShare, this role -> Collector) info; expect: per job (report count,
+        checksum) of the other aggregator, None for the leader. A job whose status is not COLLECT_OK has zeros for
+        enc, ciphertext and share; its count and checksum are reported all the same."""
+        rb, njobs = self.record_bytes(), len(jobs)
+        rec = np.ascontiguousarray(np.frombuffer(records, np.uint8) if isinstance(records, (bytes, bytearray))
+                                   else np.asarray(records, dtype=np.uint8)).reshape(-1)
+        if rec.size % rb:
+            raise ValueError(f"records: a multiple of {rb} bytes")
+        nrecords = rec.size // rb
+        sks = _u8(ephemeral_sks, njobs, 32, "ephemeral_sks")
+        off, idx, ec, ecs, aad, ao = self._collect_jobs(jobs, nrecords, expect, aads, njobs)
+        pt = self.output_len * self.field_bytes
+        out = CollectSeal(np.zeros(njobs, np.uint8), np.zeros(njobs, np.uint64), np.zeros((njobs, 32), np.uint8),
+                          np.zeros((njobs, 32), np.uint8), np.zeros((njobs, pt + 16), np.uint8),
+                          np.zeros((njobs, pt), np.uint8) if want_shares else None)
+        P64 = ctypes.POINTER(ctypes.c_uint64)
+        check(self._L.jx_collect_seal(self._h, njobs, _ptr(rec) if nrecords else None, nrecords, off.ctypes.data_as(P64),
+                                      idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                      None if ec is None else ec.ctypes.data_as(P64), _ptr(ecs), min_batch_size,
+                                      max_batch_size, _ptr(aad), ao.ctypes.data_as(P64), _ptr(sks), sender.handle,
+                                      _ptr(out.status), out.counts.ctypes.data_as(P64), _ptr(out.checksums),
+                                      _ptr(out.encs), _ptr(out.cts), _ptr(out.shares)),
+              self._h, "jx_collect_seal")
+        return out
+
+    def collect_seal_device(self, d_records: int, nrecords: int, jobs, aads, d_ephemeral_sks: int, sender,
+                            min_batch_size: int, max_batch_size: int, d_out_status: int, d_out_counts: int,
+                            d_out_checksums: int, d_out_encs: int, d_out_cts: int, d_out_shares: int | None = None,
+                            expect=None, stream=None):
+        """collect_seal with the records, the ephemeral keys and every output in HBM (jx_collect_seal_device; 8-byte
+        aligned pointers); the jobs' record lists, the aads and the expectations stay host arrays. Asynchronous, ordered
+        against `stream` (module docstring)."""
+        njobs = len(jobs)
+        off, idx, ec, ecs, aad, ao = self._collect_jobs(jobs, nrecords, expect, aads, njobs)
+        P64 = ctypes.POINTER(ctypes.c_uint64)
+        with self._ordered(stream):
+            check(self._L.jx_collect_seal_device(self._h, njobs, d_records, nrecords, off.ctypes.data_as(P64),
+                                                 idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                                 None if ec is None else ec.ctypes.data_as(P64), _ptr(ecs),
+                                                 min_batch_size, max_batch_size, _ptr(aad), ao.ctypes.data_as(P64),
+                                                 d_ephemeral_sks, sender.handle, d_out_status, d_out_counts,
+                                                 d_out_checksums, d_out_encs, d_out_cts, d_out_shares),
+                  self._h, "jx_collect_seal_device")
+
+    @staticmethod
+    def _offsets(items) -> np.ndarray:
+        off = np.zeros(len(items) + 1, np.uint64)
+        off[1:] = np.cumsum([len(x) for x in items], dtype=np.uint64)
+        return off
+
+    def collect_open(self, leader_opener, helper_opener, leader_shares, helper_shares, aads) -> CollectOpen:
+        """The collector for n collections (jx_collect_open): open both encrypted aggregate shares of each and add them
+        mod p. leader_opener / helper_opener: HpkeOpener contexts holding the collector's keypair with the
+        (AggregateShare, Leader / Helper -> Collector) infos; leader_shares / helper_shares: per collection (enc,
+        ciphertext); aads: per collection the encoded AggregateShareAad. An encapsulated key of another length than the
+        KEM's never reaches the GPU: that share did not open."""
+        n = len(aads)
+        if not len(leader_shares) == len(helper_shares) == n:
+            raise ValueError("one leader share, one helper share and one aad per collection")
+        pt = self.output_len * self.field_bytes
+        out = CollectOpen(np.zeros((n, pt), np.uint8), np.zeros(n, np.uint8))
+        pre = {i: code for i in range(n) for code, op, sh in ((COLLECT_OPEN_HELPER, helper_opener, helper_shares),
+                                                               (COLLECT_OPEN_LEADER, leader_opener, leader_shares))
+               if len(sh[i][0]) != op.enc_len}
+        keep = [i for i in range(n) if i not in pre]
+        for i, code in pre.items():
+            out.status[i] = code
+        if not keep:
+            return out
+        m = len(keep)
+        P64 = ctypes.POINTER(ctypes.c_uint64)
+        arrs = []
+        for sh in (leader_shares, helper_shares):
+            encs = np.frombuffer(b"".join(sh[i][0] for i in keep), np.uint8).copy()
+            cts = np.frombuffer(b"".join(sh[i][1] for i in keep) or b"\0", np.uint8).copy()
+            arrs += [encs, cts, self._offsets([sh[i][1] for i in keep])]
+        aad = np.frombuffer(b"".join(aads[i] for i in keep) or b"\0", np.uint8).copy()
+        ao = self._offsets([aads[i] for i in keep])
+        agg, st = np.zeros((m, pt), np.uint8), np.zeros(m, np.uint8)
+        check(self._L.jx_collect_open(self._h, leader_opener.handle, helper_opener.handle, m, _ptr(arrs[0]), _ptr(arrs[1]),
+                                      arrs[2].ctypes.data_as(P64), _ptr(arrs[3]), _ptr(arrs[4]),
+                                      arrs[5].ctypes.data_as(P64), _ptr(aad), ao.ctypes.data_as(P64), _ptr(agg), _ptr(st)),
+              self._h, "jx_collect_open")
+        out.aggregates[keep] = agg
+        out.status[keep] = st
+        return out
+
+    def collect_open_device(self, leader_opener, helper_opener, n: int, d_leader_encs: int, d_leader_cts: int,
+                            leader_ct_offsets, d_helper_encs: int, d_helper_cts: int, helper_ct_offsets, aads,
+                            d_out_aggregates: int, d_out_status: int, stream=None):
+        """collect_open with the encapsulated keys (n x enc_len rows), the ciphertexts and both outputs in HBM
+        (jx_collect_open_device); the ciphertext offsets [n + 1] and the aads stay on the host. Asynchronous, ordered
+        against `stream` (module docstring)."""
+        P64 = ctypes.POINTER(ctypes.c_uint64)
+        lo = np.ascontiguousarray(np.asarray(leader_ct_offsets, dtype=np.uint64).reshape(n + 1))
+        ho = np.ascontiguousarray(np.asarray(helper_ct_offsets, dtype=np.uint64).reshape(n + 1))
+        if len(aads) != n:
+            raise ValueError("one aad per collection")
+        aad = np.frombuffer(b"".join(aads) or b"\0", np.uint8).copy()
+        ao = self._offsets(aads)
+        with self._ordered(stream):
+            check(self._L.jx_collect_open_device(self._h, leader_opener.handle, helper_opener.handle, n, d_leader_encs,
+                                                 d_leader_cts, lo.ctypes.data_as(P64), d_helper_encs, d_helper_cts,
+                                                 ho.ctypes.data_as(P64), _ptr(aad), ao.ctypes.data_as(P64),
+                                                 d_out_aggregates, d_out_status),
+                  self._h, "jx_collect_open_device")
 
     def set_capacity(self, reports: int):
         check(self._L.jx_engine_set_capacity(self._h, reports), self._h, "jx_engine_set_capacity")

@@ -399,3 +399,257 @@ class AggregationJobResp:
         while ir.i < len(ir.b):
             resps.append(_prepare_resp_from(ir))
         return cls(tuple(resps))
+
+
+# ----------------------------------------------------------------------------- collection
+
+from .batch_aggregation import Interval  # noqa: E402  (the DAP Interval; its codec is below)
+
+_U64_MAX = (1 << 64) - 1
+
+
+def _interval_encode(iv: Interval) -> bytes:
+    """Interval (messages/src/lib.rs:219-260): u64 start || u64 duration, seconds."""
+    return struct.pack(">QQ", iv.start, iv.duration)
+
+
+def _interval_from(r: _Reader) -> Interval:
+    start, duration = r.u64(), r.u64()
+    if start + duration > _U64_MAX:  # Interval::new refuses an end past u64 (:232-240)
+        raise CodecError("interval end overflows u64")
+    return Interval(start, duration)
+
+
+def encode_interval(iv: Interval) -> bytes:
+    return _interval_encode(iv)
+
+
+def decode_interval(b: bytes) -> Interval:
+    r = _Reader(b)
+    iv = _interval_from(r)
+    r.done()
+    return iv
+
+
+def _expect_query_type(r: _Reader, query_type: int) -> None:
+    if query_type not in (QUERY_TIME_INTERVAL, QUERY_FIXED_SIZE):
+        raise ValueError("unknown query type")
+    if r.u8() != query_type:  # query_type::Code::decode_expecting_value
+        raise CodecError("unexpected query type")
+
+
+@dataclass(frozen=True)
+class BatchSelector:
+    """query type byte, then the batch interval under TimeInterval and the 32-byte batch id under FixedSize
+    (messages/src/lib.rs:2711-2777). Decoding expects the task's query type."""
+
+    query_type: int
+    batch_interval: Interval | None = None
+    batch_id: bytes | None = None
+
+    @classmethod
+    def time_interval(cls, batch_interval: Interval) -> "BatchSelector":
+        return cls(QUERY_TIME_INTERVAL, batch_interval=batch_interval)
+
+    @classmethod
+    def fixed_size(cls, batch_id: bytes) -> "BatchSelector":
+        return cls(QUERY_FIXED_SIZE, batch_id=bytes(batch_id))
+
+    def encode(self) -> bytes:
+        if self.query_type == QUERY_TIME_INTERVAL and self.batch_interval is not None:
+            return b"\x01" + _interval_encode(self.batch_interval)
+        if self.query_type != QUERY_FIXED_SIZE or self.batch_id is None or len(self.batch_id) != 32:
+            raise CodecError("TimeInterval carries an interval, FixedSize a 32-byte batch id; no other query type is known")
+        return b"\x02" + self.batch_id
+
+    @classmethod
+    def decode_from(cls, r: _Reader, query_type: int) -> "BatchSelector":
+        _expect_query_type(r, query_type)
+        if query_type == QUERY_TIME_INTERVAL:
+            return cls(query_type, batch_interval=_interval_from(r))
+        return cls(query_type, batch_id=r.take(32))
+
+    @classmethod
+    def decode(cls, b: bytes, query_type: int) -> "BatchSelector":
+        r = _Reader(b)
+        s = cls.decode_from(r, query_type)
+        r.done()
+        return s
+
+
+FIXED_SIZE_BY_BATCH_ID, FIXED_SIZE_CURRENT_BATCH = 0, 1  # FixedSizeQuery (messages/src/lib.rs:1422-1476)
+
+
+@dataclass(frozen=True)
+class Query:
+    """query type byte, then the query body (messages/src/lib.rs:1479-1550): the batch interval under TimeInterval; under
+    FixedSize a FixedSizeQuery, ByBatchId (0) with its batch id or CurrentBatch (1)."""
+
+    query_type: int
+    batch_interval: Interval | None = None
+    fixed_size_kind: int | None = None
+    batch_id: bytes | None = None
+
+    @classmethod
+    def time_interval(cls, batch_interval: Interval) -> "Query":
+        return cls(QUERY_TIME_INTERVAL, batch_interval=batch_interval)
+
+    @classmethod
+    def by_batch_id(cls, batch_id: bytes) -> "Query":
+        return cls(QUERY_FIXED_SIZE, fixed_size_kind=FIXED_SIZE_BY_BATCH_ID, batch_id=bytes(batch_id))
+
+    @classmethod
+    def current_batch(cls) -> "Query":
+        return cls(QUERY_FIXED_SIZE, fixed_size_kind=FIXED_SIZE_CURRENT_BATCH)
+
+    def encode(self) -> bytes:
+        if self.query_type == QUERY_TIME_INTERVAL and self.batch_interval is not None:
+            return b"\x01" + _interval_encode(self.batch_interval)
+        if self.query_type == QUERY_FIXED_SIZE and self.fixed_size_kind == FIXED_SIZE_CURRENT_BATCH:
+            return b"\x02\x01"
+        if self.query_type != QUERY_FIXED_SIZE or self.fixed_size_kind != FIXED_SIZE_BY_BATCH_ID or \
+                self.batch_id is None or len(self.batch_id) != 32:
+            raise CodecError("not a TimeInterval query nor a FixedSize one (ByBatchId with 32 bytes, CurrentBatch)")
+        return b"\x02\x00" + self.batch_id
+
+    @classmethod
+    def decode_from(cls, r: _Reader, query_type: int) -> "Query":
+        _expect_query_type(r, query_type)
+        if query_type == QUERY_TIME_INTERVAL:
+            return cls(query_type, batch_interval=_interval_from(r))
+        kind = r.u8()
+        if kind == FIXED_SIZE_BY_BATCH_ID:
+            return cls(query_type, fixed_size_kind=kind, batch_id=r.take(32))
+        if kind == FIXED_SIZE_CURRENT_BATCH:
+            return cls(query_type, fixed_size_kind=kind)
+        raise CodecError("unexpected FixedSizeQueryType value")
+
+    @classmethod
+    def decode(cls, b: bytes, query_type: int) -> "Query":
+        r = _Reader(b)
+        q = cls.decode_from(r, query_type)
+        r.done()
+        return q
+
+
+@dataclass(frozen=True)
+class CollectionReq:
+    """Query || u32-prefixed aggregation parameter (messages/src/lib.rs:1551-1600)."""
+
+    query: Query
+    aggregation_parameter: bytes = b""
+
+    MEDIA_TYPE = "application/dap-collect-req"
+
+    def encode(self) -> bytes:
+        return self.query.encode() + _o32(self.aggregation_parameter)
+
+    @classmethod
+    def decode(cls, b: bytes, query_type: int) -> "CollectionReq":
+        r = _Reader(b)
+        q = Query.decode_from(r, query_type)
+        param = r.opaque32()
+        r.done()
+        return cls(q, param)
+
+
+@dataclass(frozen=True)
+class AggregateShareReq:
+    """BatchSelector || u32-prefixed aggregation parameter || u64 report count || 32-byte ReportIdChecksum
+    (messages/src/lib.rs:2783-2864)."""
+
+    batch_selector: BatchSelector
+    aggregation_parameter: bytes
+    report_count: int
+    checksum: bytes
+
+    MEDIA_TYPE = "application/dap-aggregate-share-req"
+
+    def encode(self) -> bytes:
+        if len(self.checksum) != 32:
+            raise CodecError("a ReportIdChecksum is 32 bytes")
+        return (self.batch_selector.encode() + _o32(self.aggregation_parameter) + struct.pack(">Q", self.report_count) +
+                self.checksum)
+
+    @classmethod
+    def decode(cls, b: bytes, query_type: int) -> "AggregateShareReq":
+        r = _Reader(b)
+        sel = BatchSelector.decode_from(r, query_type)
+        param = r.opaque32()
+        count = r.u64()
+        checksum = r.take(32)
+        r.done()
+        return cls(sel, param, count, checksum)
+
+
+@dataclass(frozen=True)
+class AggregateShare:
+    """One HpkeCiphertext: the helper's encrypted aggregate share (messages/src/lib.rs:2869-2908)."""
+
+    encrypted_aggregate_share: HpkeCiphertext
+
+    MEDIA_TYPE = "application/dap-aggregate-share"
+
+    def encode(self) -> bytes:
+        return self.encrypted_aggregate_share.encode()
+
+    @classmethod
+    def decode(cls, b: bytes) -> "AggregateShare":
+        r = _Reader(b)
+        ct = HpkeCiphertext.decode_from(r)
+        r.done()
+        return cls(ct)
+
+
+@dataclass(frozen=True)
+class Collection:
+    """PartialBatchSelector || u64 report count || Interval || the leader's HpkeCiphertext || the helper's
+    (messages/src/lib.rs:1726-1817)."""
+
+    partial_batch_selector: PartialBatchSelector
+    report_count: int
+    interval: Interval
+    leader_encrypted_agg_share: HpkeCiphertext
+    helper_encrypted_agg_share: HpkeCiphertext
+
+    MEDIA_TYPE = "application/dap-collection"
+
+    def encode(self) -> bytes:
+        return (self.partial_batch_selector.encode() + struct.pack(">Q", self.report_count) +
+                _interval_encode(self.interval) + self.leader_encrypted_agg_share.encode() +
+                self.helper_encrypted_agg_share.encode())
+
+    @classmethod
+    def decode(cls, b: bytes, query_type: int) -> "Collection":
+        r = _Reader(b)
+        sel = PartialBatchSelector.decode_from(r, query_type)
+        count = r.u64()
+        iv = _interval_from(r)
+        leader = HpkeCiphertext.decode_from(r)
+        helper = HpkeCiphertext.decode_from(r)
+        r.done()
+        return cls(sel, count, iv, leader, helper)
+
+
+@dataclass(frozen=True)
+class AggregateShareAad:
+    """The associated data of an encrypted aggregate share: task id || u32-prefixed aggregation parameter ||
+    BatchSelector (messages/src/lib.rs:1887-1952)."""
+
+    task_id: bytes
+    aggregation_parameter: bytes
+    batch_selector: BatchSelector
+
+    def encode(self) -> bytes:
+        if len(self.task_id) != 32:
+            raise CodecError("a task id is 32 bytes")
+        return self.task_id + _o32(self.aggregation_parameter) + self.batch_selector.encode()
+
+    @classmethod
+    def decode(cls, b: bytes, query_type: int) -> "AggregateShareAad":
+        r = _Reader(b)
+        task_id = r.take(32)
+        param = r.opaque32()
+        sel = BatchSelector.decode_from(r, query_type)
+        r.done()
+        return cls(task_id, param, sel)
