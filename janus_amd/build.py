@@ -27,7 +27,7 @@ HEADERS = [os.path.join(_HERE, "csrc", f) for f in ("jx_field.h", "jx_keccak.h",
                                                   "jx_hpke_open.h", "jx_k1_plan.h", "jx_fused_plan.h", "jx_ghash_lanes.h",
                                                   "jx_hpke_long.h", "jx_upload.h", "jx_chapoly_lanes.h", "jx_enc_rows.h",
                                                   "jx_ntt.h", "jx_shard.h", "jx_sample.h", "jx_carve.h", "jx_hpke_seal.h",
-                                                  "jx_wire.h", "jx_wire_dev.h", "jx_collect.h")]
+                                                  "jx_wire.h", "jx_wire_dev.h", "jx_collect.h", "jx_engine_call.h")]
 OUT = os.path.join(_HERE, "lib", "libjanus_prio3.so")
 # jx_mp64.hip: keep the LDS for the AES table (the AMDGPU backend would otherwise move a small private
 # array of the out-of-line helpers into LDS, +16 KiB per workgroup, one workgroup less per CU)

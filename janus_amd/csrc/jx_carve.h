@@ -19,10 +19,20 @@ class Carver {
     off_ += align256(bytes ? bytes : 1);
   }
   size_t bytes() const { return off_; }
+  // The regions taken so far are a prefix that something treats as one (a handle's pinned host copy): its length.
+  size_t mark() { return mark_ = off_; }
+  size_t marked() const { return mark_; }
 
  private:
   uint8_t* base_;
-  size_t off_ = 0;
+  size_t off_ = 0, mark_ = 0;
 };
+
+// Where p, a pointer into the buffer at `base`, lies in a second buffer at `other` that holds a copy of it.
+template <class T>
+const T* same_offset(const T* p, const void* base, const void* other) {
+  return reinterpret_cast<const T*>(static_cast<const uint8_t*>(other) +
+                                    (reinterpret_cast<const uint8_t*>(p) - static_cast<const uint8_t*>(base)));
+}
 
 }  // namespace jxi

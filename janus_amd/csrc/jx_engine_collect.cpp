@@ -18,21 +18,6 @@ namespace {
 
 bool aligned8(const void* p) { return ((uintptr_t)p & 7u) == 0; }
 
-// The uploads of a device-form call's host arrays: an event recorded behind them, before the kernels are queued, and
-// waited for once they are, so the host arrays have left pageable memory when the call returns and the kernels stay
-// queued.
-struct Uploads {
-  hipEvent_t ev = nullptr;
-  ~Uploads() {
-    if (ev) (void)hipEventDestroy(ev);
-  }
-  hipError_t queued(hipStream_t s) {
-    hipError_t st = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-    return st == hipSuccess ? hipEventRecord(ev, s) : st;
-  }
-  hipError_t consumed() { return hipEventSynchronize(ev); }
-};
-
 // offsets[n + 1], non-decreasing, rebased to start at 0
 bool rebase(const uint64_t* off, uint64_t n, std::vector<uint64_t>& out) {
   out.resize(n + 1);
@@ -122,8 +107,7 @@ int32_t collect_seal(jx_engine* e, bool host, uint64_t njobs, const uint8_t* rec
     return cv.bytes();
   };
   Scratch mem;  // the call holds nothing else: it may wait for the arena
-  if (const int32_t rc = scratch_get(e, lay(nullptr), mem, true)) return rc;
-  lay(mem.p());
+  if (const int32_t rc = scratch_carve(e, mem, lay, true)) return rc;
   hipStream_t s = e->stream;
   if (!host) {
     d_rec = const_cast<uint8_t*>(records);
@@ -148,7 +132,7 @@ int32_t collect_seal(jx_engine* e, bool host, uint64_t njobs, const uint8_t* rec
     HIPCHK(e, hipMemcpyAsync(d_ecs, expect_checksums, njobs * 32, hipMemcpyHostToDevice, s));
   }
   HIPCHK(e, hipMemsetAsync(d_bad, 0, njobs * 4, s));
-  Uploads up;
+  Uploads up;  // behind the host arrays, before the kernels
   if (!host) HIPCHK(e, up.queued(s));
 
   CollectMergeArgs m{};
@@ -296,8 +280,7 @@ int32_t collect_open(jx_engine* e, bool host, jx_hpke* leader, jx_hpke* helper, 
     return cv.bytes();
   };
   Scratch mem;  // the call holds nothing else: it may wait for the arena
-  if (const int32_t rc = scratch_get(e, lay(nullptr), mem, true)) return rc;
-  lay(mem.p());
+  if (const int32_t rc = scratch_carve(e, mem, lay, true)) return rc;
   hipStream_t s = e->stream;
   if (!host) {
     d_out = out_aggregates;

@@ -1,7 +1,8 @@
 // jx_engine_internal.h — engine internals shared by the engine's host sources: jx_engine.cpp (staging, resident
 // batches, the K1 -> K3 sequencing, the ABI's lifetime and plumbing calls), the call families jx_engine_cfg.cpp,
-// _prep.cpp, _acc.cpp, _fused.cpp, _upload.cpp, _shard.cpp, _seal.cpp, _wire.cpp and _wire_upload.cpp, jx_arena.cpp (the per-device memory arena) and
-// jx_coalesce.cpp (the per-device job coalescer). Not part of the ABI: include/jx_prio3.h is.
+// _prep.cpp, _acc.cpp, _fused.cpp, _upload.cpp, _shard.cpp, _seal.cpp, _collect.cpp, _wire.cpp and _wire_upload.cpp,
+// jx_arena.cpp (the per-device memory arena) and jx_coalesce.cpp (the per-device job coalescer). The call plumbing
+// the families share is jx_engine_call.h, included at the end. Not part of the ABI: include/jx_prio3.h is.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -480,3 +481,5 @@ void coalescer_set_min_jobs(jx_engine* e, uint32_t jobs);     // debug option 7
 void coalescer_release(jx_engine* e);
 
 }  // namespace jxi
+
+#include "jx_engine_call.h"

@@ -48,7 +48,7 @@ int32_t seal_args(jx_engine* e, const uint8_t task_id[32], jx_hpke* leader, jx_h
 // a launch's times are copied in after the launch before it, in stream order
 int32_t seal_launches(jx_engine* e, ClientSealArgs a, uint64_t n, uint64_t chunk, const uint64_t* times,
                       uint64_t* d_times) {
-  const uint64_t lct = 6ull + a.lis_bytes + 16, hct = 6ull + a.his_bytes + 16;
+  const uint64_t lct = sealed_lis_bytes(e->cfg), hct = sealed_his_bytes(e->cfg);
   for (uint64_t off = 0; off < n; off += chunk) {
     const uint64_t m = n - off < chunk ? n - off : chunk;
     a.n = m;
@@ -75,8 +75,8 @@ extern "C" {
 
 int32_t jx_client_seal_sizes(const jx_engine* e, uint32_t* leader_ct_len, uint32_t* helper_ct_len) {
   if (!e) return JX_E_INVALID;
-  if (leader_ct_len) *leader_ct_len = 6 + e->cfg.lis_bytes + 16;
-  if (helper_ct_len) *helper_ct_len = 6 + e->cfg.his_bytes + 16;
+  if (leader_ct_len) *leader_ct_len = (uint32_t)sealed_lis_bytes(e->cfg);
+  if (helper_ct_len) *helper_ct_len = (uint32_t)sealed_his_bytes(e->cfg);
   return JX_OK;
 }
 
@@ -119,17 +119,11 @@ int32_t jx_client_seal_device(jx_engine* e, uint64_t n, const void* d_report_ids
     return cv.bytes();
   };
   Scratch mem;  // the call holds nothing else: it may wait for the arena
-  if (const int32_t rc = scratch_get(e, lay(nullptr), mem, true)) return rc;
-  lay(mem.p());
+  if (const int32_t rc = scratch_carve(e, mem, lay, true)) return rc;
   a.ctx = d_ctx;
   if (const int32_t rc = seal_launches(e, a, n, chunk, times, d_times)) return rc;
   // the times leave pageable host memory before the call returns; the launches themselves stay queued
-  hipEvent_t ev = nullptr;
-  hipError_t st = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-  if (st == hipSuccess) st = hipEventRecord(ev, e->stream);
-  if (st == hipSuccess) st = hipEventSynchronize(ev);
-  if (ev) (void)hipEventDestroy(ev);
-  HIPCHK(e, st);
+  HIPCHK(e, wait_uploads(e));
   return JX_OK;
 }
 
@@ -152,7 +146,7 @@ int32_t jx_client_seal_batch(jx_engine* e, uint64_t n, const uint8_t* report_ids
   HIPCHK(e, hipSetDevice(e->device));
   const uint64_t dev_stride = (c.lis_bytes + 15u) & ~15ull;  // the device rows; the caller's are lis_stride apart
   a.lis_stride = dev_stride;
-  const uint64_t lct = 6ull + c.lis_bytes + 16, hct = 6ull + c.his_bytes + 16;
+  const uint64_t lct = sealed_lis_bytes(c), hct = sealed_his_bytes(c);
   const uint64_t chunk = seal_chunk(e, n);
   uint64_t* d_times = nullptr;
   uint8_t *d_ctx = nullptr, *d_ids = nullptr, *d_ps = nullptr, *d_lis = nullptr, *d_his = nullptr, *d_sks = nullptr,
@@ -175,8 +169,7 @@ int32_t jx_client_seal_batch(jx_engine* e, uint64_t n, const uint8_t* report_ids
     return cv.bytes();
   };
   Scratch mem;  // the call holds nothing else: it may wait for the arena
-  if (const int32_t rc = scratch_get(e, lay(nullptr), mem, true)) return rc;
-  lay(mem.p());
+  if (const int32_t rc = scratch_carve(e, mem, lay, true)) return rc;
   a.ctx = d_ctx;
   a.ids = d_ids;
   a.ps = c.ps_bytes ? d_ps : nullptr;

@@ -125,9 +125,7 @@ int32_t jx_client_shard_device(jx_engine* e, uint64_t n, const void* d_measureme
   if (!d_measurements || !d_nonces || !d_rands || !d_out_leader_input_shares || !d_out_helper_input_shares ||
       (a.ps_bytes && !d_out_public_shares))
     return JX_E_INVALID;
-  if (lis_stride == 0) lis_stride = a.lis_bytes;
-  if (lis_stride < a.lis_bytes || (lis_stride != a.lis_bytes && (lis_stride & 15u)))
-    return fail(e, JX_E_INVALID, "shard: the row stride must be 0, or >= the leader input share and a multiple of 16");
+  if (const int32_t rc = lis_stride_ok(e, &lis_stride, "shard")) return rc;
   if ((reinterpret_cast<uintptr_t>(d_out_leader_input_shares) & 15u) || (reinterpret_cast<uintptr_t>(d_measurements) & 7u) ||
       ((reinterpret_cast<uintptr_t>(d_nonces) | reinterpret_cast<uintptr_t>(d_rands) |
         reinterpret_cast<uintptr_t>(d_out_public_shares) | reinterpret_cast<uintptr_t>(d_out_helper_input_shares)) & 3u))
@@ -149,8 +147,7 @@ int32_t jx_client_shard_device(jx_engine* e, uint64_t n, const void* d_measureme
     return cv.bytes();
   };
   Scratch mem;  // the call holds nothing else: it may wait for the arena
-  if (const int32_t rc = scratch_get(e, lay(nullptr), mem, true)) return rc;
-  lay(mem.p());
+  if (const int32_t rc = scratch_carve(e, mem, lay, true)) return rc;
   return shard_launches(e, a, n, chunk, (uint8_t*)d_out_status);
 }
 
@@ -186,8 +183,7 @@ int32_t jx_client_shard_batch(jx_engine* e, uint64_t n, const uint64_t* measurem
     return cv.bytes();
   };
   Scratch mem;  // the call holds nothing else: it may wait for the arena
-  if (const int32_t rc = scratch_get(e, lay(nullptr), mem, true)) return rc;
-  lay(mem.p());
+  if (const int32_t rc = scratch_carve(e, mem, lay, true)) return rc;
   a.meas = d_meas;
   a.nonces = d_non;
   a.rands = d_rand;

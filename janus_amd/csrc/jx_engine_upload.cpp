@@ -15,7 +15,6 @@ namespace {
 int32_t upload_rows(jx_engine* e, uint64_t n, const uint64_t* times, jx_hpke* const* keypairs, uint32_t nkeypairs,
                     const uint8_t* key_index, const uint64_t* enc_offsets, const uint64_t* payload_offsets,
                     uint64_t* lis_stride, std::vector<UpRow>& rows, bool* any_p256) {
-  const Cfg& c = e->cfg;
   if (nkeypairs > JX_ENC_MAX_KEYPAIRS || (nkeypairs && !keypairs))
     return fail(e, JX_E_INVALID, "upload open: at most JX_ENC_MAX_KEYPAIRS keypairs");
   uint32_t klen[JX_ENC_MAX_KEYPAIRS];
@@ -30,9 +29,7 @@ int32_t upload_rows(jx_engine* e, uint64_t n, const uint64_t* times, jx_hpke* co
     slot[k] = hpke_slot(keypairs[k]);
     *any_p256 = *any_p256 || klen[k] == 65;
   }
-  if (*lis_stride == 0) *lis_stride = c.lis_bytes;
-  if (*lis_stride < c.lis_bytes || (*lis_stride != c.lis_bytes && (*lis_stride & 15u)))
-    return fail(e, JX_E_INVALID, "upload open: the row stride must be 0, or >= the leader input share and a multiple of 16");
+  if (const int32_t rc = lis_stride_ok(e, lis_stride, "upload open")) return rc;
   rows.resize(n);
   for (uint64_t i = 0; i < n; i++) {
     const uint8_t k0 = key_index[2 * i], k1 = key_index[2 * i + 1];
@@ -128,20 +125,14 @@ int32_t jx_leader_upload_open_device(jx_engine* e, uint64_t n, const void* d_rep
     return cv.bytes();
   };
   Scratch mem;  // the call holds nothing else: it may wait for the arena
-  int32_t rc = scratch_get(e, lay(nullptr), mem, true);
+  int32_t rc = scratch_carve(e, mem, lay, true);
   if (rc) return rc;
-  lay(mem.p());
   rc = upload_launch(e, n, rows, any_p256, task_id, (const uint8_t*)d_report_ids, (const uint8_t*)d_public_shares,
                      (const uint8_t*)d_encs, (const uint8_t*)d_payloads, d_pt - c0, d_rows, d_ctx, (uint8_t*)d_out_rows,
                      lis_stride, (uint8_t*)d_out_extensions, (uint32_t*)d_out_ext_len, (uint8_t*)d_out_status);
   if (rc) return rc;
   // the rows leave pageable host memory before the call returns; the launch itself stays queued
-  hipEvent_t ev = nullptr;
-  hipError_t st = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
-  if (st == hipSuccess) st = hipEventRecord(ev, e->stream);
-  if (st == hipSuccess) st = hipEventSynchronize(ev);
-  if (ev) (void)hipEventDestroy(ev);
-  HIPCHK(e, st);
+  HIPCHK(e, wait_uploads(e));
   return JX_OK;
 }
 
@@ -188,9 +179,8 @@ int32_t jx_leader_upload_open_batch(jx_engine* e, uint64_t n, const uint8_t* rep
     return cv.bytes();
   };
   Scratch mem;  // the call holds nothing else: it may wait for the arena
-  int32_t rc = scratch_get(e, lay(nullptr), mem, true);
+  int32_t rc = scratch_carve(e, mem, lay, true);
   if (rc) return rc;
-  lay(mem.p());
   HIPCHK(e, hipMemcpyAsync(d_ids, report_ids, n * 16, hipMemcpyHostToDevice, e->stream));
   if (c.ps_bytes) HIPCHK(e, hipMemcpyAsync(d_ps, public_shares, n * c.ps_bytes, hipMemcpyHostToDevice, e->stream));
   if (enc_bytes) HIPCHK(e, hipMemcpyAsync(d_enc, encs + e0, enc_bytes, hipMemcpyHostToDevice, e->stream));

@@ -30,9 +30,8 @@ struct jx_init_req {
   jx_engine* e = nullptr;
   jx_init_req_info_t info{};
   jx_init_req_arrays_t arr{};
-  Slab arrays;  // the pinned copy's device side (times .. wire_status), then route and the two rows arrays
-  Slab packed;  // the encapsulated keys and the payloads, packed
-  void* host = nullptr;  // pinned
+  Mirror arrays;  // times .. wire_status with their pinned copy, then route and the two rows arrays
+  Slab packed;    // the encapsulated keys and the payloads, packed
   bool has_deadline = false;
   uint64_t deadline = 0;
   uint64_t n = 0;
@@ -48,10 +47,9 @@ struct jx_init_req {
 struct jx_leader_req {
   jx_engine* e = nullptr;
   uint64_t n = 0, n_sent = 0, body_len = 0;
-  Slab dev;  // sent_index u32[n] | sent_ids [n x 16]
+  Mirror dev;  // sent_index u32[n] | sent_ids [n x 16], and the pinned copy of both
   uint32_t* d_sent_index = nullptr;
   uint8_t* d_sent_ids = nullptr;
-  void* host = nullptr;  // pinned: the same two arrays
   const uint32_t* sent_index = nullptr;
   const uint8_t* sent_ids = nullptr;
   PinnedBuf up;  // a response decode's one upload: the body, then where each row's prep message lies
@@ -62,33 +60,16 @@ namespace {
 void req_free(jx_init_req* r) {
   if (!r) return;
   jx_engine* e = r->e;
-  if (r->arrays.p) arena_put(e->arena, r->arrays, e->stream);
+  r->arrays.put(e);
   if (r->packed.p) arena_put(e->arena, r->packed, e->stream);
-  if (r->host) (void)hipHostFree(r->host);
+  r->arrays.free(e);
   delete r;
 }
-
-// frees the handle unless the decode hands it out
-struct ReqGuard {
-  jx_init_req* r;
-  ~ReqGuard() { req_free(r); }
-  jx_init_req* give() {
-    jx_init_req* x = r;
-    r = nullptr;
-    return x;
-  }
-};
+using ReqGuard = HandleGuard<jx_init_req, req_free>;
 
 int32_t read_state(jx_engine* e, const WireState* d_st, WireState& st) {
   HIPCHK(e, hipMemcpyAsync(&st, d_st, sizeof st, hipMemcpyDeviceToHost, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));
-  return JX_OK;
-}
-
-int32_t slab_get(jx_engine* e, size_t bytes, Slab& out, const char* what) {
-  const hipError_t st = arena_get(e->arena, bytes, e->stream, false, false, out);
-  if (st == hipErrorOutOfMemory) return fail(e, JX_E_NOMEM, std::string(what) + ": the device arena cannot hold it");
-  HIPCHK(e, st);
   return JX_OK;
 }
 
@@ -119,8 +100,7 @@ int32_t decode_core(jx_engine* e, const uint8_t* d_body, uint64_t len, uint32_t 
     return cv.bytes();
   };
   Scratch small;
-  if (const int32_t rc = scratch_get(e, lay0(nullptr), small)) return rc;
-  lay0(small.p());
+  if (const int32_t rc = scratch_carve(e, small, lay0)) return rc;
   HIPCHK(e, hipMemsetAsync(d_st, 0, sizeof(WireState), e->stream));
   uint8_t keys[512];
   memcpy(keys, key_first, 256);
@@ -166,7 +146,7 @@ int32_t decode_core(jx_engine* e, const uint8_t* d_body, uint64_t len, uint32_t 
   info.fallback_iterations = st.iters;
   if (st.status != WIRE_OK) return refuse(st.status, st.err_off);
   const uint64_t n = st.n, nfast = st.nfast;
-  if (n >= 0x7FFFFFFFull) return fail(e, JX_E_UNSUPPORTED, "init req: more than 2^31 - 2 PrepareInits in one request");
+  if (const int32_t rc = call_count_ok(e, n, "init req", "PrepareInits")) return rc;
   if (nfast < n && !one_pass) {
     if (const int32_t rc = scratch_get(e, (n - nfast) * 8, offs_mem)) return rc;
     d_offs = (uint64_t*)offs_mem.p();
@@ -174,7 +154,6 @@ int32_t decode_core(jx_engine* e, const uint8_t* d_body, uint64_t len, uint32_t 
   }
 
   // ---- phase 3: records, per-report scalars, the duplicate check, the scans
-  size_t host_bytes = 0;
   auto lay = [&](void* base) {
     Carver cv(base);
     cv.take(r->times, n * 8);
@@ -184,14 +163,13 @@ int32_t decode_core(jx_engine* e, const uint8_t* d_body, uint64_t len, uint32_t 
     cv.take(r->ids, n * 16);
     cv.take(r->key_index, n * 2);
     cv.take(r->wire_status, n);
-    host_bytes = cv.bytes();  // up to here: one copy to the pinned buffer
+    r->arrays.host_bytes = cv.mark();  // up to here: one copy to the pinned buffer
     cv.take(r->route, n * 4);
     cv.take(r->ps, n * c.ps_bytes);
     cv.take(r->lps, n * c.lps_bytes);
     return cv.bytes();
   };
-  if (const int32_t rc = slab_get(e, lay(nullptr), r->arrays, "init req arrays")) return rc;
-  lay(r->arrays.p);
+  if (const int32_t rc = slab_carve(e, r->arrays.slab, lay, "init req arrays")) return rc;
   const uint64_t slots = 2 * n;
   Scratch tab;
   if (const int32_t rc = scratch_get(e, slots * 4, tab)) return rc;
@@ -227,8 +205,7 @@ int32_t decode_core(jx_engine* e, const uint8_t* d_body, uint64_t len, uint32_t 
   if (st.dup != WIRE_NO_DUPLICATE) {
     info.status = WIRE_DUPLICATE_ID;
     info.duplicate_index = st.dup;
-    arena_put(e->arena, r->arrays, e->stream);
-    r->arrays = Slab{};
+    r->arrays.put(e);
     *out = g.give();
     return JX_OK;
   }
@@ -243,17 +220,13 @@ int32_t decode_core(jx_engine* e, const uint8_t* d_body, uint64_t len, uint32_t 
     cv.take(r->payloads, st.pay_total);
     return cv.bytes();
   };
-  if (const int32_t rc = slab_get(e, layp(nullptr), r->packed, "init req ciphertexts")) return rc;
-  layp(r->packed.p);
+  if (const int32_t rc = slab_carve(e, r->packed, layp, "init req ciphertexts")) return rc;
   a.encs = r->encs;
   a.payloads = r->payloads;
   HIPCHK(e, launch_wire_gather(a, e->stream));
-  HIPCHK(e, hipHostMalloc(&r->host, host_bytes, hipHostMallocDefault));
-  HIPCHK(e, hipMemcpyAsync(r->host, r->arrays.p, host_bytes, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (const int32_t rc = r->arrays.download(e)) return rc;
+  const Mirror& M = r->arrays;
   r->n = n;
-  const uint8_t *hb = (const uint8_t*)r->host, *db = (const uint8_t*)r->arrays.p;
-  auto host_of = [&](const void* d) { return hb + ((const uint8_t*)d - db); };
   jx_init_req_arrays_t& A = r->arr;
   A.d_report_ids = r->ids;
   A.d_times = r->times;
@@ -267,13 +240,13 @@ int32_t decode_core(jx_engine* e, const uint8_t* d_body, uint64_t len, uint32_t 
   A.d_wire_status = r->wire_status;
   A.d_route = r->route;
   A.d_records = r->recs;
-  A.times = (const uint64_t*)host_of(r->times);
-  A.enc_offsets = (const uint64_t*)host_of(r->eoff);
-  A.payload_offsets = (const uint64_t*)host_of(r->poff);
-  A.records = (const jx_wire_record*)host_of(r->recs);
-  A.report_ids = host_of(r->ids);
-  A.key_index = host_of(r->key_index);
-  A.wire_status = host_of(r->wire_status);
+  A.times = M.host_of(r->times);
+  A.enc_offsets = M.host_of(r->eoff);
+  A.payload_offsets = M.host_of(r->poff);
+  A.records = (const jx_wire_record*)M.host_of(r->recs);
+  A.report_ids = M.host_of(r->ids);
+  A.key_index = M.host_of(r->key_index);
+  A.wire_status = M.host_of(r->wire_status);
   *out = g.give();
   return JX_OK;
 }
@@ -310,8 +283,7 @@ int32_t encode_core(jx_engine* e, jx_init_req* r, const void* d_verdicts, const 
     return cv.bytes();
   };
   Scratch mem;
-  if (const int32_t rc = scratch_get(e, lay(nullptr), mem, true)) return rc;
-  lay(mem.p());
+  if (const int32_t rc = scratch_carve(e, mem, lay, true)) return rc;
   if (n && host_errors) HIPCHK(e, hipMemcpyAsync(d_herr, host_errors, n, hipMemcpyHostToDevice, e->stream));
   if (n && replayed) HIPCHK(e, hipMemcpyAsync(d_rep, replayed, n, hipMemcpyHostToDevice, e->stream));
   WireEncodeArgs a{};
@@ -355,20 +327,10 @@ void leader_req_free(jx_leader_req* r) {
   jx_engine* e = r->e;
   if (r->up.ev) (void)hipEventSynchronize(r->up.ev);  // the last decode's upload has read the pinned buffer
   r->up.destroy();
-  if (r->dev.p) arena_put(e->arena, r->dev, e->stream);
-  if (r->host) (void)hipHostFree(r->host);
+  r->dev.free(e);
   delete r;
 }
-
-struct LeaderReqGuard {
-  jx_leader_req* r;
-  ~LeaderReqGuard() { leader_req_free(r); }
-  jx_leader_req* give() {
-    jx_leader_req* x = r;
-    r = nullptr;
-    return x;
-  }
-};
+using LeaderReqGuard = HandleGuard<jx_leader_req, leader_req_free>;
 
 // what both forms of the request encode take; the bulk pointers are device pointers by the time req_encode_core runs
 struct ReqIn {
@@ -390,7 +352,7 @@ int32_t req_check(jx_engine* e, const ReqIn& in, uint64_t* bound) {
   if (in.query_type != JX_QUERY_TIME_INTERVAL && in.query_type != JX_QUERY_FIXED_SIZE) return JX_E_INVALID;
   if (in.query_type == JX_QUERY_FIXED_SIZE && !in.batch_id) return JX_E_INVALID;
   if (in.agg_param_len > 0xFFFFFFFFull || (in.agg_param_len && !in.agg_param)) return JX_E_INVALID;
-  if (in.n >= 0x7FFFFFFFull) return fail(e, JX_E_UNSUPPORTED, "init req encode: more than 2^31 - 2 reports in one request");
+  if (const int32_t rc = call_count_ok(e, in.n, "init req encode", "reports")) return rc;
   if (in.n && (!in.ids || !in.times || !in.config_ids || !in.payload_offsets || !in.encs || !in.lps || !in.verdicts ||
                (c.ps_bytes && !in.ps)))
     return JX_E_INVALID;
@@ -440,17 +402,14 @@ int32_t req_encode_core(jx_engine* e, const ReqIn& in, uint8_t* d_out, uint64_t 
     return cv.bytes();
   };
   Scratch mem;
-  if (const int32_t rc = scratch_get(e, lay(nullptr), mem, may_wait)) return rc;
-  lay(mem.p());
+  if (const int32_t rc = scratch_carve(e, mem, lay, may_wait)) return rc;
   auto layh = [&](void* base) {
     Carver cv(base);
     cv.take(r->d_sent_index, n * 4);
     cv.take(r->d_sent_ids, n * 16);
-    return cv.bytes();
+    return r->dev.host_bytes = cv.mark();  // all of it has a pinned copy
   };
-  const size_t handle_bytes = layh(nullptr);
-  if (const int32_t rc = slab_get(e, handle_bytes, r->dev, "init req encode")) return rc;
-  layh(r->dev.p);
+  if (const int32_t rc = slab_carve(e, r->dev.slab, layh, "init req encode")) return rc;
   if (n) {
     HIPCHK(e, hipMemcpyAsync(d_times, in.times, n * 8, hipMemcpyHostToDevice, e->stream));
     if (in.enc_offsets) HIPCHK(e, hipMemcpyAsync(d_eoff, in.enc_offsets, (n + 1) * 8, hipMemcpyHostToDevice, e->stream));
@@ -493,12 +452,9 @@ int32_t req_encode_core(jx_engine* e, const ReqIn& in, uint8_t* d_out, uint64_t 
   const uint64_t total = a.header_len + t.vec_bytes;
   if (capacity < total) return fail(e, JX_E_INVALID, "init req encode: the output buffer is shorter than the request body");
   HIPCHK(e, launch_wire_req_pack(a, t.n_sent, (uint32_t)t.vec_bytes, e->stream));
-  HIPCHK(e, hipHostMalloc(&r->host, handle_bytes, hipHostMallocDefault));
-  HIPCHK(e, hipMemcpyAsync(r->host, r->dev.p, handle_bytes, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  const uint8_t *hb = (const uint8_t*)r->host, *db = (const uint8_t*)r->dev.p;
-  r->sent_index = (const uint32_t*)(hb + ((const uint8_t*)r->d_sent_index - db));
-  r->sent_ids = hb + (r->d_sent_ids - db);
+  if (const int32_t rc = r->dev.download(e)) return rc;
+  r->sent_index = r->dev.host_of(r->d_sent_index);
+  r->sent_ids = r->dev.host_of(r->d_sent_ids);
   r->n_sent = t.n_sent;
   r->body_len = total;
   *out_len = total;
@@ -577,12 +533,7 @@ int32_t jx_init_resp_encode(jx_engine* e, jx_init_req* r, const void* d_verdicts
                      capacity, out_len, out_finished);
 }
 
-void jx_init_req_release(jx_init_req* r) {
-  if (!r) return;
-  std::lock_guard<FairMutex> lk(r->e->mu);
-  (void)hipSetDevice(r->e->device);
-  req_free(r);
-}
+void jx_init_req_release(jx_init_req* r) { handle_release(r, req_free); }
 
 int32_t jx_init_req_encode_bound(const jx_engine* e, uint64_t n, const uint64_t* enc_offsets, const uint64_t* payload_offsets,
                                  uint64_t agg_param_len, uint32_t query_type, uint64_t* out_bound) {
@@ -648,8 +599,7 @@ int32_t jx_init_req_encode(jx_engine* e, uint64_t n, const uint8_t* report_ids, 
     return cv.bytes();
   };
   Scratch mem;  // the call holds nothing else yet: it may wait for the arena
-  if (const int32_t rc = scratch_get(e, lay(nullptr), mem, true)) return rc;
-  lay(mem.p());
+  if (const int32_t rc = scratch_carve(e, mem, lay, true)) return rc;
   if (n) {
     HIPCHK(e, hipMemcpyAsync(d_ids, report_ids, n * 16, hipMemcpyHostToDevice, e->stream));
     if (c.ps_bytes) HIPCHK(e, hipMemcpyAsync(d_ps, public_shares, n * c.ps_bytes, hipMemcpyHostToDevice, e->stream));
@@ -756,11 +706,6 @@ int32_t jx_init_resp_decode(jx_engine* e, jx_leader_req* r, const uint8_t* body,
   return JX_OK;
 }
 
-void jx_leader_req_release(jx_leader_req* r) {
-  if (!r) return;
-  std::lock_guard<FairMutex> lk(r->e->mu);
-  (void)hipSetDevice(r->e->device);
-  leader_req_free(r);
-}
+void jx_leader_req_release(jx_leader_req* r) { handle_release(r, leader_req_free); }
 
 }  // extern "C"

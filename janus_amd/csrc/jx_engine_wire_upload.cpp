@@ -22,9 +22,8 @@ struct jx_upload_req {
   jx_engine* e = nullptr;
   jx_upload_req_info_t info{};
   jx_upload_req_arrays_t arr{};
-  Slab arrays;  // the pinned copy's device side, then the dense ids and public-share rows
-  Slab packed;  // the four packed fields
-  void* host = nullptr;  // pinned
+  Mirror arrays;  // the arrays with a pinned copy, then the dense ids and public-share rows
+  Slab packed;    // the four packed fields
 };
 
 namespace {
@@ -32,28 +31,12 @@ namespace {
 void upload_req_free(jx_upload_req* r) {
   if (!r) return;
   jx_engine* e = r->e;
-  if (r->arrays.p) arena_put(e->arena, r->arrays, e->stream);
+  r->arrays.put(e);
   if (r->packed.p) arena_put(e->arena, r->packed, e->stream);
-  if (r->host) (void)hipHostFree(r->host);
+  r->arrays.free(e);
   delete r;
 }
-
-struct UploadReqGuard {
-  jx_upload_req* r;
-  ~UploadReqGuard() { upload_req_free(r); }
-  jx_upload_req* give() {
-    jx_upload_req* x = r;
-    r = nullptr;
-    return x;
-  }
-};
-
-int32_t slab_get(jx_engine* e, size_t bytes, Slab& out, const char* what) {
-  const hipError_t st = arena_get(e->arena, bytes, e->stream, false, false, out);
-  if (st == hipErrorOutOfMemory) return fail(e, JX_E_NOMEM, std::string(what) + ": the device arena cannot hold it");
-  HIPCHK(e, st);
-  return JX_OK;
-}
+using UploadReqGuard = HandleGuard<jx_upload_req, upload_req_free>;
 
 // Waves per report for m reports of `bytes` together: one, unless so few reports with such long fields that one wave
 // each would leave most of the device without work; then slices of at least 4 KiB, up to about 8192 waves in all.
@@ -79,7 +62,7 @@ bool decode_args_ok(jx_engine* e, const void* bodies, uint64_t len, uint64_t n, 
 
 // what is refused from the host array alone, with nothing queued
 int32_t offsets_check(jx_engine* e, uint64_t len, uint64_t n, const uint64_t* body_offsets) {
-  if (n >= 0x7FFFFFFFull) return fail(e, JX_E_UNSUPPORTED, "upload decode: more than 2^31 - 2 uploads in one call");
+  if (const int32_t rc = call_count_ok(e, n, "upload decode", "uploads")) return rc;
   for (uint64_t i = 0; i < n; i++)
     if (body_offsets[i + 1] < body_offsets[i]) return fail(e, JX_E_INVALID, "upload decode: body_offsets must not decrease");
   if (n && body_offsets[n] > len) return fail(e, JX_E_INVALID, "upload decode: a body offset lies past the bodies' length");
@@ -102,7 +85,6 @@ int32_t decode_core(jx_engine* e, const uint8_t* d_bodies, uint64_t n, const uin
   }
   WireUploadArgs a{};
   // the handle's arrays: sized by n, of which the dense ones use m
-  size_t host_bytes = 0;
   auto lay = [&](void* base) {
     Carver cv(base);
     cv.take(a.times_all, n * 8);
@@ -114,13 +96,12 @@ int32_t decode_core(jx_engine* e, const uint8_t* d_bodies, uint64_t n, const uin
     cv.take(a.key_index, n * 2);
     cv.take(a.config_ids, n);
     cv.take(a.status, n);
-    host_bytes = cv.bytes();  // up to here: one copy to the pinned buffer
+    r->arrays.host_bytes = cv.mark();  // up to here: one copy to the pinned buffer
     cv.take(a.ids, n * 16);
     cv.take(a.ps, n * c.ps_bytes);
     return cv.bytes();
   };
-  if (const int32_t rc = slab_get(e, lay(nullptr), r->arrays, "upload arrays")) return rc;
-  lay(r->arrays.p);
+  if (const int32_t rc = slab_carve(e, r->arrays.slab, lay, "upload arrays")) return rc;
   // the call's own scratch
   uint64_t* d_boff = nullptr;
   uint8_t* d_keys = nullptr;
@@ -135,8 +116,7 @@ int32_t decode_core(jx_engine* e, const uint8_t* d_bodies, uint64_t n, const uin
     return cv.bytes();
   };
   Scratch mem;
-  if (const int32_t rc = scratch_get(e, lays(nullptr), mem)) return rc;
-  lays(mem.p());
+  if (const int32_t rc = scratch_carve(e, mem, lays)) return rc;
   uint8_t keys[512];
   memcpy(keys, key_first, 256);
   memcpy(keys + 256, key_second, 256);
@@ -168,16 +148,12 @@ int32_t decode_core(jx_engine* e, const uint8_t* d_bodies, uint64_t n, const uin
     cv.take(a.packed[3], t.hpay_bytes);
     return cv.bytes();
   };
-  if (const int32_t rc = slab_get(e, layp(nullptr), r->packed, "upload ciphertexts")) return rc;
-  layp(r->packed.p);
+  if (const int32_t rc = slab_carve(e, r->packed, layp, "upload ciphertexts")) return rc;
   const uint64_t m = t.m;
   const uint64_t field_bytes = t.lenc_bytes + t.lpay_bytes + t.henc_bytes + t.hpay_bytes;
   HIPCHK(e, launch_wire_upload_gather(a, m, copy_parts(e, m, field_bytes), e->stream));
-  HIPCHK(e, hipHostMalloc(&r->host, host_bytes, hipHostMallocDefault));
-  HIPCHK(e, hipMemcpyAsync(r->host, r->arrays.p, host_bytes, hipMemcpyDeviceToHost, e->stream));
-  HIPCHK(e, hipStreamSynchronize(e->stream));
-  const uint8_t *hb = (const uint8_t*)r->host, *db = (const uint8_t*)r->arrays.p;
-  auto host_of = [&](const void* d) { return hb + ((const uint8_t*)d - db); };
+  if (const int32_t rc = r->arrays.download(e)) return rc;
+  const Mirror& M = r->arrays;
   jx_upload_req_arrays_t& A = r->arr;
   A.d_index = a.index;
   A.d_report_ids = a.ids;
@@ -197,18 +173,18 @@ int32_t decode_core(jx_engine* e, const uint8_t* d_bodies, uint64_t n, const uin
   A.d_all_times = a.times_all;
   A.d_upload_status = a.status;
   A.d_row_of = a.row_of;
-  A.index = (const uint32_t*)host_of(a.index);
-  A.times = (const uint64_t*)host_of(a.times);
-  A.key_index = host_of(a.key_index);
-  A.leader_enc_offsets = (const uint64_t*)host_of(a.offs[0]);
-  A.leader_payload_offsets = (const uint64_t*)host_of(a.offs[1]);
-  A.helper_enc_offsets = (const uint64_t*)host_of(a.offs[2]);
-  A.helper_payload_offsets = (const uint64_t*)host_of(a.offs[3]);
-  A.helper_config_ids = host_of(a.config_ids);
-  A.all_report_ids = host_of(a.ids_all);
-  A.all_times = (const uint64_t*)host_of(a.times_all);
-  A.upload_status = host_of(a.status);
-  A.row_of = (const uint32_t*)host_of(a.row_of);
+  A.index = M.host_of(a.index);
+  A.times = M.host_of(a.times);
+  A.key_index = M.host_of(a.key_index);
+  A.leader_enc_offsets = M.host_of(a.offs[0]);
+  A.leader_payload_offsets = M.host_of(a.offs[1]);
+  A.helper_enc_offsets = M.host_of(a.offs[2]);
+  A.helper_payload_offsets = M.host_of(a.offs[3]);
+  A.helper_config_ids = M.host_of(a.config_ids);
+  A.all_report_ids = M.host_of(a.ids_all);
+  A.all_times = M.host_of(a.times_all);
+  A.upload_status = M.host_of(a.status);
+  A.row_of = M.host_of(a.row_of);
   jx_upload_req_info_t& info = r->info;
   info.m = m;
   info.leader_enc_bytes = t.lenc_bytes;
@@ -236,11 +212,11 @@ int32_t report_check(jx_engine* e, const ReportIn& in, uint64_t* bound) {
   const Cfg& c = e->cfg;
   if (in.lenc_len >= (1u << 16) || in.henc_len >= (1u << 16))
     return fail(e, JX_E_INVALID, "report encode: an encapsulated key of 2^16 bytes or more");
-  if (in.n >= 0x7FFFFFFFull) return fail(e, JX_E_UNSUPPORTED, "report encode: more than 2^31 - 2 reports in one call");
+  if (const int32_t rc = call_count_ok(e, in.n, "report encode", "reports")) return rc;
   if (in.n && (!in.ids || !in.times || !in.lcts || !in.hcts || (c.ps_bytes && !in.ps) || (in.lenc_len && !in.lencs) ||
                (in.henc_len && !in.hencs)))
     return JX_E_INVALID;
-  *bound = in.n * wire_report_len(c.ps_bytes, in.lenc_len, 6ull + c.lis_bytes + 16, in.henc_len, 6ull + c.his_bytes + 16);
+  *bound = in.n * wire_report_len(c.ps_bytes, in.lenc_len, sealed_lis_bytes(c), in.henc_len, sealed_his_bytes(c));
   return JX_OK;
 }
 
@@ -262,8 +238,7 @@ int32_t report_encode_core(jx_engine* e, const ReportIn& in, uint8_t* d_out, uin
     return cv.bytes();
   };
   Scratch mem;
-  if (const int32_t rc = scratch_get(e, lay(nullptr), mem, may_wait)) return rc;
-  lay(mem.p());
+  if (const int32_t rc = scratch_carve(e, mem, lay, may_wait)) return rc;
   if (n) HIPCHK(e, hipMemcpyAsync(d_times, in.times, n * 8, hipMemcpyHostToDevice, e->stream));
   a.n = n;
   a.ids = in.ids;
@@ -276,9 +251,9 @@ int32_t report_encode_core(jx_engine* e, const ReportIn& in, uint8_t* d_out, uin
   a.status = in.status;
   a.ps_bytes = c.ps_bytes;
   a.lenc_len = in.lenc_len;
-  a.lct_len = 6 + c.lis_bytes + 16;
+  a.lct_len = (uint32_t)sealed_lis_bytes(c);
   a.henc_len = in.henc_len;
-  a.hct_len = 6 + c.his_bytes + 16;
+  a.hct_len = (uint32_t)sealed_his_bytes(c);
   a.leader_config_id = in.leader_config_id;
   a.helper_config_id = in.helper_config_id;
   a.out = d_out;
@@ -337,19 +312,14 @@ int32_t jx_upload_req_arrays(const jx_upload_req* r, jx_upload_req_arrays_t* out
   return JX_OK;
 }
 
-void jx_upload_req_release(jx_upload_req* r) {
-  if (!r) return;
-  std::lock_guard<FairMutex> lk(r->e->mu);
-  (void)hipSetDevice(r->e->device);
-  upload_req_free(r);
-}
+void jx_upload_req_release(jx_upload_req* r) { handle_release(r, upload_req_free); }
 
 int32_t jx_report_encode_bound(const jx_engine* e, uint64_t n, uint32_t leader_enc_len, uint32_t helper_enc_len,
                                uint64_t* out_bound) {
-  if (!e || !out_bound || leader_enc_len >= (1u << 16) || helper_enc_len >= (1u << 16) || n >= 0x7FFFFFFFull)
+  if (!e || !out_bound || leader_enc_len >= (1u << 16) || helper_enc_len >= (1u << 16) || !call_count_fits(n))
     return JX_E_INVALID;
-  *out_bound = n * wire_report_len(e->cfg.ps_bytes, leader_enc_len, 6ull + e->cfg.lis_bytes + 16, helper_enc_len,
-                                   6ull + e->cfg.his_bytes + 16);
+  *out_bound = n * wire_report_len(e->cfg.ps_bytes, leader_enc_len, sealed_lis_bytes(e->cfg), helper_enc_len,
+                                   sealed_his_bytes(e->cfg));
   return JX_OK;
 }
 
@@ -384,7 +354,7 @@ int32_t jx_report_encode(jx_engine* e, uint64_t n, const uint8_t* report_ids, co
   uint64_t bound = 0;
   if (const int32_t rc = report_check(e, in, &bound)) return rc;
   HIPCHK(e, hipSetDevice(e->device));
-  const uint64_t lct = 6ull + c.lis_bytes + 16, hct = 6ull + c.his_bytes + 16;
+  const uint64_t lct = sealed_lis_bytes(c), hct = sealed_his_bytes(c);
   uint8_t *d_ids = nullptr, *d_ps = nullptr, *d_le = nullptr, *d_lc = nullptr, *d_he = nullptr, *d_hc = nullptr,
           *d_st = nullptr, *d_body = nullptr;
   auto lay = [&](void* base) {
@@ -400,8 +370,7 @@ int32_t jx_report_encode(jx_engine* e, uint64_t n, const uint8_t* report_ids, co
     return cv.bytes();
   };
   Scratch mem;  // the call holds nothing else yet: it may wait for the arena
-  if (const int32_t rc = scratch_get(e, lay(nullptr), mem, true)) return rc;
-  lay(mem.p());
+  if (const int32_t rc = scratch_carve(e, mem, lay, true)) return rc;
   if (n) {
     HIPCHK(e, hipMemcpyAsync(d_ids, report_ids, n * 16, hipMemcpyHostToDevice, e->stream));
     if (c.ps_bytes) HIPCHK(e, hipMemcpyAsync(d_ps, public_shares, n * c.ps_bytes, hipMemcpyHostToDevice, e->stream));

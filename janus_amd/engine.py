@@ -96,6 +96,32 @@ def _u8(a, n: int, width: int, what: str) -> np.ndarray:
     return arr
 
 
+_U64P = ctypes.POINTER(ctypes.c_uint64)
+
+
+def _u64p(a: np.ndarray | None):
+    return None if a is None else a.ctypes.data_as(_U64P)
+
+
+def _items(a, n: int, dtype, *row) -> np.ndarray:
+    """n items (rows of shape `row`) of dtype, contiguous; a 1-item dummy the call never reads when n is 0."""
+    if not n:
+        return np.zeros((1, *row), dtype)
+    return np.ascontiguousarray(np.asarray(a, dtype=dtype).reshape(n, *row))
+
+
+def _offs(a, n: int) -> np.ndarray:
+    """n + 1 uint64 offsets, contiguous."""
+    return np.ascontiguousarray(np.asarray(a, dtype=np.uint64).reshape(n + 1))
+
+
+def _packed(items) -> tuple[np.ndarray, np.ndarray]:
+    """Byte strings laid back to back (one zero byte when there are none) and their len(items) + 1 offsets."""
+    off = np.zeros(len(items) + 1, np.uint64)
+    off[1:] = np.cumsum([len(x) for x in items], dtype=np.uint64)
+    return np.frombuffer(b"".join(bytes(x) for x in items) or b"\0", np.uint8).copy(), off
+
+
 def _seg_table(segment_ids):
     ids = np.ascontiguousarray(np.asarray(segment_ids, dtype=np.uint32).reshape(-1))
     if ids.size == 0:
@@ -194,15 +220,55 @@ class _DeviceBytes:
         self.__cuda_array_interface__ = {"shape": (nbytes,), "typestr": "|u1", "data": (ptr, False), "version": 2}
 
 
-class InitReq:
+class _Req:
+    """What the request handles share: a C handle that owns device arrays and a pinned host copy of the small ones.
+    A subclass names its release symbol (_RELEASE) and the attributes whose memory goes with the handle (_VIEWS)."""
+
+    def __init__(self, engine: "HelperEngine", handle):
+        self._engine, self._h = engine, handle
+
+    @staticmethod
+    def view(ptr, dtype, count):  # count items at ptr, the handle's pinned host memory, without a copy
+        if count == 0:
+            return np.zeros(0, dtype)
+        buf = (ctypes.c_uint8 * (np.dtype(dtype).itemsize * count)).from_address(ptr)
+        return np.frombuffer(buf, dtype=dtype, count=count)
+
+    def _device_tensor(self, name: str, size: int):  # d.d_<name> as torch uint8[size]; empty when there is none
+        import torch
+
+        dev = torch.device("cuda", self._engine.device)
+        ptr = getattr(self.d, "d_" + name) if self.d is not None else None
+        if not size or not ptr:
+            return torch.zeros(0, dtype=torch.uint8, device=dev)
+        return torch.as_tensor(_DeviceBytes(ptr, size), device=dev)
+
+    def release(self):
+        if self._h:
+            for name in self._VIEWS:  # the views' memory goes with the handle
+                setattr(self, name, None)
+            getattr(self._engine._L, self._RELEASE)(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.release()
+
+
+class InitReq(_Req):
     """A decoded AggregationJobInitializeReq (jx_init_req): the request's status, and for an accepted one the device
     arrays the sealed fused call reads (`d`, a _lib.JxInitReqArrays of device pointers) with the pinned host copy of
     the small ones as numpy views: times, enc_offsets, payload_offsets, key_index, wire_status, report_ids, records
     (WIRE_RECORD). Holds device memory until release() (or the end of a `with`), which must come before the engine's
     close()."""
 
+    _RELEASE = "jx_init_req_release"
+    _VIEWS = ("times", "enc_offsets", "payload_offsets", "records", "report_ids", "key_index", "wire_status", "d")
+
     def __init__(self, engine: "HelperEngine", handle):
-        self._engine, self._h = engine, handle
+        super().__init__(engine, handle)
         L = engine._L
         info = _lib.JxInitReqInfo()
         check(L.jx_init_req_info(handle, ctypes.byref(info)), engine._h, "jx_init_req_info")
@@ -217,12 +283,7 @@ class InitReq:
         if self.status == WIRE_OK and n:
             a = _lib.JxInitReqArrays()
             check(L.jx_init_req_arrays(handle, ctypes.byref(a)), engine._h, "jx_init_req_arrays")
-            self.d = a
-
-            def view(ptr, dtype, count):
-                buf = (ctypes.c_uint8 * (np.dtype(dtype).itemsize * count)).from_address(ptr)
-                return np.frombuffer(buf, dtype=dtype, count=count)
-
+            self.d, view = a, self.view
             self.times = view(a.times, np.uint64, n)
             self.enc_offsets = view(a.enc_offsets, np.uint64, n + 1)
             self.payload_offsets = view(a.payload_offsets, np.uint64, n + 1)
@@ -239,50 +300,35 @@ class InitReq:
     def device_bytes(self, name: str):
         """One of the device arrays (report_ids, times, public_shares, leader_prep_shares, encs, enc_offsets, payloads,
         payload_offsets, key_index, wire_status, route, records) as a torch uint8 tensor over the handle's memory."""
-        import torch
-
         e, n = self._engine, self.n
         size = {"report_ids": 16 * n, "times": 8 * n, "public_shares": n * e.public_share_len,
                 "leader_prep_shares": n * e.prep_share_len, "encs": self.enc_bytes, "enc_offsets": 8 * (n + 1),
                 "payloads": self.payload_bytes, "payload_offsets": 8 * (n + 1), "key_index": 2 * n, "wire_status": n,
                 "route": 4 * n, "records": WIRE_RECORD.itemsize * n}[name]
-        ptr = getattr(self.d, "d_" + name) if self.d is not None else None
-        if not size or not ptr:
-            return torch.zeros(0, dtype=torch.uint8, device=torch.device("cuda", e.device))
-        return torch.as_tensor(_DeviceBytes(ptr, size), device=torch.device("cuda", e.device))
+        return self._device_tensor(name, size)
 
     def exclude(self, mask):
         """Route the reports with mask[i] away from every aggregation (jx_init_req_exclude)."""
-        m = np.ascontiguousarray(np.asarray(mask).astype(np.uint8).reshape(self.n)) if self.n else np.zeros(1, np.uint8)
+        m = _items(np.asarray(mask).astype(np.uint8), self.n, np.uint8)
         check(self._engine._L.jx_init_req_exclude(self._h, _ptr(m)), self._engine._h, "jx_init_req_exclude")
-
-    def release(self):
-        if self._h:
-            self.times = self.enc_offsets = self.payload_offsets = self.records = self.report_ids = None
-            self.key_index = self.wire_status = self.d = None  # the views' memory goes with the handle
-            self._engine._L.jx_init_req_release(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.release()
 
 
 WIRE_RESP_MISMATCH = 4         # JX_WIRE_RESP_MISMATCH: the response's PrepareResps are not the sent reports in order
 RESP_CONTINUED, RESP_REJECTED, RESP_FINISHED, RESP_MESSAGE_MISMATCH = 0, 1, 2, 3  # JX_RESP_*
 
 
-class LeaderReq:
+class LeaderReq(_Req):
     """An encoded AggregationJobInitializeReq (jx_leader_req): `body` (bytes; the device form copies it from its
     device buffer `d_body`, a torch uint8 tensor, when first asked), `body_len`, `n` (rows of the leader batch),
     `n_sent` and `sent_index` (numpy uint32[n_sent]: sent report k is row sent_index[k]; `d_sent_index` is the same
     list on the device). Holds device memory until release() (or the end of a `with`), which must come before the
     engine's close()."""
 
+    _RELEASE = "jx_leader_req_release"
+    _VIEWS = ("d_sent_index",)
+
     def __init__(self, engine: "HelperEngine", handle, body: bytes | None = None, d_body=None):
-        self._engine, self._h = engine, handle
+        super().__init__(engine, handle)
         L = engine._L
         info = _lib.JxLeaderReqInfo()
         check(L.jx_leader_req_info(handle, ctypes.byref(info)), engine._h, "jx_leader_req_info")
@@ -290,11 +336,7 @@ class LeaderReq:
         hp, dp = ctypes.c_void_p(), ctypes.c_void_p()
         check(L.jx_leader_req_sent(handle, ctypes.byref(hp), ctypes.byref(dp)), engine._h, "jx_leader_req_sent")
         self.d_sent_index = dp.value
-        if self.n_sent:
-            buf = (ctypes.c_uint8 * (4 * self.n_sent)).from_address(hp.value)
-            self.sent_index = np.frombuffer(buf, dtype=np.uint32, count=self.n_sent).copy()
-        else:
-            self.sent_index = np.zeros(0, np.uint32)
+        self.sent_index = self.view(hp.value, np.uint32, self.n_sent).copy()
         self._body, self.d_body = body, d_body
 
     @property
@@ -302,18 +344,6 @@ class LeaderReq:
         if self._body is None:
             self._body = self.d_body[:self.body_len].cpu().numpy().tobytes()
         return self._body
-
-    def release(self):
-        if self._h:
-            self._engine._L.jx_leader_req_release(self._h)
-            self._h = None
-            self.d_sent_index = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.release()
 
 
 @dataclass
@@ -331,7 +361,7 @@ UPLOAD_OK, UPLOAD_MALFORMED, UPLOAD_TOO_EARLY, UPLOAD_TASK_EXPIRED, UPLOAD_EXPIR
 UPLOAD_NO_ROW = 0xFFFFFFFF     # row_of[i] of an upload that is not accepted
 
 
-class UploadReq:
+class UploadReq(_Req):
     """A batch of decoded upload bodies (jx_upload_req). For all n uploads, numpy views of the pinned host copy:
     status (UPLOAD_*), row_of (UPLOAD_NO_ROW where not accepted), report_ids (n x 16) and all_times. For the m accepted
     reports, dense and in order: index (accepted report k is upload index[k]), times, key_index (m x 2),
@@ -341,10 +371,11 @@ class UploadReq:
     the engine's close()."""
 
     _VIEWS = ("status", "row_of", "report_ids", "all_times", "index", "times", "key_index", "leader_enc_offsets",
-              "leader_payload_offsets", "helper_enc_offsets", "helper_payload_offsets", "helper_config_ids")
+              "leader_payload_offsets", "helper_enc_offsets", "helper_payload_offsets", "helper_config_ids", "d")
+    _RELEASE = "jx_upload_req_release"
 
     def __init__(self, engine: "HelperEngine", handle):
-        self._engine, self._h = engine, handle
+        super().__init__(engine, handle)
         L = engine._L
         info = _lib.JxUploadReqInfo()
         check(L.jx_upload_req_info(handle, ctypes.byref(info)), engine._h, "jx_upload_req_info")
@@ -353,65 +384,29 @@ class UploadReq:
         self.helper_enc_bytes, self.helper_payload_bytes = int(info.helper_enc_bytes), int(info.helper_payload_bytes)
         self.status_count = [int(x) for x in info.status_count]
         n, m = self.n, self.m
-        self.d = None
-        if n:
-            a = _lib.JxUploadReqArrays()
-            check(L.jx_upload_req_arrays(handle, ctypes.byref(a)), engine._h, "jx_upload_req_arrays")
-            self.d = a
-
-            def view(ptr, dtype, count):
-                if count == 0:
-                    return np.zeros(0, dtype)
-                buf = (ctypes.c_uint8 * (np.dtype(dtype).itemsize * count)).from_address(ptr)
-                return np.frombuffer(buf, dtype=dtype, count=count)
-
-            self.status = view(a.upload_status, np.uint8, n)
-            self.row_of = view(a.row_of, np.uint32, n)
-            self.report_ids = view(a.all_report_ids, np.uint8, 16 * n).reshape(n, 16)
-            self.all_times = view(a.all_times, np.uint64, n)
-            self.index = view(a.index, np.uint32, m)
-            self.times = view(a.times, np.uint64, m)
-            self.key_index = view(a.key_index, np.uint8, 2 * m).reshape(m, 2)
-            self.leader_enc_offsets = view(a.leader_enc_offsets, np.uint64, m + 1)
-            self.leader_payload_offsets = view(a.leader_payload_offsets, np.uint64, m + 1)
-            self.helper_enc_offsets = view(a.helper_enc_offsets, np.uint64, m + 1)
-            self.helper_payload_offsets = view(a.helper_payload_offsets, np.uint64, m + 1)
-            self.helper_config_ids = view(a.helper_config_ids, np.uint8, m)
-        else:
-            self.status, self.row_of = np.zeros(0, np.uint8), np.zeros(0, np.uint32)
-            self.report_ids, self.all_times = np.zeros((0, 16), np.uint8), np.zeros(0, np.uint64)
-            self.index, self.times, self.key_index = np.zeros(0, np.uint32), np.zeros(0, np.uint64), np.zeros((0, 2), np.uint8)
-            self.leader_enc_offsets = self.leader_payload_offsets = np.zeros(1, np.uint64)
-            self.helper_enc_offsets = self.helper_payload_offsets = np.zeros(1, np.uint64)
-            self.helper_config_ids = np.zeros(0, np.uint8)
+        a = _lib.JxUploadReqArrays()  # all null for a call of no uploads
+        check(L.jx_upload_req_arrays(handle, ctypes.byref(a)), engine._h, "jx_upload_req_arrays")
+        self.d, view = (a if n else None), self.view
+        offs = (lambda p: view(p, np.uint64, m + 1)) if n else (lambda p: np.zeros(1, np.uint64))
+        self.status = view(a.upload_status, np.uint8, n)
+        self.row_of = view(a.row_of, np.uint32, n)
+        self.report_ids = view(a.all_report_ids, np.uint8, 16 * n).reshape(n, 16)
+        self.all_times = view(a.all_times, np.uint64, n)
+        self.index = view(a.index, np.uint32, m)
+        self.times = view(a.times, np.uint64, m)
+        self.key_index = view(a.key_index, np.uint8, 2 * m).reshape(m, 2)
+        self.leader_enc_offsets, self.leader_payload_offsets = offs(a.leader_enc_offsets), offs(a.leader_payload_offsets)
+        self.helper_enc_offsets, self.helper_payload_offsets = offs(a.helper_enc_offsets), offs(a.helper_payload_offsets)
+        self.helper_config_ids = view(a.helper_config_ids, np.uint8, m)
 
     def device_bytes(self, name: str):
         """One of the device arrays of the accepted reports (report_ids, public_shares, leader_encs, leader_payloads,
         helper_encs, helper_payloads) as a torch uint8 tensor over the handle's memory."""
-        import torch
-
         e, m = self._engine, self.m
         size = {"report_ids": 16 * m, "public_shares": m * e.public_share_len, "leader_encs": self.leader_enc_bytes,
                 "leader_payloads": self.leader_payload_bytes, "helper_encs": self.helper_enc_bytes,
                 "helper_payloads": self.helper_payload_bytes}[name]
-        ptr = getattr(self.d, "d_" + name) if self.d is not None else None
-        if not size or not ptr:
-            return torch.zeros(0, dtype=torch.uint8, device=torch.device("cuda", e.device))
-        return torch.as_tensor(_DeviceBytes(ptr, size), device=torch.device("cuda", e.device))
-
-    def release(self):
-        if self._h:
-            for name in self._VIEWS:  # the views' memory goes with the handle
-                setattr(self, name, None)
-            self.d = None
-            self._engine._L.jx_upload_req_release(self._h)
-            self._h = None
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.release()
+        return self._device_tensor(name, size)
 
 
 class HelperEngine:
@@ -425,6 +420,7 @@ class HelperEngine:
         # guards the per-instance defaults (last leader batch) when threads share the engine; the
         # C engine serializes the calls themselves
         self._lock = threading.Lock()
+        self._init_reqs = weakref.WeakSet()  # live request handles: they hold the engine's arena memory
         if len(verify_key) != vdaf.verify_key_len:
             raise ValueError(f"verify key must be {vdaf.verify_key_len} bytes for {vdaf.name()} "
                              "(VERIFY_KEY_LENGTH / VERIFY_KEY_LENGTH_HMACSHA256_AES128, core/src/vdaf.rs:16,24)")
@@ -452,10 +448,16 @@ class HelperEngine:
     # ------------------------------------------------------------------ lifecycle
     def close(self):
         if getattr(self, "_h", None):
-            for r in list(getattr(self, "_init_reqs", ())):  # decoded requests hold the engine's arena memory
+            for r in list(self._init_reqs):
                 r.release()
             self._L.jx_engine_destroy(self._h)
             self._h = None
+
+    def _track(self, req):
+        """Remember a request handle so that close() releases it if its owner has not."""
+        with self._lock:
+            self._init_reqs.add(req)
+        return req
 
     def __del__(self):
         try:
@@ -569,24 +571,18 @@ class HelperEngine:
         nn = _u8(nonces, n, 16, "nonces")
         ps = _u8(public_shares, n, self.public_share_len, "public_shares")
         lps = _u8(leader_prep_shares, n, self.prep_share_len, "leader_prep_shares")
-        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
-        ki = np.ascontiguousarray(np.asarray(key_index, dtype=np.uint8).reshape(n, 2)) if n else np.zeros((1, 2), np.uint8)
+        tm = _items(times, n, np.uint64)
+        ki = _items(key_index, n, np.uint8, 2)
         if isinstance(encs, (list, tuple)):
             if len(encs) != n:
                 raise ValueError("one encapsulated key per report")
-            en = np.frombuffer(b"".join(bytes(x) for x in encs) or b"\0", np.uint8).copy()
-            eoff = np.zeros(n + 1, np.uint64)
-            if n:
-                eoff[1:] = np.cumsum([len(x) for x in encs])
+            en, eoff = _packed(encs)
         else:
             en = _u8(encs, n, 32, "encs") if n else np.zeros((1, 32), np.uint8)
             eoff = np.arange(n + 1, dtype=np.uint64) * 32
         if len(task_id) != 32 or len(payloads) != n:
             raise ValueError("task id is 32 bytes; one payload per report")
-        off = np.zeros(n + 1, np.uint64)
-        if n:
-            off[1:] = np.cumsum([len(p) for p in payloads])
-        ct = np.frombuffer(b"".join(payloads) or b"\0", np.uint8).copy()
+        ct, off = _packed(payloads)
         task = np.frombuffer(task_id, np.uint8).copy()
         hs = (ctypes.c_void_p * max(1, len(keypairs)))(*[k.handle for k in keypairs])
         verdicts = np.zeros(max(n, 1), np.uint8)
@@ -594,10 +590,8 @@ class HelperEngine:
         msgs = np.zeros((max(n, 1), max(self.prep_msg_len, 1)), np.uint8)
         bid = ctypes.c_uint64()
         st = self._L.jx_helper_prep_encrypted_batch2(
-            self._h, n, _ptr(nn), tm.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
-            _ptr(ps) if self.public_share_len else None, _ptr(task), hs, len(keypairs), _ptr(ki), _ptr(en),
-            eoff.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _ptr(ct),
-            off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), ENC_REQUIRE_TASKPROV if require_taskprov else 0,
+            self._h, n, _ptr(nn), _u64p(tm), _ptr(ps) if self.public_share_len else None, _ptr(task), hs, len(keypairs),
+            _ptr(ki), _ptr(en), _u64p(eoff), _ptr(ct), _u64p(off), ENC_REQUIRE_TASKPROV if require_taskprov else 0,
             _ptr(lps), _ptr(msgs) if self.prep_msg_len else None, _ptr(verdicts), _ptr(status), ctypes.byref(bid))
         check(st, self._h, "jx_helper_prep_encrypted_batch2")
         if not keep:
@@ -787,7 +781,7 @@ class HelperEngine:
             raise ValueError("leader_input_shares: rows shorter than the leader input share")
         his = _u8(helper_input_shares, n, self.helper_input_share_len, "helper_input_shares")
         sks = _u8(ephemeral_sks, n, 64, "ephemeral_sks")
-        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
+        tm = _items(times, n, np.uint64)
         ss = None if shard_status is None else _u8(shard_status, n, 1, "shard_status")
         if len(task_id) != 32:
             raise ValueError("task id is 32 bytes")
@@ -795,7 +789,7 @@ class HelperEngine:
         lct, hct = self.client_seal_sizes()
         out = SealResult(np.zeros((n, 32), np.uint8), np.zeros((n, lct), np.uint8), np.zeros((n, 32), np.uint8),
                          np.zeros((n, hct), np.uint8), np.zeros(n, np.uint8))
-        check(self._L.jx_client_seal_batch(self._h, n, _ptr(ids), tm.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+        check(self._L.jx_client_seal_batch(self._h, n, _ptr(ids), _u64p(tm),
                                            _ptr(ps) if self.public_share_len and n else None, _ptr(lis), stride,
                                            _ptr(his), _ptr(task), leader_sealer.handle, helper_sealer.handle, _ptr(sks),
                                            _ptr(ss), _ptr(out.leader_encs), _ptr(out.leader_cts), _ptr(out.helper_encs),
@@ -812,12 +806,12 @@ class HelperEngine:
         against `stream` (module docstring): it reads the rows shard_device wrote, at the same lis_stride, and writes
         the ciphertext rows jx_leader_upload_open_device and jx_helper_prep_aggregate_encrypted_device read with
         payload offsets i x client_seal_sizes()."""
-        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
+        tm = _items(times, n, np.uint64)
         if len(task_id) != 32:
             raise ValueError("task id is 32 bytes")
         task = np.frombuffer(task_id, np.uint8).copy()
         with self._ordered(stream):
-            check(self._L.jx_client_seal_device(self._h, n, d_report_ids, tm.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)),
+            check(self._L.jx_client_seal_device(self._h, n, d_report_ids, _u64p(tm),
                                                 d_public_shares, d_leader_input_shares, lis_stride, d_helper_input_shares,
                                                 _ptr(task), leader_sealer.handle, helper_sealer.handle, d_ephemeral_sks,
                                                 d_shard_status, d_out_leader_encs, d_out_leader_cts, d_out_helper_encs,
@@ -857,29 +851,22 @@ class HelperEngine:
         n = int(np.asarray(report_ids).reshape(-1, 16).shape[0])
         ids = _u8(report_ids, n, 16, "report_ids")
         ps = _u8(public_shares, n, self.public_share_len, "public_shares")
-        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
-        ki = np.ascontiguousarray(np.asarray(key_index, dtype=np.uint8).reshape(n, 2)) if n else np.zeros((1, 2), np.uint8)
+        tm = _items(times, n, np.uint64)
+        ki = _items(key_index, n, np.uint8, 2)
         if isinstance(encs, (list, tuple)):
             if len(encs) != n:
                 raise ValueError("one encapsulated key per report")
-            en = np.frombuffer(b"".join(bytes(x) for x in encs) or b"\0", np.uint8).copy()
-            eoff = np.zeros(n + 1, np.uint64)
-            if n:
-                eoff[1:] = np.cumsum([len(x) for x in encs])
+            en, eoff = _packed(encs)
         else:
             en = _u8(encs, n, 32, "encs").reshape(-1) if n else np.zeros(32, np.uint8)
             eoff = np.arange(n + 1, dtype=np.uint64) * 32
         if len(task_id) != 32 or len(payloads) != n:
             raise ValueError("task id is 32 bytes; one payload per report")
-        off = np.zeros(n + 1, np.uint64)
-        if n:
-            off[1:] = np.cumsum([len(p) for p in payloads])
-        ct = np.frombuffer(b"".join(payloads) or b"\0", np.uint8).copy()
+        ct, off = _packed(payloads)
         task = np.frombuffer(task_id, np.uint8).copy()
         hs = (ctypes.c_void_p * max(1, len(keypairs)))(*[k.handle for k in keypairs])
         stride = lis_stride or self.leader_input_share_len
         dev = torch.device("cuda", self.device)
-        u64p = ctypes.POINTER(ctypes.c_uint64)
         with torch.cuda.device(dev):
             d_ids, d_ps, d_en, d_ct = (torch.from_numpy(a.reshape(-1).copy()).to(dev) for a in (ids, ps, en, ct))
             # 16 spare bytes: the rows start at the tensor's next 16-byte boundary whatever the allocator gives
@@ -891,9 +878,8 @@ class HelperEngine:
             d_st = torch.zeros(max(n, 1), dtype=torch.uint8, device=dev)
             with self._ordered(stream):
                 st = self._L.jx_leader_upload_open_device(
-                    self._h, n, d_ids.data_ptr(), tm.ctypes.data_as(u64p),
-                    d_ps.data_ptr() if self.public_share_len else None, _ptr(task), hs, len(keypairs), _ptr(ki),
-                    d_en.data_ptr(), eoff.ctypes.data_as(u64p), d_ct.data_ptr(), off.ctypes.data_as(u64p),
+                    self._h, n, d_ids.data_ptr(), _u64p(tm), d_ps.data_ptr() if self.public_share_len else None,
+                    _ptr(task), hs, len(keypairs), _ptr(ki), d_en.data_ptr(), _u64p(eoff), d_ct.data_ptr(), _u64p(off),
                     rows.data_ptr(), lis_stride, d_ext.data_ptr(), d_len.data_ptr(), d_st.data_ptr())
                 check(st, self._h, "jx_leader_upload_open_device")
             status, ext_len, ext = d_st.cpu().numpy()[:n], d_len.cpu().numpy()[:n], d_ext.cpu().numpy()
@@ -954,29 +940,23 @@ class HelperEngine:
         """The sealed-share arguments of the fused calls as host arrays (the conventions of
         helper_initialized_encrypted_batch): times, key-index pairs, the encapsulated keys packed with their
         offsets (None: n x 32), the payloads packed with theirs, the task id and the keypair handles."""
-        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
-        ki = np.ascontiguousarray(np.asarray(key_index, dtype=np.uint8).reshape(n, 2)) if n else np.zeros((1, 2), np.uint8)
+        tm = _items(times, n, np.uint64)
+        ki = _items(key_index, n, np.uint8, 2)
         if isinstance(encs, (list, tuple)):
             if len(encs) != n:
                 raise ValueError("one encapsulated key per report")
-            en = np.frombuffer(b"".join(bytes(x) for x in encs) or b"\0", np.uint8).copy()
-            eoff = np.zeros(n + 1, np.uint64)
-            if n:
-                eoff[1:] = np.cumsum([len(x) for x in encs])
+            en, eoff = _packed(encs)
         else:
             en = _u8(encs, n, 32, "encs").reshape(-1) if n else np.zeros(32, np.uint8)
             eoff = None
         if isinstance(payloads, (list, tuple)):
             if len(payloads) != n or payload_offsets is not None:
                 raise ValueError("one payload per report (a list carries its own offsets)")
-            off = np.zeros(n + 1, np.uint64)
-            if n:
-                off[1:] = np.cumsum([len(p) for p in payloads])
-            ct = np.frombuffer(b"".join(payloads) or b"\0", np.uint8).copy()
+            ct, off = _packed(payloads)
         else:
             if payload_offsets is None:
                 raise ValueError("packed payloads need payload_offsets (n + 1)")
-            off = np.ascontiguousarray(np.asarray(payload_offsets, dtype=np.uint64).reshape(n + 1))
+            off = _offs(payload_offsets, n)
             ct = np.ascontiguousarray(np.frombuffer(payloads, np.uint8) if isinstance(payloads, (bytes, bytearray))
                                       else payloads, dtype=np.uint8).reshape(-1)
             if ct.size == 0:
@@ -1005,12 +985,10 @@ class HelperEngine:
         verdicts = np.zeros(max(n, 1), np.uint8)
         status = np.zeros(max(n, 1), np.uint8)
         msgs = np.zeros((max(n, 1), max(self.prep_msg_len, 1)), np.uint8)
-        u64p = ctypes.POINTER(ctypes.c_uint64)
         st = self._L.jx_helper_prep_aggregate_encrypted(
-            self._h, n, _ptr(nn), tm.ctypes.data_as(u64p), _ptr(ps) if self.public_share_len else None, _ptr(task), hs,
-            len(keypairs), _ptr(ki), _ptr(en), eoff.ctypes.data_as(u64p) if eoff is not None else None, _ptr(ct),
-            off.ctypes.data_as(u64p), ENC_REQUIRE_TASKPROV if require_taskprov else 0, _ptr(lps), segment,
-            _ptr(msgs) if self.prep_msg_len else None, _ptr(verdicts), _ptr(status))
+            self._h, n, _ptr(nn), _u64p(tm), _ptr(ps) if self.public_share_len else None, _ptr(task), hs, len(keypairs),
+            _ptr(ki), _ptr(en), _u64p(eoff), _ptr(ct), _u64p(off), ENC_REQUIRE_TASKPROV if require_taskprov else 0,
+            _ptr(lps), segment, _ptr(msgs) if self.prep_msg_len else None, _ptr(verdicts), _ptr(status))
         check(st, self._h, "jx_helper_prep_aggregate_encrypted")
         return EncryptedResult(verdicts[:n], msgs[:n, : self.prep_msg_len], status[:n], 0)
 
@@ -1025,22 +1003,20 @@ class HelperEngine:
         (packed, report i's at payload_offsets[i]) and leader prep shares and for the three optional outputs; host
         arrays for times, key_index and the two offset arrays. The ciphertexts and keys are read in place.
         Segments and stream ordering as prep_and_aggregate_device."""
-        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
-        ki = np.ascontiguousarray(np.asarray(key_index, dtype=np.uint8).reshape(n, 2)) if n else np.zeros((1, 2), np.uint8)
-        off = np.ascontiguousarray(np.asarray(payload_offsets, dtype=np.uint64).reshape(n + 1))
-        eoff = None if enc_offsets is None else np.ascontiguousarray(np.asarray(enc_offsets, dtype=np.uint64).reshape(n + 1))
+        tm = _items(times, n, np.uint64)
+        ki = _items(key_index, n, np.uint8, 2)
+        off = _offs(payload_offsets, n)
+        eoff = None if enc_offsets is None else _offs(enc_offsets, n)
         if len(task_id) != 32:
             raise ValueError("task id is 32 bytes")
         task = np.frombuffer(task_id, np.uint8).copy()
         hs = (ctypes.c_void_p * max(1, len(keypairs)))(*[k.handle for k in keypairs])
         ids, ptr = _seg_table([segment] if segment_ids is None else segment_ids)
-        u64p = ctypes.POINTER(ctypes.c_uint64)
         with self._ordered(stream):
             st = self._L.jx_helper_prep_aggregate_encrypted_device(
-                self._h, n, d_nonces, tm.ctypes.data_as(u64p), d_public_shares, _ptr(task), hs, len(keypairs), _ptr(ki),
-                d_encs, eoff.ctypes.data_as(u64p) if eoff is not None else None, d_payloads, off.ctypes.data_as(u64p),
-                ENC_REQUIRE_TASKPROV if require_taskprov else 0, d_leader_prep_shares, d_segments, ptr, ids.size,
-                d_out_prep_msgs, d_out_verdicts, d_out_open_status)
+                self._h, n, d_nonces, _u64p(tm), d_public_shares, _ptr(task), hs, len(keypairs), _ptr(ki), d_encs,
+                _u64p(eoff), d_payloads, _u64p(off), ENC_REQUIRE_TASKPROV if require_taskprov else 0,
+                d_leader_prep_shares, d_segments, ptr, ids.size, d_out_prep_msgs, d_out_verdicts, d_out_open_status)
             check(st, self._h, "jx_helper_prep_aggregate_encrypted_device")
 
     # ------------------------------------------------------------------ wire in, wire out
@@ -1065,12 +1041,7 @@ class HelperEngine:
                 st = self._L.jx_init_req_decode_device(self._h, ptr, length, query_type, _ptr(kf), _ptr(ks), dl,
                                                        ctypes.byref(h))
                 check(st, self._h, "jx_init_req_decode_device")
-        req = InitReq(self, h)
-        with self._lock:
-            if not hasattr(self, "_init_reqs"):
-                self._init_reqs = weakref.WeakSet()
-            self._init_reqs.add(req)
-        return req
+        return self._track(InitReq(self, h))
 
     def encode_init_resp(self, req: InitReq, d_verdicts: int | None, d_open_status: int | None, d_prep_msgs: int | None,
                          host_errors=None, replayed=None, prep_msg_stride: int = 0, d_out: int | None = None,
@@ -1101,37 +1072,27 @@ class HelperEngine:
     # ------------------------------------------------------------------ the leader's end of the wire
     def _req_host_arrays(self, n: int, times, config_ids, enc_offsets, payload_offsets, exclude, agg_param, query_type,
                          batch_id):
-        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
-        cf = np.ascontiguousarray(np.asarray(config_ids, dtype=np.uint8).reshape(n)) if n else np.zeros(1, np.uint8)
-        off = np.ascontiguousarray(np.asarray(payload_offsets, dtype=np.uint64).reshape(n + 1))
-        eoff = None if enc_offsets is None else np.ascontiguousarray(np.asarray(enc_offsets, dtype=np.uint64).reshape(n + 1))
+        tm = _items(times, n, np.uint64)
+        cf = _items(config_ids, n, np.uint8)
+        off = _offs(payload_offsets, n)
+        eoff = None if enc_offsets is None else _offs(enc_offsets, n)
         ex = None if exclude is None or not n else np.ascontiguousarray(np.asarray(exclude).astype(np.uint8).reshape(n))
         par = np.frombuffer(bytes(agg_param) or b"\0", np.uint8)
         if query_type == 2 and (batch_id is None or len(batch_id) != 32):
             raise ValueError("FixedSize carries a 32-byte batch id")
         bid = None if batch_id is None else np.frombuffer(bytes(batch_id), np.uint8)
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        return (tm.ctypes.data_as(u64p), _ptr(cf), eoff.ctypes.data_as(u64p) if eoff is not None else None,
-                off.ctypes.data_as(u64p), _ptr(ex), _ptr(par), len(agg_param), query_type, _ptr(bid)), (tm, cf, off, eoff, ex, par, bid)
+        return (_u64p(tm), _ptr(cf), _u64p(eoff), _u64p(off), _ptr(ex), _ptr(par), len(agg_param), query_type,
+                _ptr(bid)), (tm, cf, off, eoff, ex, par, bid)
 
     def init_req_bound(self, n: int, payload_offsets, agg_param_len: int, query_type: int, enc_offsets=None) -> int:
         """The length of the request body if every report were sent (jx_init_req_encode_bound)."""
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        off = np.ascontiguousarray(np.asarray(payload_offsets, dtype=np.uint64).reshape(n + 1))
-        eoff = None if enc_offsets is None else np.ascontiguousarray(np.asarray(enc_offsets, dtype=np.uint64).reshape(n + 1))
+        off = _offs(payload_offsets, n)
+        eoff = None if enc_offsets is None else _offs(enc_offsets, n)
         out = ctypes.c_uint64()
-        check(self._L.jx_init_req_encode_bound(self._h, n, eoff.ctypes.data_as(u64p) if eoff is not None else None,
-                                               off.ctypes.data_as(u64p), agg_param_len, query_type, ctypes.byref(out)),
+        check(self._L.jx_init_req_encode_bound(self._h, n, _u64p(eoff), _u64p(off), agg_param_len, query_type,
+                                               ctypes.byref(out)),
               self._h, "jx_init_req_encode_bound")
         return out.value
-
-    def _leader_req(self, h, body=None, d_body=None) -> LeaderReq:
-        req = LeaderReq(self, h, body, d_body)
-        with self._lock:
-            if not hasattr(self, "_init_reqs"):
-                self._init_reqs = weakref.WeakSet()
-            self._init_reqs.add(req)
-        return req
 
     def encode_init_req(self, n: int, d_report_ids: int, times, d_public_shares: int | None, config_ids, d_encs: int,
                         d_payloads: int, payload_offsets, d_prep_shares: int, d_verdicts: int, agg_param: bytes = b"",
@@ -1165,7 +1126,7 @@ class HelperEngine:
             import torch
 
             d_body = torch.as_tensor(_DeviceBytes(d_out, ln.value), device=torch.device("cuda", self.device))
-        return self._leader_req(h, None, d_body)
+        return self._track(LeaderReq(self, h, None, d_body))
 
     def encode_init_req_host(self, report_ids, times, public_shares, config_ids, encs, payloads, payload_offsets,
                              prep_shares, verdicts, agg_param: bytes = b"", query_type: int = 1,
@@ -1178,7 +1139,7 @@ class HelperEngine:
         ids = _u8(report_ids, n, 16, "report_ids") if n else np.zeros((1, 16), np.uint8)
         ps = _u8(public_shares, n, self.public_share_len, "public_shares")
         lps = _u8(prep_shares, n, self.prep_share_len, "prep_shares")
-        vd = np.ascontiguousarray(np.asarray(verdicts, dtype=np.uint8).reshape(n)) if n else np.zeros(1, np.uint8)
+        vd = _items(verdicts, n, np.uint8)
         en = np.ascontiguousarray(np.frombuffer(bytes(encs) or b"\0", np.uint8))
         pay = np.ascontiguousarray(np.frombuffer(bytes(payloads) or b"\0", np.uint8))
         args, keep = self._req_host_arrays(n, times, config_ids, enc_offsets, payload_offsets, exclude, agg_param,
@@ -1192,7 +1153,7 @@ class HelperEngine:
                                         _ptr(out), cap, ctypes.byref(ln), ctypes.byref(h))
         check(st, self._h, "jx_init_req_encode")
         del keep
-        return self._leader_req(h, out[:ln.value].tobytes())
+        return self._track(LeaderReq(self, h, out[:ln.value].tobytes()))
 
     def decode_init_resp(self, req: LeaderReq, body: bytes, d_out_prep_msgs: int | None, d_out_peer_verdicts: int | None,
                          prep_msg_stride: int = 0, stream=None) -> InitRespDecode:
@@ -1232,7 +1193,7 @@ class HelperEngine:
         of report_bound). Ordered against `stream` like the other device-pointer methods; waits for its result."""
         import torch
 
-        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
+        tm = _items(times, n, np.uint64)
         dev = torch.device("cuda", self.device)
         keep = None
         if d_out is None:
@@ -1241,12 +1202,11 @@ class HelperEngine:
             d_out = keep.data_ptr()
         offs = np.zeros(n + 1, np.uint64)
         ln = ctypes.c_uint64()
-        u64p = ctypes.POINTER(ctypes.c_uint64)
         with self._ordered(stream):
-            st = self._L.jx_report_encode_device(self._h, n, d_report_ids, tm.ctypes.data_as(u64p), d_public_shares,
+            st = self._L.jx_report_encode_device(self._h, n, d_report_ids, _u64p(tm), d_public_shares,
                                                  d_leader_encs, leader_enc_len, d_leader_cts, d_helper_encs, helper_enc_len,
                                                  d_helper_cts, leader_config_id, helper_config_id, d_seal_status, d_out,
-                                                 capacity, None, offs.ctypes.data_as(u64p), ctypes.byref(ln))
+                                                 capacity, None, _u64p(offs), ctypes.byref(ln))
             check(st, self._h, "jx_report_encode_device")
         if keep is not None:
             bodies = keep[:ln.value]
@@ -1267,15 +1227,14 @@ class HelperEngine:
         if n and (lc.shape[1], hc.shape[1]) != self.client_seal_sizes():
             raise ValueError("ciphertext rows of client_seal_sizes() bytes")
         ps = _u8(public_shares, n, self.public_share_len, "public_shares")
-        tm = np.ascontiguousarray(np.asarray(times, dtype=np.uint64).reshape(n)) if n else np.zeros(1, np.uint64)
+        tm = _items(times, n, np.uint64)
         ss = None if seal_status is None else _u8(seal_status, n, 1, "seal_status")
         le_len, he_len = (le.shape[1], he.shape[1]) if n else (32, 32)
         cap = self.report_bound(n, le_len, he_len)
         out, offs, ln = np.zeros(max(cap, 1), np.uint8), np.zeros(n + 1, np.uint64), ctypes.c_uint64()
-        u64p = ctypes.POINTER(ctypes.c_uint64)
-        st = self._L.jx_report_encode(self._h, n, _ptr(ids), tm.ctypes.data_as(u64p), _ptr(ps) if self.public_share_len else None,
+        st = self._L.jx_report_encode(self._h, n, _ptr(ids), _u64p(tm), _ptr(ps) if self.public_share_len else None,
                                       _ptr(le), le_len, _ptr(lc), _ptr(he), he_len, _ptr(hc), leader_config_id,
-                                      helper_config_id, _ptr(ss), _ptr(out), cap, offs.ctypes.data_as(u64p), ctypes.byref(ln))
+                                      helper_config_id, _ptr(ss), _ptr(out), cap, _u64p(offs), ctypes.byref(ln))
         check(st, self._h, "jx_report_encode")
         return out[:ln.value].tobytes(), offs
 
@@ -1297,24 +1256,18 @@ class HelperEngine:
         ck = _lib.JxUploadChecks(now, tolerable_clock_skew, task_expiration is not None, task_expiration or 0,
                                  report_expiry_age is not None, report_expiry_age or 0)
         h = ctypes.c_void_p()
-        u64p = ctypes.POINTER(ctypes.c_uint64)
         if length is None:
             b = np.frombuffer(bytes(bodies) or b"\0", np.uint8)
-            st = self._L.jx_upload_decode(self._h, _ptr(b), len(bodies), n, off.ctypes.data_as(u64p), ctypes.byref(ck),
+            st = self._L.jx_upload_decode(self._h, _ptr(b), len(bodies), n, _u64p(off), ctypes.byref(ck),
                                           _ptr(kf), _ptr(ks), ctypes.byref(h))
             check(st, self._h, "jx_upload_decode")
         else:
             ptr = int(bodies.data_ptr()) if hasattr(bodies, "data_ptr") else int(bodies)
             with self._ordered(stream):
-                st = self._L.jx_upload_decode_device(self._h, ptr, length, n, off.ctypes.data_as(u64p), ctypes.byref(ck),
+                st = self._L.jx_upload_decode_device(self._h, ptr, length, n, _u64p(off), ctypes.byref(ck),
                                                      _ptr(kf), _ptr(ks), ctypes.byref(h))
                 check(st, self._h, "jx_upload_decode_device")
-        req = UploadReq(self, h)
-        with self._lock:
-            if not hasattr(self, "_init_reqs"):
-                self._init_reqs = weakref.WeakSet()
-            self._init_reqs.add(req)
-        return req
+        return self._track(UploadReq(self, h))
 
     # ------------------------------------------------------------------ aggregation state
     def aggregate_share(self, segment: int = 0) -> tuple[bytes, int, bytes]:
@@ -1368,9 +1321,7 @@ class HelperEngine:
         if idx.min() < 0 or idx.max() >= 2**32:
             raise ValueError("record indices are u32")
         idx = idx.astype(np.uint32)
-        ao = np.zeros(njobs + 1, np.uint64)
-        ao[1:] = np.cumsum([len(a) for a in aads], dtype=np.uint64)
-        aad = np.frombuffer(b"".join(aads) or b"\0", np.uint8).copy()
+        aad, ao = _packed(aads)
         ec = ecs = None
         if expect is not None:
             ec = np.ascontiguousarray(np.asarray([c for c, _ in expect] or [0], dtype=np.uint64))
@@ -1400,13 +1351,11 @@ class HelperEngine:
         out = CollectSeal(np.zeros(njobs, np.uint8), np.zeros(njobs, np.uint64), np.zeros((njobs, 32), np.uint8),
                           np.zeros((njobs, 32), np.uint8), np.zeros((njobs, pt + 16), np.uint8),
                           np.zeros((njobs, pt), np.uint8) if want_shares else None)
-        P64 = ctypes.POINTER(ctypes.c_uint64)
-        check(self._L.jx_collect_seal(self._h, njobs, _ptr(rec) if nrecords else None, nrecords, off.ctypes.data_as(P64),
-                                      idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-                                      None if ec is None else ec.ctypes.data_as(P64), _ptr(ecs), min_batch_size,
-                                      max_batch_size, _ptr(aad), ao.ctypes.data_as(P64), _ptr(sks), sender.handle,
-                                      _ptr(out.status), out.counts.ctypes.data_as(P64), _ptr(out.checksums),
-                                      _ptr(out.encs), _ptr(out.cts), _ptr(out.shares)),
+        check(self._L.jx_collect_seal(self._h, njobs, _ptr(rec) if nrecords else None, nrecords, _u64p(off),
+                                      idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _u64p(ec), _ptr(ecs),
+                                      min_batch_size, max_batch_size, _ptr(aad), _u64p(ao), _ptr(sks), sender.handle,
+                                      _ptr(out.status), _u64p(out.counts), _ptr(out.checksums), _ptr(out.encs),
+                                      _ptr(out.cts), _ptr(out.shares)),
               self._h, "jx_collect_seal")
         return out
 
@@ -1419,21 +1368,13 @@ class HelperEngine:
         against `stream` (module docstring)."""
         njobs = len(jobs)
         off, idx, ec, ecs, aad, ao = self._collect_jobs(jobs, nrecords, expect, aads, njobs)
-        P64 = ctypes.POINTER(ctypes.c_uint64)
         with self._ordered(stream):
-            check(self._L.jx_collect_seal_device(self._h, njobs, d_records, nrecords, off.ctypes.data_as(P64),
-                                                 idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-                                                 None if ec is None else ec.ctypes.data_as(P64), _ptr(ecs),
-                                                 min_batch_size, max_batch_size, _ptr(aad), ao.ctypes.data_as(P64),
+            check(self._L.jx_collect_seal_device(self._h, njobs, d_records, nrecords, _u64p(off),
+                                                 idx.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), _u64p(ec),
+                                                 _ptr(ecs), min_batch_size, max_batch_size, _ptr(aad), _u64p(ao),
                                                  d_ephemeral_sks, sender.handle, d_out_status, d_out_counts,
                                                  d_out_checksums, d_out_encs, d_out_cts, d_out_shares),
                   self._h, "jx_collect_seal_device")
-
-    @staticmethod
-    def _offsets(items) -> np.ndarray:
-        off = np.zeros(len(items) + 1, np.uint64)
-        off[1:] = np.cumsum([len(x) for x in items], dtype=np.uint64)
-        return off
 
     def collect_open(self, leader_opener, helper_opener, leader_shares, helper_shares, aads) -> CollectOpen:
         """The collector for n collections (jx_collect_open): open both encrypted aggregate shares of each and add them
@@ -1455,18 +1396,15 @@ class HelperEngine:
         if not keep:
             return out
         m = len(keep)
-        P64 = ctypes.POINTER(ctypes.c_uint64)
         arrs = []
         for sh in (leader_shares, helper_shares):
             encs = np.frombuffer(b"".join(sh[i][0] for i in keep), np.uint8).copy()
-            cts = np.frombuffer(b"".join(sh[i][1] for i in keep) or b"\0", np.uint8).copy()
-            arrs += [encs, cts, self._offsets([sh[i][1] for i in keep])]
-        aad = np.frombuffer(b"".join(aads[i] for i in keep) or b"\0", np.uint8).copy()
-        ao = self._offsets([aads[i] for i in keep])
+            arrs += [encs, *_packed([sh[i][1] for i in keep])]
+        aad, ao = _packed([aads[i] for i in keep])
         agg, st = np.zeros((m, pt), np.uint8), np.zeros(m, np.uint8)
         check(self._L.jx_collect_open(self._h, leader_opener.handle, helper_opener.handle, m, _ptr(arrs[0]), _ptr(arrs[1]),
-                                      arrs[2].ctypes.data_as(P64), _ptr(arrs[3]), _ptr(arrs[4]),
-                                      arrs[5].ctypes.data_as(P64), _ptr(aad), ao.ctypes.data_as(P64), _ptr(agg), _ptr(st)),
+                                      _u64p(arrs[2]), _ptr(arrs[3]), _ptr(arrs[4]),
+                                      _u64p(arrs[5]), _ptr(aad), _u64p(ao), _ptr(agg), _ptr(st)),
               self._h, "jx_collect_open")
         out.aggregates[keep] = agg
         out.status[keep] = st
@@ -1478,18 +1416,15 @@ class HelperEngine:
         """collect_open with the encapsulated keys (n x enc_len rows), the ciphertexts and both outputs in HBM
         (jx_collect_open_device); the ciphertext offsets [n + 1] and the aads stay on the host. Asynchronous, ordered
         against `stream` (module docstring)."""
-        P64 = ctypes.POINTER(ctypes.c_uint64)
-        lo = np.ascontiguousarray(np.asarray(leader_ct_offsets, dtype=np.uint64).reshape(n + 1))
-        ho = np.ascontiguousarray(np.asarray(helper_ct_offsets, dtype=np.uint64).reshape(n + 1))
+        lo = _offs(leader_ct_offsets, n)
+        ho = _offs(helper_ct_offsets, n)
         if len(aads) != n:
             raise ValueError("one aad per collection")
-        aad = np.frombuffer(b"".join(aads) or b"\0", np.uint8).copy()
-        ao = self._offsets(aads)
+        aad, ao = _packed(aads)
         with self._ordered(stream):
             check(self._L.jx_collect_open_device(self._h, leader_opener.handle, helper_opener.handle, n, d_leader_encs,
-                                                 d_leader_cts, lo.ctypes.data_as(P64), d_helper_encs, d_helper_cts,
-                                                 ho.ctypes.data_as(P64), _ptr(aad), ao.ctypes.data_as(P64),
-                                                 d_out_aggregates, d_out_status),
+                                                 d_leader_cts, _u64p(lo), d_helper_encs, d_helper_cts, _u64p(ho),
+                                                 _ptr(aad), _u64p(ao), d_out_aggregates, d_out_status),
                   self._h, "jx_collect_open_device")
 
     def set_capacity(self, reports: int):

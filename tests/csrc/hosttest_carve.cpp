@@ -26,11 +26,13 @@ struct Regions {
   uint16_t* d = nullptr;
 };
 static const size_t kSizes[5] = {1, 4 * 77, 8 * 1000, 0, 2 * 128};  // odd, below and above 256, empty, exactly 256
-static size_t lay(Regions& r, void* base) {
+// prefix (optional): the layout marks the first three regions as a handle's host-visible prefix (Carver::mark)
+static size_t lay(Regions& r, void* base, size_t* prefix = nullptr) {
   Carver cv(base);
   cv.take(r.a, kSizes[0]);
   cv.take(r.b, kSizes[1]);
   cv.take(r.c, kSizes[2]);
+  if (prefix) *prefix = cv.mark() == cv.bytes() ? cv.marked() : 0;  // the running total where it is taken
   cv.take(r.empty, kSizes[3]);
   cv.take(r.d, kSizes[4]);
   return cv.bytes();
@@ -108,6 +110,23 @@ int main() {
     check(outs - mem.data() == 0 && ver - mem.data() == 3072 && msg - mem.data() == 3328 && non - mem.data() == 5376,
           "a batch of 64 reports: offsets 0 / 3072 / 3328 / 5376");
     check(sized_total == 6400 && carved_total == 6400, "a batch of 64 reports: 6400 bytes, sized or carved");
+  }
+
+  // ---- a handle's layout: the regions up to the mark are the prefix its pinned host copy holds, and a pointer into
+  // the device slab is the same offset of the copy (same_offset)
+  {
+    Regions h;
+    size_t sized_prefix = 0, prefix = 0;
+    const size_t sized_total = lay(h, nullptr, &sized_prefix), carved_total = lay(h, base, &prefix);
+    check(sized_prefix == 256 + 512 + 8192 && prefix == sized_prefix,
+          "the mark is the running total where it is taken, sized or carved");
+    check(sized_total == total && carved_total == total, "a layout with a mark has the total of the layout without");
+    const std::vector<uint8_t> copy(base, base + prefix);
+    const uint8_t* first = same_offset(h.a, base, copy.data());
+    const uint64_t* last = same_offset(h.c, base, copy.data());
+    check(first == copy.data() && (const uint8_t*)last == copy.data() + 768 && first[0] == 1 && last[999] == 3 &&
+              (const uint8_t*)(last + 1000) <= copy.data() + prefix,
+          "the prefix's first and last region lie at the same offsets of its copy");
   }
 
   if (g_failed) {

@@ -8,7 +8,7 @@ import os
 import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-CHECKS = 14
+CHECKS = 17
 
 
 def test_carve_under_sanitizers():
