@@ -783,6 +783,7 @@ int32_t jx_engine_debug(jx_engine* e, int32_t option, int64_t value) {
     return JX_OK;
   }
   if (option == 2) {  // accumulate chunking (tests); staging is sized per call
+    // first user: tests/test_gpu_accumulate_edges.py (block splits of accumulate_kernel, work-item lengths of seg_*)
     if (value < 1 || value > 4096) return JX_E_INVALID;
     e->acc_chunks = (uint32_t)value;
     return JX_OK;
