@@ -544,6 +544,34 @@ int32_t jx_init_req_arrays(const jx_init_req* r, jx_init_req_arrays_t* out);
 /* Route the reports with exclude[i] != 0 (a host array of n) away from every aggregation: route[i] = 0xFFFFFFFF. For
  * reports the caller knows before the prepare call that it will not accept, such as replayed ones. */
 int32_t jx_init_req_exclude(jx_init_req* r, const uint8_t* exclude);
+/* Route the reports of a time-interval request to their batch buckets on the device, as the reference's aggregation
+ * job writer indexes them (aggregation_job_writer.rs:557-605, :608-708). A report's bucket starts at its time rounded
+ * down to time_precision (> 0; exact for every u64). The table that comes back holds the distinct bucket starts over
+ * all n reports, ascending, at most JX_ROUTE_MAX_BUCKETS of them: min_time, max_time and reports cover every report of
+ * the bucket, the excluded and failed ones too (the writer widens the batch's client-timestamp interval with all of
+ * them); routed counts the reports this call routes to the bucket; collected is 1 when the start is among
+ * collected_starts (a host array in any order, repeats allowed; a start that is no bucket of the request matches
+ * nothing). Per report, route[i] becomes its bucket's index in the table when it was 0 and the bucket is not
+ * collected, and 0xFFFFFFFF otherwise: pass it as d_segment with segment_ids[k] the aggregation of bucket k. The
+ * response encode answers the otherwise finished reports of a collected bucket with BatchCollected (code point 0),
+ * which ranks below ReportReplayed. jx_init_req_exclude may still follow: it routes out as before, and the table's
+ * `routed` counts, which are this call's, are not updated by it. The call waits for its table.
+ * JX_E_INVALID: time_precision 0, or a request with a batch id (FixedSize: its one batch needs no route). JX_E_STATE: a
+ * refused request, or a handle that is routed already. *out_status JX_ROUTE_TOO_MANY_BUCKETS: more than
+ * JX_ROUTE_MAX_BUCKETS distinct buckets; route and the handle are as they were, and it may be routed again. */
+#define JX_ROUTE_MAX_BUCKETS 1024
+#define JX_ROUTE_OK 0
+#define JX_ROUTE_TOO_MANY_BUCKETS 1
+typedef struct jx_route_bucket {
+  uint64_t start, min_time, max_time;
+  uint32_t reports, routed, collected, pad_;
+} jx_route_bucket;
+int32_t jx_init_req_route(jx_engine* e, jx_init_req* r, uint64_t time_precision, const uint64_t* collected_starts,
+                          uint64_t ncollected, uint32_t* out_status, uint32_t* out_nbuckets,
+                          jx_route_bucket* out_buckets /* [JX_ROUTE_MAX_BUCKETS] */);
+/* A routed handle's per-report device arrays: bucket_index u32[n], bucket_collected u8[n] (either pointer nullable).
+ * JX_E_STATE unless the handle is routed. */
+int32_t jx_init_req_route_arrays(const jx_init_req* r, const void** d_bucket_index, const void** d_bucket_collected);
 /* The AggregationJobResp body of the request: per report, by the helper loop's precedence (aggregator.rs:1781-2013,
  * :2127-2132): host_errors[i] (a PrepareError code point, JX_WIRE_NO_ERROR: none) for reports the host resolved; the
  * open status (1: HpkeDecryptError, 2-6: InvalidMessage, 7: HpkeUnknownConfigId); a time after the decode's deadline:

@@ -29,6 +29,7 @@ EXPORTED_SYMBOLS = (
     "jx_client_shard_batch", "jx_client_shard_device", "jx_client_rand_bytes",
     "jx_client_seal_sizes", "jx_client_seal_batch", "jx_client_seal_device",
     "jx_init_req_decode", "jx_init_req_decode_device", "jx_init_req_info", "jx_init_req_arrays", "jx_init_req_exclude",
+    "jx_init_req_route", "jx_init_req_route_arrays",
     "jx_init_resp_encode_device", "jx_init_resp_encode", "jx_init_req_release",
     "jx_init_req_encode_bound", "jx_init_req_encode_device", "jx_init_req_encode", "jx_leader_req_info",
     "jx_leader_req_sent", "jx_init_resp_decode", "jx_leader_req_release",
@@ -187,6 +188,8 @@ def load():
         "jx_init_req_info": (i32, [vp, P(JxInitReqInfo)]),
         "jx_init_req_arrays": (i32, [vp, P(JxInitReqArrays)]),
         "jx_init_req_exclude": (i32, [vp, u8p]),
+        "jx_init_req_route": (i32, [vp, vp, u64, P(u64), u64, P(u32), P(u32), vp]),
+        "jx_init_req_route_arrays": (i32, [vp, P(vp), P(vp)]),
         "jx_init_resp_encode_device": (i32, [vp, vp, vp, vp, vp, u64, u8p, u8p, vp, u64, P(u64), vp]),
         "jx_init_resp_encode": (i32, [vp, vp, vp, vp, vp, u64, u8p, u8p, u8p, u64, P(u64), u8p]),
         "jx_init_req_release": (None, [vp]),

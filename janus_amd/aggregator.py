@@ -802,6 +802,152 @@ def handle_aggregate_init_wire(engine: HelperEngine, body: bytes, task_id: bytes
     return out, finished, failures
 
 
+class TooManyBuckets(ValueError):
+    """The request's reports fall into more batch buckets than the device route holds (engine.ROUTE_MAX_BUCKETS):
+    nothing was queued, and the request is served by the object path (handle_aggregate_init with segments=)."""
+
+
+def _wire_key_tables(opener, hpke_config_id: int, globals_: dict):
+    """(keypairs, key_first, key_second) as decode_init_req and the sealed calls take them: per config id the task's
+    keypair first and the global one second, each distinct keypair in one slot."""
+    from .engine import KEY_NONE
+
+    keypairs = [opener]
+    slot = {id(opener): 0}
+
+    def key_slot(k) -> int:
+        if id(k) not in slot:
+            slot[id(k)] = len(keypairs)
+            keypairs.append(k)
+        return slot[id(k)]
+
+    key_first, key_second = np.full(256, KEY_NONE, np.uint8), np.full(256, KEY_NONE, np.uint8)
+    for cfg in range(256):
+        task_k = opener if cfg == hpke_config_id else None
+        glob_k = globals_.get(cfg)
+        first, second = (task_k, glob_k) if task_k is not None else (glob_k, None)
+        if first is not None:
+            key_first[cfg] = key_slot(first)
+            if second is not None:
+                key_second[cfg] = key_slot(second)
+    if len(keypairs) > 8:
+        raise ValueError("more than JX_ENC_MAX_KEYPAIRS distinct keypairs for one task")
+    return keypairs, key_first, key_second
+
+
+def _wire_accept(req) -> int:
+    """The request-level refusals of a decoded request (aggregator.rs:1740-1758, :2017-2028); its report count."""
+    from .engine import WIRE_DUPLICATE_ID, WIRE_OK, WIRE_WRONG_QUERY_TYPE
+
+    if req.status == WIRE_DUPLICATE_ID:
+        raise ValueError(f"aggregate request contains duplicate report IDs (invalidMessage): report {req.duplicate_index}")
+    if req.status != WIRE_OK:
+        what = "unexpected query type" if req.status == WIRE_WRONG_QUERY_TYPE else "malformed"
+        raise CodecError(f"AggregationJobInitializeReq: {what} at byte {req.error_offset}")
+    if req.n == 0:
+        raise EmptyAggregation("aggregation job request holds no report")
+    return req.n
+
+
+def _wire_host_errors(req, body: bytes, opener, hpke_config_id: int, globals_: dict, task_id: bytes, v,
+                      require_taskprov: bool, failures: Counter):
+    """host_errors for the reports the rows cannot carry (a public share of another length): the reference's checks on
+    the host, from the body's bytes. None when there is no such report."""
+    from .engine import WIRE_NO_ERROR, WIRE_REPORT_ODD_PUBLIC_SHARE
+
+    odd = np.nonzero(req.wire_status == WIRE_REPORT_ODD_PUBLIC_SHARE)[0]
+    if not odd.size:
+        return None
+    host_err = np.full(req.n, WIRE_NO_ERROR, np.uint8)
+    for i in odd:
+        rec = req.records[i]
+        pi = PrepareInit.decode(body[int(rec["off"]):int(rec["off"]) + int(rec["len"])])
+        host_err[i] = int(_open_alone(pi, opener, hpke_config_id, globals_, task_id, v, require_taskprov, failures))
+    return host_err
+
+
+def _wire_replayed_mask(req, replayed):
+    """replayed (a set of report ids, or a mask of n) as a mask of n; None when there is none."""
+    if replayed is not None and not isinstance(replayed, (set, frozenset)):
+        return np.asarray(replayed).astype(bool).reshape(req.n)
+    if replayed:
+        return np.fromiter((r.tobytes() in replayed for r in req.report_ids), bool, req.n)
+    return None
+
+
+def _wire_count_failures(failures: Counter, req, st, vd, report_deadline) -> None:
+    """janus_step_failures from the open statuses and verdicts, by the handler's precedence, whole arrays at a time."""
+    from .engine import OPEN_STATUS, WIRE_REPORT_NOT_INITIALIZE, WIRE_REPORT_ODD_PREP_SHARE, WIRE_REPORT_ODD_PUBLIC_SHARE
+
+    ws = req.wire_status
+    live = ws != WIRE_REPORT_ODD_PUBLIC_SHARE
+    for code, cnt in enumerate(np.bincount(st[live & (st != 0)], minlength=8)):
+        if cnt:
+            failures[OPEN_STATUS[code][0]] += int(cnt)
+    rest = live & (st == 0)
+    if report_deadline is not None:
+        rest &= req.times <= np.uint64(report_deadline)
+    for code, label in ((WIRE_REPORT_NOT_INITIALIZE, "leader_ping_pong_message_mismatch"),
+                        (WIRE_REPORT_ODD_PREP_SHARE, "leader_prep_share_decode_failure")):
+        cnt = int((rest & (ws == code)).sum())
+        if cnt:
+            failures[label] += cnt
+    for code, cnt in enumerate(np.bincount(vd[rest & (ws == 0) & (vd != FINISHED)], minlength=1)):
+        if cnt:
+            failures[VERDICT_LABELS[code]] += int(cnt)
+
+
+def handle_aggregate_init_wire_buckets(engine: HelperEngine, body: bytes, task_id: bytes, opener, hpke_config_id: int,
+                                       time_precision: int, segment_of, collected=(), global_keypairs=None,
+                                       require_taskprov: bool = False, report_deadline: int | None = None, replayed=None):
+    """handle_aggregate_init_wire for a time-interval task whose request spans batches: between the decode and the
+    sealed fused call the reports are routed to their batch buckets on the GPU (InitReq.route: the report time rounded
+    down to time_precision, as aggregation_job_writer.rs:557-605 indexes them), so that one call accumulates every
+    bucket's aggregation. segment_of maps a bucket start to the deployment's u32 aggregation id; collected: the starts
+    of the batches that no longer accept aggregations, whose otherwise finished reports are answered with
+    BatchCollected and reach no aggregation (:608-708). The other arguments and the errors raised are
+    handle_aggregate_init_wire's; a request of more than ROUTE_MAX_BUCKETS buckets raises TooManyBuckets before
+    anything is queued. Returns (response body, finished mask, janus_step_failures counter, bucket table): the table
+    is a ROUTE_BUCKET array whose min_time / max_time / reports cover every report of the request, as the writer
+    widens each batch's client-timestamp interval."""
+    import torch
+
+    from .engine import ROUTE_MAX_BUCKETS, ROUTE_OK
+    from .messages import QUERY_TIME_INTERVAL
+
+    globals_ = dict(global_keypairs or {})
+    keypairs, key_first, key_second = _wire_key_tables(opener, hpke_config_id, globals_)
+    failures: Counter = Counter()
+    with engine.decode_init_req(body, QUERY_TIME_INTERVAL, key_first, key_second, report_deadline) as req:
+        n = _wire_accept(req)
+        host_err = _wire_host_errors(req, body, opener, hpke_config_id, globals_, task_id, engine.vdaf, require_taskprov,
+                                     failures)
+        rep = _wire_replayed_mask(req, replayed)
+        if rep is not None and rep.any():
+            req.exclude(rep)
+        status, buckets = req.route(time_precision, collected)
+        if status != ROUTE_OK:
+            raise TooManyBuckets(f"aggregation job request spans more than {ROUTE_MAX_BUCKETS} batch buckets")
+        S = engine.prep_msg_len
+        dev = torch.device("cuda", engine.device)
+        with torch.cuda.device(dev):
+            d_v = torch.zeros(n, dtype=torch.uint8, device=dev)
+            d_st = torch.zeros(n, dtype=torch.uint8, device=dev)
+            d_m = torch.zeros((n, max(S, 1)), dtype=torch.uint8, device=dev)
+            a = req.d
+            engine.prep_and_aggregate_encrypted_device(
+                a.d_report_ids, req.times, a.d_public_shares, task_id, keypairs, req.key_index, a.d_encs, a.d_payloads,
+                req.payload_offsets, a.d_leader_prep_shares, n, enc_offsets=req.enc_offsets,
+                require_taskprov=require_taskprov, d_out_prep_msgs=d_m.data_ptr() if S else None,
+                d_out_verdicts=d_v.data_ptr(), d_out_open_status=d_st.data_ptr(), d_segments=a.d_route,
+                segment_ids=[int(segment_of(int(b["start"]))) for b in buckets])
+            out, finished = engine.encode_init_resp(req, d_v.data_ptr(), d_st.data_ptr(), d_m.data_ptr() if S else None,
+                                                    host_err, rep, prep_msg_stride=max(S, 1) if S else 0)
+            st, vd = d_st.cpu().numpy(), d_v.cpu().numpy()
+        _wire_count_failures(failures, req, st, vd, report_deadline)
+    return out, finished, failures, buckets
+
+
 # ----------------------------------------------------------------------------- upload (leader)
 
 

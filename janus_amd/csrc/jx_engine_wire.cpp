@@ -6,6 +6,7 @@
 // The leader's end of the same exchange: jx_init_req_encode* writes the request body from the arrays the leader holds
 // (one round trip: the body's length is a result), and jx_init_resp_decode walks the response on the host, matches it
 // against the ids the request sent, and queues one upload and one kernel that fill the rows the leader's finish reads.
+#include <algorithm>
 #include <cstring>
 #include <new>
 #include <random>
@@ -22,6 +23,8 @@ static_assert(sizeof(jx_wire_record) == sizeof(WireRec), "jx_wire_record is Wire
 static_assert(JX_WIRE_MALFORMED == WIRE_MALFORMED && JX_WIRE_WRONG_QUERY_TYPE == WIRE_WRONG_QUERY_TYPE &&
                   JX_WIRE_DUPLICATE_ID == WIRE_DUPLICATE_ID && JX_WIRE_NO_ERROR == WIRE_ERR_NONE,
               "the header's code points are the rule's");
+static_assert(sizeof(jx_route_bucket) == sizeof(WireBucket) && JX_ROUTE_MAX_BUCKETS == WIRE_ROUTE_MAX_BUCKETS,
+              "jx_route_bucket is WireBucket");
 static_assert(JX_RESP_CONTINUED == RESP_CONTINUED && JX_RESP_REJECTED == RESP_REJECTED && JX_RESP_FINISHED == RESP_FINISHED &&
                   JX_RESP_MESSAGE_MISMATCH == RESP_MESSAGE_MISMATCH && JX_QUERY_FIXED_SIZE == WIRE_QUERY_FIXED_SIZE,
               "the response's results are the rule's");
@@ -32,6 +35,8 @@ struct jx_init_req {
   jx_init_req_arrays_t arr{};
   Mirror arrays;  // times .. wire_status with their pinned copy, then route and the two rows arrays
   Slab packed;    // the encapsulated keys and the payloads, packed
+  Slab buckets;   // a routed request's bucket_index and bucket_collected
+  bool routed = false;
   bool has_deadline = false;
   uint64_t deadline = 0;
   uint64_t n = 0;
@@ -40,7 +45,8 @@ struct jx_init_req {
   WireRec* recs = nullptr;
   uint8_t *ids = nullptr, *key_index = nullptr, *wire_status = nullptr, *ps = nullptr, *lps = nullptr, *encs = nullptr,
           *payloads = nullptr;
-  uint32_t* route = nullptr;
+  uint32_t *route = nullptr, *bucket_index = nullptr;
+  uint8_t* bucket_collected = nullptr;
 };
 
 // The leader's encoded request: which reports it sent, in order, for the response to be matched against.
@@ -62,6 +68,7 @@ void req_free(jx_init_req* r) {
   jx_engine* e = r->e;
   r->arrays.put(e);
   if (r->packed.p) arena_put(e->arena, r->packed, e->stream);
+  if (r->buckets.p) arena_put(e->arena, r->buckets, e->stream);
   r->arrays.free(e);
   delete r;
 }
@@ -296,6 +303,7 @@ int32_t encode_core(jx_engine* e, jx_init_req* r, const void* d_verdicts, const 
   a.prep_msgs = (const uint8_t*)d_prep_msgs;
   a.host_err = n && host_errors ? d_herr : nullptr;
   a.replayed = n && replayed ? d_rep : nullptr;
+  a.bucket_collected = n && r->routed ? r->bucket_collected : nullptr;
   a.prep_msg_bytes = S;
   a.prep_msg_stride = (uint32_t)prep_msg_stride;
   a.has_deadline = r->has_deadline;
@@ -514,6 +522,98 @@ int32_t jx_init_req_exclude(jx_init_req* r, const uint8_t* exclude) {
   HIPCHK(e, hipMemcpyAsync(mem.p(), exclude, r->n, hipMemcpyHostToDevice, e->stream));
   HIPCHK(e, launch_wire_exclude(r->route, mem.p(), r->n, e->stream));
   HIPCHK(e, hipStreamSynchronize(e->stream));  // the caller's mask has been read
+  return JX_OK;
+}
+
+int32_t jx_init_req_route(jx_engine* e, jx_init_req* r, uint64_t time_precision, const uint64_t* collected_starts,
+                          uint64_t ncollected, uint32_t* out_status, uint32_t* out_nbuckets, jx_route_bucket* out_buckets) {
+  if (!e || !r || r->e != e || !out_status || !out_nbuckets || !out_buckets || (ncollected && !collected_starts))
+    return JX_E_INVALID;
+  LOCK(e);
+  if (time_precision == 0) return fail(e, JX_E_INVALID, "init req route: the time precision must not be 0");
+  if (r->info.status != WIRE_OK) return fail(e, JX_E_STATE, "init req route: the request was refused; it routes nothing");
+  if (r->info.has_batch_id) return fail(e, JX_E_INVALID, "init req route: a FixedSize request has one batch, its batch id's");
+  if (r->routed) return fail(e, JX_E_STATE, "init req route: the request is routed already");
+  *out_status = JX_ROUTE_OK;
+  *out_nbuckets = 0;
+  const uint64_t n = r->n;
+  if (n == 0) {
+    r->routed = true;
+    return JX_OK;
+  }
+  HIPCHK(e, hipSetDevice(e->device));
+  std::vector<uint64_t> collected(collected_starts, collected_starts + ncollected);
+  std::sort(collected.begin(), collected.end());
+  collected.erase(std::unique(collected.begin(), collected.end()), collected.end());
+  WireRouteArgs a{};
+  a.n = n;
+  a.times = r->times;
+  a.precision = time_precision;
+  a.ncollected = collected.size();
+  a.slots = 2 * n;
+  a.k0 = e->wire_key[0];
+  a.k1 = e->wire_key[1];
+  a.route = r->route;
+  uint64_t* d_collected = nullptr;
+  size_t zeroed = 0;
+  auto lay = [&](void* base) {
+    Carver cv(base);
+    cv.take(a.st, sizeof(WireRouteState));
+    cv.take(a.tab, a.slots * 4);
+    zeroed = cv.bytes();  // up to here: one memset
+    cv.take(a.buckets, sizeof(WireBucket) * WIRE_ROUTE_MAX_BUCKETS);
+    cv.take(a.list, 4 * WIRE_ROUTE_MAX_BUCKETS);
+    cv.take(a.rank, n * 4);
+    cv.take(d_collected, a.ncollected * 8);
+    return cv.bytes();
+  };
+  Scratch mem;  // the call holds nothing else yet: it may wait for the arena
+  if (const int32_t rc = scratch_carve(e, mem, lay, true)) return rc;
+  Slab out;
+  auto layb = [&](void* base) {
+    Carver cv(base);
+    cv.take(a.bucket_index, n * 4);
+    cv.take(a.bucket_collected, n);
+    return cv.bytes();
+  };
+  if (const int32_t rc = slab_carve(e, out, layb, "init req buckets")) return rc;
+  struct PutBack {  // the per-report arrays go back unless the handle takes them
+    jx_engine* e;
+    Slab* s;
+    ~PutBack() {
+      if (s) arena_put(e->arena, *s, e->stream);
+    }
+  } back{e, &out};
+  a.collected = d_collected;
+  HIPCHK(e, hipMemsetAsync(a.st, 0, zeroed, e->stream));
+  if (a.ncollected)
+    HIPCHK(e, hipMemcpyAsync(d_collected, collected.data(), a.ncollected * 8, hipMemcpyHostToDevice, e->stream));
+  HIPCHK(e, launch_wire_route(a, e->stream));
+  WireRouteState st{};
+  std::vector<WireBucket> table(WIRE_ROUTE_MAX_BUCKETS);
+  HIPCHK(e, hipMemcpyAsync(&st, a.st, sizeof st, hipMemcpyDeviceToHost, e->stream));
+  HIPCHK(e, hipMemcpyAsync(table.data(), a.buckets, sizeof(WireBucket) * WIRE_ROUTE_MAX_BUCKETS, hipMemcpyDeviceToHost,
+                           e->stream));
+  HIPCHK(e, hipStreamSynchronize(e->stream));
+  if (st.claims > WIRE_ROUTE_MAX_BUCKETS) {
+    *out_status = JX_ROUTE_TOO_MANY_BUCKETS;
+    return JX_OK;
+  }
+  memcpy(out_buckets, table.data(), sizeof(WireBucket) * st.claims);
+  *out_nbuckets = st.claims;
+  back.s = nullptr;
+  r->buckets = out;
+  r->bucket_index = a.bucket_index;
+  r->bucket_collected = a.bucket_collected;
+  r->routed = true;
+  return JX_OK;
+}
+
+int32_t jx_init_req_route_arrays(const jx_init_req* r, const void** d_bucket_index, const void** d_bucket_collected) {
+  if (!r) return JX_E_INVALID;
+  if (!r->routed) return JX_E_STATE;
+  if (d_bucket_index) *d_bucket_index = r->bucket_index;
+  if (d_bucket_collected) *d_bucket_collected = r->bucket_collected;
   return JX_OK;
 }
 

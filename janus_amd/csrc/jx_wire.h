@@ -257,6 +257,89 @@ JX_HD uint64_t wire_id_hash(const uint8_t id[16], uint64_t k0, uint64_t k1) {
   return v0 ^ v1 ^ v2 ^ v3;
 }
 
+// ---- the batch buckets of a time-interval task (aggregation_job_writer.rs:557-605, :608-708): a report belongs to the
+// batch whose identifier is its time rounded down to the task's time_precision (Time::to_batch_interval_start).
+// precision > 0; exact for every u64: the remainder is never more than the time.
+JX_HD uint64_t wire_bucket_start(uint64_t time, uint64_t precision) { return time - time % precision; }
+
+// is `start` one of the m collected starts, which ascend?
+JX_HD bool wire_bucket_collected(const uint64_t* collected, uint64_t m, uint64_t start) {
+  uint64_t lo = 0, hi = m;
+  while (lo < hi) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (collected[mid] < start) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < m && collected[lo] == start;
+}
+
+// wire_outcome for a routed request. The writer fails what is left of a batch that no longer accepts aggregations:
+// BatchCollected ranks below every other error, ReportReplayed included, since the reference marks replays before the
+// writer runs and the writer skips report aggregations that have already failed.
+constexpr uint8_t WIRE_ERR_BATCH_COLLECTED = 0;
+JX_HD uint8_t wire_outcome_routed(uint8_t host_err, uint8_t open, bool too_early, uint8_t wire, uint8_t verdict,
+                                  bool replayed, bool collected) {
+  const uint8_t err = wire_outcome(host_err, open, too_early, wire, verdict, replayed);
+  return err == WIRE_ERR_NONE && collected ? WIRE_ERR_BATCH_COLLECTED : err;
+}
+
+// One bucket of a request (jx_route_bucket). min_time / max_time / reports: over every report of the bucket, excluded
+// and failed ones included (the writer widens the batch's client-timestamp interval with all of them).
+struct WireBucket {
+  uint64_t start, min_time, max_time;
+  uint32_t reports, routed, collected, pad_;
+};
+static_assert(sizeof(WireBucket) == 40, "WireBucket is copied to the host as bytes");
+constexpr uint32_t WIRE_ROUTE_MAX_BUCKETS = 1024;
+constexpr uint32_t WIRE_ROUTE_OUT = 0xFFFFFFFFu;
+
+// The distinct buckets are found as the duplicate ids are: tab holds `slots` zeroed words, a slot holds claimant
+// index + 1, and a report walks its bucket's probe chain from the keyed hash of the start. An empty slot is claimed
+// (cas(&slot, value): a compare-exchange with 0 that returns what the slot held); an occupied one names its holder,
+// whose bucket is recomputed from times, the pass's input, never from anything the pass writes. True: report i
+// claimed its bucket's slot, as exactly one report of every bucket does, whichever comes first.
+JX_HD uint64_t wire_bucket_slot(uint64_t start, uint64_t k0, uint64_t k1, uint64_t slots) {
+  uint8_t id[16] = {0};
+  for (int k = 0; k < 8; k++) id[k] = (uint8_t)(start >> (8 * k));
+  return wire_id_hash(id, k0, k1) % slots;
+}
+template <class Cas>
+JX_HD bool wire_route_claim(uint64_t i, const uint64_t* times, uint64_t precision, uint32_t* tab, uint64_t slots,
+                            uint64_t k0, uint64_t k1, Cas cas) {
+  const uint64_t b = wire_bucket_start(times[i], precision);
+  uint64_t s = wire_bucket_slot(b, k0, k1, slots);
+  for (uint64_t probes = 0; probes < slots; probes++) {
+    const uint32_t seen = cas(&tab[s], (uint32_t)i + 1u);
+    if (seen == 0) return true;
+    if (wire_bucket_start(times[seen - 1u], precision) == b) return false;
+    s = s + 1 == slots ? 0 : s + 1;
+  }
+  return false;  // not reached: fewer claimants than slots
+}
+// the claimant of start's slot once every claim is made (WIRE_ROUTE_OUT: none, which no bucket of the request gives)
+JX_HD uint32_t wire_route_holder(uint64_t start, const uint64_t* times, uint64_t precision, const uint32_t* tab,
+                                 uint64_t slots, uint64_t k0, uint64_t k1) {
+  uint64_t s = wire_bucket_slot(start, k0, k1, slots);
+  for (uint64_t probes = 0; probes < slots; probes++) {
+    const uint32_t seen = tab[s];
+    if (seen == 0) break;
+    if (wire_bucket_start(times[seen - 1u], precision) == start) return seen - 1u;
+    s = s + 1 == slots ? 0 : s + 1;
+  }
+  return WIRE_ROUTE_OUT;
+}
+// the place of keys[k] among m distinct keys in ascending order
+JX_HD uint32_t wire_rank(const uint64_t* keys, uint32_t m, uint32_t k) {
+  const uint64_t mine = keys[k];
+  uint32_t r = 0;
+  for (uint32_t j = 0; j < m; j++) r += keys[j] < mine;
+  return r;
+}
+// route[i] after the route: the bucket's index for a report that was routed in and whose bucket is open
+JX_HD uint32_t wire_route_of(uint32_t before, bool collected, uint32_t bucket) {
+  return before == 0 && !collected ? bucket : WIRE_ROUTE_OUT;
+}
+
 // The whole index as the kernels compute it, one loop iteration per lane: the fast pass over every candidate at
 // start + i * l0 (the kernel takes the minimum of the failing i with one atomic), then the fallback loop. iters: the
 // fallback's iterations (0 for a uniform body).
@@ -566,12 +649,34 @@ struct WireEncodeArgs {
   const uint64_t* times;
   const uint8_t *wire_status, *verdicts, *open_status, *prep_msgs;
   const uint8_t *host_err, *replayed;  // nullable
+  const uint8_t* bucket_collected;     // a routed request's (null: the request is not routed)
   uint32_t prep_msg_bytes, prep_msg_stride;
   uint32_t has_deadline;
   uint64_t deadline;
   uint8_t *err, *finished;  // [n]
   uint64_t* offsets;        // [n + 1]: PrepareResp i at 4 + offsets[i] of out
   uint8_t* out;
+};
+
+// The route. st->claims counts the buckets claimed; past WIRE_ROUTE_MAX_BUCKETS the request has too many, and the
+// kernels behind the claims write nothing.
+struct WireRouteState {
+  uint32_t claims, pad_;
+};
+struct WireRouteArgs {
+  uint64_t n;
+  const uint64_t* times;
+  uint64_t precision;
+  const uint64_t* collected;  // ascending, distinct
+  uint64_t ncollected;
+  uint32_t* tab;              // [slots], zeroed
+  uint64_t slots, k0, k1;
+  WireRouteState* st;         // zeroed
+  uint32_t* list;             // [WIRE_ROUTE_MAX_BUCKETS]: the claimants, in the order they drew their places
+  uint32_t* rank;             // [n]: rank[c] of a claimant c is its bucket's index
+  WireBucket* buckets;        // [WIRE_ROUTE_MAX_BUCKETS]
+  uint32_t *route, *bucket_index;
+  uint8_t* bucket_collected;
 };
 
 // The leader's request encode. The host arrays of the call (times .. exclude) are device copies here.
@@ -626,6 +731,8 @@ hipError_t launch_wire_records(const WireDecodeArgs& a, uint32_t* dup_tab, uint6
                                uint64_t k1, hipStream_t s);
 hipError_t launch_wire_gather(const WireDecodeArgs& a, hipStream_t s);
 hipError_t launch_wire_exclude(uint32_t* route, const uint8_t* mask, uint64_t n, hipStream_t s);
+// the claims, the sort of the claimed buckets, and the pass that routes every report and counts its bucket (n > 0)
+hipError_t launch_wire_route(const WireRouteArgs& a, hipStream_t s);
 hipError_t launch_wire_encode_sizes(const WireEncodeArgs& a, hipStream_t s);
 hipError_t launch_wire_encode_pack(const WireEncodeArgs& a, hipStream_t s);
 #endif

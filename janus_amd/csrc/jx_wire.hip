@@ -184,13 +184,109 @@ __global__ __launch_bounds__(256) void wire_exclude_kernel(uint32_t* route, cons
   if (i < n && mask[i]) route[i] = 0xFFFFFFFFu;
 }
 
+// ---- the route: every report to its batch bucket (the rule: wire_bucket_start .. wire_route_of in jx_wire.h).
+// Three launches. The claims find the distinct buckets in the hash table and give each a place in a list of at most
+// WIRE_ROUTE_MAX_BUCKETS. One workgroup ranks the list's starts in LDS and writes the table's entries, empty. The last
+// pass looks every report's bucket up again, writes its three per-report values and counts it in its entry. The
+// reports of a request mostly arrive in time order, so the lanes of a wave mostly share a bucket: the wave's lanes are
+// taken a group of equal starts at a time, and one lane of a group claims, looks up and issues the atomics for it.
+
+// f(lead, in) for every group of active lanes with equal keys: lead is the group's lowest lane, `in` says whether
+// this lane belongs to it. All 64 lanes run f, so f may use cross-lane operations.
+template <class F>
+__device__ void wave_groups(bool active, uint64_t key, F f) {
+  unsigned long long todo = __ballot(active);
+  while (todo) {
+    const int lead = __ffsll((long long)todo) - 1;
+    const bool in = active && key == __shfl((unsigned long long)key, lead);
+    f(lead, in);
+    todo &= ~__ballot(in);  // the lead is in its group: the loop ends
+  }
+}
+
+__global__ __launch_bounds__(256) void wire_route_claim_kernel(WireRouteArgs a) {
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool active = i < a.n;
+  const uint64_t b = active ? wire_bucket_start(a.times[i], a.precision) : 0;
+  bool leads = false;
+  wave_groups(active, b, [&](int lead, bool) { leads |= lane == lead; });
+  if (!leads) return;
+  auto cas = [](uint32_t* slot, uint32_t v) {
+    uint32_t seen = 0;
+    __hip_atomic_compare_exchange_strong(slot, &seen, v, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return seen;
+  };
+  if (!wire_route_claim(i, a.times, a.precision, a.tab, a.slots, a.k0, a.k1, cas)) return;
+  const uint32_t at = __hip_atomic_fetch_add(&a.st->claims, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (at < WIRE_ROUTE_MAX_BUCKETS) a.list[at] = (uint32_t)i;
+}
+
+// One workgroup, behind the kernel boundary of the claims. The starts are distinct, so a start's rank is the number
+// of smaller ones: every thread counts them over the LDS copy, which all lanes read at the same address.
+__global__ __launch_bounds__(1024) void wire_route_sort_kernel(WireRouteArgs a) {
+  __shared__ uint64_t keys[WIRE_ROUTE_MAX_BUCKETS];
+  const uint32_t m = a.st->claims, t = threadIdx.x;
+  if (m > WIRE_ROUTE_MAX_BUCKETS) return;  // too many buckets: the whole workgroup leaves
+  const uint32_t c = t < m ? a.list[t] : 0;
+  if (t < m) keys[t] = wire_bucket_start(a.times[c], a.precision);
+  __syncthreads();
+  if (t >= m) return;
+  const uint32_t r = wire_rank(keys, m, t);
+  a.rank[c] = r;
+  a.buckets[r] = WireBucket{keys[t], ~0ull, 0, 0, 0, wire_bucket_collected(a.collected, a.ncollected, keys[t]), 0};
+}
+
+__global__ __launch_bounds__(256) void wire_route_assign_kernel(WireRouteArgs a) {
+  if (a.st->claims > WIRE_ROUTE_MAX_BUCKETS) return;  // too many buckets: route stays as it is
+  const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+  const int lane = threadIdx.x & 63;
+  const bool active = i < a.n;
+  const uint64_t t = active ? a.times[i] : 0;
+  const uint64_t b = active ? wire_bucket_start(t, a.precision) : 0;
+  int my_lead = lane;
+  wave_groups(active, b, [&](int lead, bool in) { my_lead = in ? lead : my_lead; });
+  uint32_t k = WIRE_ROUTE_OUT;
+  if (active && my_lead == lane) {
+    const uint32_t c = wire_route_holder(b, a.times, a.precision, a.tab, a.slots, a.k0, a.k1);
+    if (c != WIRE_ROUTE_OUT) k = a.rank[c];
+  }
+  k = __shfl(k, my_lead);
+  const bool found = active && k < WIRE_ROUTE_MAX_BUCKETS;  // every bucket was claimed: a guard for the index below
+  const bool collected = found && a.buckets[k].collected != 0;
+  uint32_t to = WIRE_ROUTE_OUT;
+  if (found) {
+    to = wire_route_of(a.route[i], collected, k);
+    a.route[i] = to;
+    a.bucket_index[i] = k;
+    a.bucket_collected[i] = collected;
+  }
+  wave_groups(found, b, [&](int lead, bool in) {
+    const uint32_t reports = (uint32_t)__popcll(__ballot(in));
+    const uint32_t routed = (uint32_t)__popcll(__ballot(in && to != WIRE_ROUTE_OUT));
+    unsigned long long lo = in ? t : ~0ull, hi = in ? t : 0;
+    if (reports > 1)  // the same for all lanes
+      for (int d = 32; d; d >>= 1) {
+        const unsigned long long l2 = __shfl_xor(lo, d), h2 = __shfl_xor(hi, d);
+        lo = l2 < lo ? l2 : lo;
+        hi = h2 > hi ? h2 : hi;
+      }
+    if (lane != lead) return;
+    WireBucket* e = &a.buckets[k];
+    __hip_atomic_fetch_min((unsigned long long*)&e->min_time, lo, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_max((unsigned long long*)&e->max_time, hi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_add(&e->reports, reports, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (routed) __hip_atomic_fetch_add(&e->routed, routed, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  });
+}
+
 // ---- the response
 __global__ __launch_bounds__(256) void wire_resp_outcome_kernel(WireEncodeArgs a) {
   const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= a.n) return;
-  const uint8_t err = wire_outcome(a.host_err ? a.host_err[i] : (uint8_t)WIRE_ERR_NONE, a.open_status[i],
-                                   a.has_deadline && a.times[i] > a.deadline, a.wire_status[i], a.verdicts[i],
-                                   a.replayed && a.replayed[i]);
+  const uint8_t err = wire_outcome_routed(a.host_err ? a.host_err[i] : (uint8_t)WIRE_ERR_NONE, a.open_status[i],
+                                          a.has_deadline && a.times[i] > a.deadline, a.wire_status[i], a.verdicts[i],
+                                          a.replayed && a.replayed[i], a.bucket_collected && a.bucket_collected[i]);
   a.err[i] = err;
   a.finished[i] = err == WIRE_ERR_NONE;
 }
@@ -352,6 +448,16 @@ hipError_t launch_wire_gather(const WireDecodeArgs& a, hipStream_t s) {
 hipError_t launch_wire_exclude(uint32_t* route, const uint8_t* mask, uint64_t n, hipStream_t s) {
   if (n == 0) return hipSuccess;
   hipLaunchKernelGGL(wire_exclude_kernel, dim3(blocks(n, 256)), dim3(256), 0, s, route, mask, n);
+  return hipGetLastError();
+}
+
+hipError_t launch_wire_route(const WireRouteArgs& a, hipStream_t s) {
+  hipLaunchKernelGGL(wire_route_claim_kernel, dim3(blocks(a.n, 256)), dim3(256), 0, s, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(wire_route_sort_kernel, dim3(1), dim3(1024), 0, s, a);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(wire_route_assign_kernel, dim3(blocks(a.n, 256)), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 

@@ -206,6 +206,9 @@ WIRE_OK, WIRE_MALFORMED, WIRE_WRONG_QUERY_TYPE, WIRE_DUPLICATE_ID = 0, 1, 2, 3  
 WIRE_REPORT_ODD_PUBLIC_SHARE, WIRE_REPORT_NOT_INITIALIZE, WIRE_REPORT_ODD_PREP_SHARE = 1, 2, 3  # wire_status
 WIRE_NO_ERROR = 0xFF           # JX_WIRE_NO_ERROR: no host-resolved error for the report
 ROUTE_OUT = 0xFFFFFFFF         # route[i] of a report that must not reach an aggregation
+ROUTE_OK, ROUTE_TOO_MANY_BUCKETS, ROUTE_MAX_BUCKETS = 0, 1, 1024  # JX_ROUTE_*
+ROUTE_BUCKET = np.dtype([("start", "<u8"), ("min_time", "<u8"), ("max_time", "<u8"), ("reports", "<u4"), ("routed", "<u4"),
+                         ("collected", "<u4"), ("pad_", "<u4")])  # jx_route_bucket
 WIRE_RECORD = np.dtype([(name, "<u8") for name in ("off", "len", "public_share_off", "enc_off", "payload_off", "message_off",
                                                     "prep_msg_off", "prep_share_off")] +
                        [(name, "<u4") for name in ("public_share_len", "enc_len", "payload_len", "message_len",
@@ -299,8 +302,20 @@ class InitReq(_Req):
 
     def device_bytes(self, name: str):
         """One of the device arrays (report_ids, times, public_shares, leader_prep_shares, encs, enc_offsets, payloads,
-        payload_offsets, key_index, wire_status, route, records) as a torch uint8 tensor over the handle's memory."""
+        payload_offsets, key_index, wire_status, route, records; bucket_index, bucket_collected once the request is
+        routed) as a torch uint8 tensor over the handle's memory."""
         e, n = self._engine, self.n
+        if name in ("bucket_index", "bucket_collected"):
+            import torch
+
+            ptrs = (ctypes.c_void_p(), ctypes.c_void_p())
+            check(e._L.jx_init_req_route_arrays(self._h, ctypes.byref(ptrs[0]), ctypes.byref(ptrs[1])), e._h,
+                  "jx_init_req_route_arrays")
+            ptr, size = (ptrs[0].value, 4 * n) if name == "bucket_index" else (ptrs[1].value, n)
+            dev = torch.device("cuda", e.device)
+            if not size or not ptr:
+                return torch.zeros(0, dtype=torch.uint8, device=dev)
+            return torch.as_tensor(_DeviceBytes(ptr, size), device=dev)
         size = {"report_ids": 16 * n, "times": 8 * n, "public_shares": n * e.public_share_len,
                 "leader_prep_shares": n * e.prep_share_len, "encs": self.enc_bytes, "enc_offsets": 8 * (n + 1),
                 "payloads": self.payload_bytes, "payload_offsets": 8 * (n + 1), "key_index": 2 * n, "wire_status": n,
@@ -311,6 +326,20 @@ class InitReq(_Req):
         """Route the reports with mask[i] away from every aggregation (jx_init_req_exclude)."""
         m = _items(np.asarray(mask).astype(np.uint8), self.n, np.uint8)
         check(self._engine._L.jx_init_req_exclude(self._h, _ptr(m)), self._engine._h, "jx_init_req_exclude")
+
+    def route(self, time_precision: int, collected=()):
+        """Route the reports to their batch buckets, the report time rounded down to time_precision, on the GPU
+        (jx_init_req_route). collected: the starts of the batches that no longer accept aggregations, in any order.
+        Returns (ROUTE_OK, the bucket table as a ROUTE_BUCKET array, ascending by start): route[i] is then the index of
+        report i's bucket in the table, or ROUTE_OUT; or (ROUTE_TOO_MANY_BUCKETS, an empty table) for a request of
+        more than ROUTE_MAX_BUCKETS buckets, which leaves the request as it was."""
+        e = self._engine
+        col = np.ascontiguousarray(np.asarray(list(collected), dtype=np.uint64))
+        table = np.zeros(ROUTE_MAX_BUCKETS, ROUTE_BUCKET)
+        status, nb = ctypes.c_uint32(), ctypes.c_uint32()
+        check(e._L.jx_init_req_route(e._h, self._h, time_precision, _u64p(col) if col.size else None, col.size,
+                                     ctypes.byref(status), ctypes.byref(nb), _ptr(table)), e._h, "jx_init_req_route")
+        return int(status.value), table[:nb.value].copy()
 
 
 WIRE_RESP_MISMATCH = 4         # JX_WIRE_RESP_MISMATCH: the response's PrepareResps are not the sent reports in order

@@ -21,9 +21,17 @@ lengths than 32 are random bytes: those reports do not open.
   fused     jx_helper_prep_aggregate_encrypted_device on the decoded arrays, the same way
   host      tools/wire_split.cpp: one thread walking and splitting the same body (median of five after two warm-ups)
 
+  --route   the route leg alone (jx_init_req_route): a request of the same lengths filled with random bytes (the route
+            reads nothing but the times), its times spread over 1, 8 and 1,024 batch buckets of an hour. Checked first
+            against what a caller of the decode did before there was a route: np.unique(times - times % P,
+            return_inverse=True) on the pinned times, whose inverse is the route and whose values are the table. Timed
+            with device events around the call on a freshly decoded handle (a handle routes once) and by the host
+            clock; the caller's way, the np.unique and the copy of the n x 4-byte route to the device, by the host clock
+
 No threshold: the ratios are written down as found.
 
   python tools/bench_wire.py --out profiles/wire_decode.json
+  python tools/bench_wire.py --route --out profiles/wire_route.json
 """
 from __future__ import annotations
 
@@ -55,6 +63,97 @@ def split_exe() -> str:
     return exe
 
 
+def route_leg(a) -> int:
+    import random
+
+    import torch
+
+    from janus_amd.engine import KEY_NONE, ROUTE_OK, WIRE_OK, HelperEngine
+    from janus_amd.messages import (QUERY_TIME_INTERVAL, AggregationJobInitializeReq, HpkeCiphertext, PartialBatchSelector,
+                                    PingPongMessage, PrepareInit, ReportMetadata, ReportShare)
+    from janus_amd.vdaf import Prio3
+
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_wire needs a GPU (there is no CPU path)")
+    n, P = a.n, 3600
+    v = Prio3.sum_vec(8, 1000, 88)
+    rnd = random.Random(12)
+    t0 = 1_700_000_000 - 1_700_000_000 % P
+    parts = [(rnd.randbytes(16), rnd.randbytes(v.public_share_len), rnd.randbytes(32),
+              rnd.randbytes(22 + v.helper_input_share_len), rnd.randbytes(v.prep_share_len)) for _ in range(n)]
+    dev = torch.device("cuda", 0)
+    kf, ks = np.full(256, KEY_NONE, np.uint8), np.full(256, KEY_NONE, np.uint8)
+    kf[7] = 0
+    result = {"tool": "tools/bench_wire.py --route", "vdaf": v.name(), "n": n, "time_precision": P,
+              "device": torch.cuda.get_device_name(0),
+              "timing": f"medians of {a.runs} runs after {a.warmups} warm-ups; the route by device events on the engine "
+                        "stream around the call and by the host clock, the caller's way by the host clock", "buckets": {}}
+    with HelperEngine(v, bytes(range(16))) as eng:
+        s_eng = torch.cuda.ExternalStream(eng.stream())
+        for B in (1, 8, 1024):
+            times = np.array([t0 + (i * B // n) * P + i % P for i in range(n)], np.uint64)
+            body = AggregationJobInitializeReq(b"", PartialBatchSelector.time_interval(), tuple(
+                PrepareInit(ReportShare(ReportMetadata(rid, int(t)), ps, HpkeCiphertext(7, enc, pay)),
+                            PingPongMessage.initialize(lps)) for (rid, ps, enc, pay, lps), t in zip(parts, times))).encode()
+            d_body = torch.from_numpy(np.frombuffer(body, np.uint8).copy()).to(dev)
+            torch.cuda.synchronize()
+
+            def decode():
+                req = eng.decode_init_req(d_body, QUERY_TIME_INTERVAL, kf, ks, length=len(body))
+                assert req.status == WIRE_OK and req.n == n
+                return req
+
+            # ---- check: the device route against the caller's np.unique
+            with decode() as req:
+                starts, inverse = np.unique(req.times - req.times % np.uint64(P), return_inverse=True)
+                status, table = req.route(P)
+                route = req.device_bytes("route").cpu().numpy().view(np.uint32)
+                lo, hi = np.full(len(starts), np.iinfo(np.uint64).max, np.uint64), np.zeros(len(starts), np.uint64)
+                np.minimum.at(lo, inverse, req.times)
+                np.maximum.at(hi, inverse, req.times)
+                ok = (status == ROUTE_OK and np.array_equal(table["start"], starts) and np.array_equal(route, inverse)
+                      and np.array_equal(table["reports"], np.bincount(inverse)) and np.array_equal(table["routed"], table["reports"])
+                      and np.array_equal(table["min_time"], lo) and np.array_equal(table["max_time"], hi) and len(starts) == B)
+            if not ok:
+                raise SystemExit(f"bench_wire: the device route over {B} buckets differs from np.unique's")
+            # ---- timings
+            ev, host, caller = [], [], []
+            d_route = torch.zeros(n, dtype=torch.int32, device=dev)
+            for i in range(a.warmups + a.runs):
+                with decode() as req:
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    e0.record(s_eng)
+                    req.route(P)
+                    e1.record(s_eng)
+                    e1.synchronize()
+                    t_route = (time.perf_counter() - t) * 1e3
+                    t = time.perf_counter()
+                    _, inverse = np.unique(req.times - req.times % np.uint64(P), return_inverse=True)
+                    d_route.copy_(torch.from_numpy(inverse.astype(np.int32)))
+                    torch.cuda.synchronize()
+                    t_caller = (time.perf_counter() - t) * 1e3
+                    if i >= a.warmups:
+                        ev.append(e0.elapsed_time(e1))
+                        host.append(t_route)
+                        caller.append(t_caller)
+            r = {"body_bytes": len(body), "equals_np_unique": True,
+                 "route_device_ms_median": round(float(np.median(ev)), 3),
+                 "route_host_clock_ms_median": round(float(np.median(host)), 3),
+                 "caller_np_unique_and_copy_ms_median": round(float(np.median(caller)), 3),
+                 "route_device_ms": [round(x, 3) for x in ev]}
+            result["buckets"][str(B)] = r
+            print(f"{B} buckets: " + json.dumps(r), flush=True)
+    print(json.dumps(result), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as fh:
+            json.dump(result, fh, indent=1)
+            fh.write("\n")
+    return 0
+
+
 def main() -> int:
     ap = argparse.ArgumentParser()
     ap.add_argument("--n", type=int, default=16384)
@@ -62,7 +161,10 @@ def main() -> int:
     ap.add_argument("--warmups", type=int, default=2)
     ap.add_argument("--pool", default=None, help="an .npz to keep the reports in: read when it is there, written when not")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--route", action="store_true", help="the route leg alone")
     a = ap.parse_args()
+    if a.route:
+        return route_leg(a)
     n = a.n
 
     import torch
